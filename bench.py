@@ -8,14 +8,16 @@ over one batch of synthetic 640x480 frames already resident in HBM --
     mask gate (31x31 closing + keypoint removal)                [HIP]
     blur + rBRIEF descriptors                                   [HIP]
     N x N best-2 Hamming match of frame k against frame k-1     [HIP]
-(Tracking.cc:366 -> Frame.cc:491-496,633 -> ORBmatcher).  `value` is that.  The same JSON line carries the
-mask-off sub-leg (`extract_match_leg`, BASELINE configs[1]: extract + match only, the part that is hand-written
-HIP), its HBM `roofline` for the dominant kernel, `roofline_mask` (achieved fp32 TFLOP/s of the network against
-the MFMA fp32 peak) and `cpu_baseline` (the CPU oracle on all granted host cores, plus one thread).
+(Tracking.cc:366 -> Frame.cc:491-496,633 -> ORBmatcher).  `value` is that.  A plain run does only that: set-up,
+warm-up, the timed steps, the outputs of the last step under --dump-outputs DIR, the JSON line.  With --full the same
+line also carries the mask-off sub-leg (`extract_match_leg`, BASELINE configs[1]: extract + match only, the part that
+is hand-written HIP), its HBM `roofline` for the dominant kernel, `roofline_mask` (achieved fp32 TFLOP/s of the network
+against the MFMA fp32 peak), the gated match, the one-frame `drop_in_latency`, the per-rank result digests and
+`cpu_baseline` (the CPU oracle on all granted host cores, plus one thread).
 
 One process per GPU; rank r works on its own synthetic stream r (frames are independent: no data-path
-collective, weak scaling); RCCL is used only for the barrier / max-over-ranks time and the final gather of the
-per-frame result digests.  `python bench.py --gpus N` with N > 1 and no launcher environment starts
+collective, weak scaling); RCCL is used only for the barrier / max-over-ranks time and (--full) the final gather of
+the per-frame result digests.  `python bench.py --gpus N` with N > 1 and no launcher environment starts
 `python -m torch.distributed.run` itself (before anything touches a GPU) and relays rank 0's line.
 
 Prints ONE JSON line on rank 0 (see README / DESIGN.md for the fields).
@@ -378,6 +380,54 @@ def use_mask_cfg(args):
     return bool(CONFIGS[args.config].get("mask"))
 
 
+DUMP_BYTES = 60_000_000  # every array --dump-outputs writes, together (the limit is 64 MB)
+DUMP_MASK_BYTES = 24_000_000  # of which the masks of a mask-on run
+
+
+def dump_outputs(path, lanes, bl, cap, masked, width, height):
+    """The arrays a caller of the timed path receives after its last step, as float32 .npy files under `path`.  Frames are numbered
+    across the step's batch (lane li holds frames li * bl ... li * bl + bl - 1).  When a step holds more frames than DUMP_BYTES allows,
+    a fixed sample of them (seeded, the same for the same arguments) is written; the mask-on run's masks are a smaller sample of their own.
+      frame_index [F]          frames written, ascending
+      keypoint_counts [F]      keypoints of each of those frames
+      keypoints [K, 7]         x, y, size, angle, response, octave, class_id of every keypoint of those frames, frame after frame
+      descriptors [K, 32]      the 32 descriptor bytes of each keypoint
+      matches [K, 4]           best_idx, best_dist, second_idx, second_dist of each keypoint against the lane's previous frame
+      mask_frame_index [M]     (mask-on runs) frames whose masks are written, ascending
+      masks [M, height, width] (mask-on runs) the person mask the gate used"""
+    n_frames = bl * len(lanes)
+    rng = np.random.default_rng(0)
+    mask_bytes = width * height * 4
+    n_mask = min(n_frames, max(1, DUMP_MASK_BYTES // mask_bytes)) if masked else 0
+    row_bytes = (7 + 32 + 4) * 4  # keypoints + descriptors + matches of one keypoint; a frame has at most cap + 1 of them
+    n_kp = min(n_frames, max(1, (DUMP_BYTES - n_mask * mask_bytes - 8 * n_frames) // ((cap + 1) * row_bytes)))
+
+    def sample(n):
+        return np.arange(n_frames) if n == n_frames else np.sort(rng.choice(n_frames, n, replace=False))
+
+    frames = sample(n_kp)
+    mask_frames = sample(n_mask) if masked else None
+    matches_of = {}
+    counts, kps, descs, matches = [], [], [], []
+    for g in frames:
+        li, f = int(g // bl), int(g % bl)
+        if li not in matches_of:
+            matches_of[li] = lanes[li].d_match[:bl].cpu().numpy()
+        k, d = lanes[li].ext.batch_fetch(f)
+        counts.append(len(k))
+        kps.append(np.stack([k[name].astype(np.float32) for name in k.dtype.names], axis=1))
+        descs.append(d.astype(np.float32))
+        matches.append(matches_of[li][f, :len(k)].astype(np.float32))
+    out = {"frame_index": frames.astype(np.float32), "keypoint_counts": np.array(counts, np.float32),
+           "keypoints": np.concatenate(kps), "descriptors": np.concatenate(descs), "matches": np.concatenate(matches)}
+    if masked:
+        out["mask_frame_index"] = mask_frames.astype(np.float32)
+        out["masks"] = np.stack([lanes[g // bl].masks[int(g % bl)].cpu().numpy().astype(np.float32) for g in mask_frames])
+    os.makedirs(path, exist_ok=True)
+    for name, arr in out.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -386,9 +436,9 @@ def main():
     ap.add_argument("--batch", type=int, default=0, help="frames per step per GPU of the headline config (default 128 = 2 lanes x 64 with the mask; 512 for c2; 128 for c5)")
     ap.add_argument("--config", choices=sorted(CONFIGS), default="c3", help="c3 = BASELINE configs[2] (default, the metric as written); c2 = configs[1]; c5 = configs[4]")
     ap.add_argument("--streams", type=int, default=0, help="independent lanes (handle + HIP streams) the batch is split over")
-    ap.add_argument("--leg-steps", type=int, default=100, help="timed steps of the mask-off extract+match sub-leg of a c3 run (0 = skip the leg)")
+    ap.add_argument("--leg-steps", type=int, default=100, help="timed steps of the mask-off extract+match sub-leg of a c3 --full run (0 = skip the leg)")
     ap.add_argument("--leg-batch", type=int, default=512, help="frames per step of that sub-leg (4 lanes)")
-    ap.add_argument("--cpu-frames", type=int, default=-1, help="frames of the 1-thread CPU baseline sample (0 = skip the CPU baseline)")
+    ap.add_argument("--cpu-frames", type=int, default=-1, help="frames of the 1-thread CPU baseline sample of a --full run (0 = skip the CPU baseline)")
     ap.add_argument("--cpu-cores", type=int, default=-1, help="processes of the all-cores CPU baseline (default: every granted core, bounded by a cgroup quota and memory; 0 = skip)")
     ap.add_argument("--tum-root", default=os.environ.get("AMOS_TUM_ROOT", ""), help="directory holding TUM RGB-D sequences (default $AMOS_TUM_ROOT): the 640x480 "
                     "configs then run on real frames (BASELINE north_star: fr3/walking_xyz) instead of the synthetic stream")
@@ -401,10 +451,16 @@ def main():
     ap.add_argument("--mask-chunk", type=int, default=0, help="frames per network forward (default: frames per lane)")
     ap.add_argument("--match-kernel", choices=["auto", "popcount", "mfma"], default="auto", help="brute-force matcher kernel (identical results; A/B switch)")
     ap.add_argument("--latency-frames", type=int, default=30, help="frames of the single-frame drop-in latency measurement reported as the extra key "
-                    "`drop_in_latency` (rank 0 of a one-GPU run, after every timed region; 0 = skip); never part of `value`")
+                    "`drop_in_latency` (rank 0 of a one-GPU --full run, after every timed region; 0 = skip); never part of `value`")
     ap.add_argument("--check", action="store_true", help="verify frames of the batch against the oracle")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: the mask-off extract+match leg, the rooflines, "
+                    "the gated match, the drop-in latency, the CPU baseline and the per-rank digests (without it: only the headline's timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write what the timed path computed in its last step (rank 0) to DIR/<name>.npy, "
+                    "float32, at most 64 MB in all (a seeded sample of the frames when a step holds more)")
     ap.add_argument("--dry-run", action="store_true", help="launcher / collective rehearsal without a GPU (value null)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(self_launch(args))
@@ -443,8 +499,8 @@ def main():
     while B % S:
         S -= 1
     Bl = B // S  # frames per lane and step
-    # the mask-off sub-leg of a c3 run uses BASELINE configs[1]'s shape: leg_batch frames over 4 lanes
-    leg = use_mask and args.leg_steps > 0
+    # the mask-off sub-leg of a c3 --full run uses BASELINE configs[1]'s shape: leg_batch frames over 4 lanes
+    leg = args.full and use_mask and args.leg_steps > 0
     legS = 4 if leg else 0
     legB = (args.leg_batch // 4) * 4 if leg else 0
     legBl = legB // 4 if leg else 0
@@ -506,7 +562,8 @@ def main():
             b[1, 3] += 5.5
             head.copy_(b.view(-1).to(head.device))
         engine.prepare()  # fold the batch norms into the convolutions (inference form)
-        net_flops, net_flops_executed = count_network_flops(torch, engine, min(chunk, 4), chunk)
+        if args.full:  # for roofline_mask: one forward of its own through the library convolutions
+            net_flops, net_flops_executed = count_network_flops(torch, engine, min(chunk, 4), chunk)
 
     def assign(nl, bl):
         """frames [li * bl, (li + 1) * bl) of the resident stream -> lane li"""
@@ -597,10 +654,12 @@ def main():
     active = assign(S, Bl)
     elapsed, stage_ms = run_leg(active, Bl, use_mask, args.steps, args.warmup)
     fps = world * B * args.steps / elapsed
+    if args.dump_outputs and rank == 0:  # before anything else runs on the lanes' buffers
+        dump_outputs(args.dump_outputs, active, Bl, cap, use_mask, W, H)
     digest = frame_digest(lanes[0], Bl)
     n_kp = digest[0::3]
     mean_kp = float(np.mean(n_kp))
-    digest_all = shard.gather_digests(digest, coll_dev)  # the one collective of the path
+    digest_all = shard.gather_digests(digest, coll_dev) if args.full else None
 
     checked, mask_iou = None, None
     if args.check and rank == 0:
@@ -632,14 +691,14 @@ def main():
                 assert iou >= 1 - 1e-3, f"lane 0 frame {f}: mask of the {Bl}-frame launch vs the one-frame pass: IoU {iou}"
                 mask_iou.append(round(iou, 6))
 
-    # ---------------------------------------------------------------- mask-off extract+match leg (c3 runs) or the same leg's extras
+    # ---------------------------------------------------------------- --full: mask-off extract+match leg (c3 runs) or the same leg's extras
     em = None  # dict describing the extract+match measurement the roofline refers to
-    if use_mask and leg:
+    if leg:
         em_active = assign(legS, legBl)
         em_elapsed, em_stage = run_leg(em_active, legBl, False, args.leg_steps, 3)
         em = dict(S=legS, Bl=legBl, B=legB, steps=args.leg_steps, elapsed=em_elapsed, stage_ms=em_stage,
                   fps=world * legB * args.leg_steps / em_elapsed, mean_kp=float(np.mean(frame_digest(lanes[0], legBl)[0::3])))
-    elif not use_mask:
+    elif args.full and not use_mask:
         em = dict(S=S, Bl=Bl, B=B, steps=args.steps, elapsed=elapsed, stage_ms=stage_ms, fps=fps, mean_kp=mean_kp)
     alone_ms = None
     if em and em["S"] > 1:
@@ -691,7 +750,7 @@ def main():
     #   ctypes_mirror -- the same C ABI driven from Python with persistent handles (amos-slam_amd/__init__.py; NOT what the reference's C++ links):
     #                    the same call sequence up to the descriptors (mask session, detect, gate, describe), then an N x N best-2 match
     latency = None
-    if rank == 0 and world == 1 and args.latency_frames > 0 and (W, H) == (640, 480):
+    if args.full and rank == 0 and world == 1 and args.latency_frames > 0 and (W, H) == (640, 480):
         try:
             n = args.latency_frames
             lat_ext = pkg.OrbExtractor(n_features=cfg["n_features"], n_levels=cfg["n_levels"], max_width=W, max_height=H, max_batch=1, device=local_rank)
@@ -799,8 +858,9 @@ def main():
                                                  else "n/a: frames of " + data_label + " from frame %d on" % tum_source[4]),
                        "parallelism": f"frames sharded {world} ways, one process per GPU, no data-path collective"},
             "stage_ms_per_launch": {k: round(v, 4) for k, v in stage_ms.items()},
-            "digest_per_rank": {"layout": "per frame of the rank's first lane: keypoints, CRC32 of descriptor bytes, matches <= TH_LOW", "rows": digest_all},
         }
+        if digest_all is not None:
+            out["digest_per_rank"] = {"layout": "per frame of the rank's first lane: keypoints, CRC32 of descriptor bytes, matches <= TH_LOW", "rows": digest_all}
         if checked is not None:
             out["oracle_checked_frames"] = checked
             if use_mask:
@@ -811,6 +871,7 @@ def main():
         if use_mask:
             out["config"]["mask"] = {"network": "YOLACT-R50-FPN 550x550, %s, batch-norm folded, NHWC, random weights (no checkpoint offline)" % args.mask_conv_dtype,
                                      "frames_per_forward": chunk}
+        if use_mask and net_flops is not None:
             n_fwd = (Bl + chunk - 1) // chunk
             net_ms = stage_ms.get("mask_pass", 0.0)
             step_s = elapsed / args.steps
@@ -895,7 +956,7 @@ def main():
         if latency:
             out["drop_in_latency"] = latency
         n_cpu = args.cpu_frames if args.cpu_frames >= 0 else (100 if W == 640 else 12)
-        if world == 1 and n_cpu > 0:
+        if args.full and world == 1 and n_cpu > 0:
             granted, quota = granted_cores()
             cores = args.cpu_cores if args.cpu_cores >= 0 else all_cores_worker_count()
             one = cpu_baseline_one_thread(synth, cfg, n_cpu, tum_source or ("synth", 0))

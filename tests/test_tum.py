@@ -100,7 +100,7 @@ def test_bench_cpu_leg_reads_the_sequence(tum, fake_root, ob, synth):
 def test_bench_on_a_tum_sequence(gpu_lib, fake_root):
     """`bench.py --config c2 --tum-root ...`: real frames resident in HBM, checked against the oracle, `data` says which sequence."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c2", "--steps", "2", "--warmup", "1", "--batch", "8", "--cpu-frames", "2",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", "c2", "--steps", "2", "--warmup", "1", "--batch", "8", "--cpu-frames", "2",
                           "--cpu-cores", "2", "--check", "--tum-root", fake_root], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])

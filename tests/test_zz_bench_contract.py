@@ -48,8 +48,8 @@ def _common(d, steps, warmup):
 
 @pytest.mark.gpu
 def test_default_run_is_the_baseline_metric_with_the_mask(gpu_lib):
-    """`python bench.py --gpus 1` times BASELINE.json configs[2] (mask on) and carries the mask-off leg beside it."""
-    d = _run(["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "8", "--leg-steps", "3", "--leg-batch", "64", "--cpu-frames", "3",
+    """`python bench.py --gpus 1 --full` times BASELINE.json configs[2] (mask on) and carries the mask-off leg beside it."""
+    d = _run(["--gpus", "1", "--full", "--steps", "2", "--warmup", "1", "--batch", "8", "--leg-steps", "3", "--leg-batch", "64", "--cpu-frames", "3",
               "--cpu-cores", "2", "--check"])
     _common(d, 2, 1)
     assert "+mask" in d["metric"] and "configs[2]" in d["config"]["workload"]
@@ -85,8 +85,30 @@ def test_default_run_is_the_baseline_metric_with_the_mask(gpu_lib):
 
 @pytest.mark.gpu
 def test_mask_off_config(gpu_lib):
-    d = _run(["--gpus", "1", "--config", "c2", "--steps", "4", "--warmup", "1", "--batch", "64", "--cpu-frames", "3", "--cpu-cores", "2", "--check"])
+    d = _run(["--gpus", "1", "--full", "--config", "c2", "--steps", "4", "--warmup", "1", "--batch", "64", "--cpu-frames", "3", "--cpu-cores", "2", "--check"])
     _common(d, 4, 1)
     assert "mask off" in d["metric"] and d["dtype"] == "u8" and "configs[1]" in d["config"]["workload"]
     assert abs(d["value"] - 64 * 4 / (d["ms_per_step"] * 4 * 1e-3)) / d["value"] < 0.01
     assert "extract_match_leg" not in d and d["stage_ms_per_launch"]["fast"] > 0
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_headline_only_and_dumps_its_outputs(gpu_lib, tmp_path):
+    """Without --full the line holds the headline and nothing that needs runs of its own; --dump-outputs writes the last timed step's
+    keypoints, descriptors, matches and masks as float32 arrays."""
+    import numpy as np
+    d = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "8", "--check", "--dump-outputs", str(tmp_path)])
+    assert "+mask" in d["metric"] and "fp32" in d["dtype"] and d["unit"] == "frames/s" and d["higher_is_better"] is True
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["oracle_checked_frames"] == 2
+    assert abs(d["value"] - 8 * 3 / (d["ms_per_step"] * 3 * 1e-3)) / d["value"] < 0.01
+    for k in ("extract_match_leg", "roofline", "roofline_mask", "pipeline_roofline", "gated_match", "drop_in_latency", "cpu_baseline", "digest_per_rank"):
+        assert k not in d, k
+    a = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert set(a) == {"frame_index", "keypoint_counts", "keypoints", "descriptors", "matches", "mask_frame_index", "masks"}
+    assert all(v.dtype == np.float32 for v in a.values()) and sum(os.path.getsize(tmp_path / f) for f in os.listdir(tmp_path)) <= 64e6
+    assert a["frame_index"].tolist() == list(range(8)) and a["mask_frame_index"].tolist() == list(range(8))
+    n = int(a["keypoint_counts"].sum())
+    assert a["keypoints"].shape == (n, 7) and a["descriptors"].shape == (n, 32) and a["matches"].shape == (n, 4) and a["masks"].shape == (8, 480, 640)
+    assert a["descriptors"].min() >= 0 and a["descriptors"].max() <= 255 and np.all(a["descriptors"] == np.round(a["descriptors"]))
+    # lane 0 holds frames 0 - 3 (2 lanes of 4): the line's mean keypoint count is of those frames
+    assert abs(float(a["keypoint_counts"][:4].mean()) - d["config"]["mean_keypoints_per_frame"]) <= 0.05

@@ -10,12 +10,12 @@ cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/prof_r4
 rm -rf $O; mkdir -p $O
-timeout -k 10 500 python3 $R/bench.py --gpus 1 --check > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -5 $O/bench.err; exit 1; }
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --gpus 1 --steps 6 --warmup 2 --leg-steps 20 --cpu-frames 0 > $O/trace.log 2>&1 || { echo "trace failed"; tail -5 $O/trace.log; exit 1; }
+timeout -k 10 500 python3 $R/bench.py --gpus 1 --full --check > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -5 $O/bench.err; exit 1; }
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --gpus 1 --full --steps 6 --warmup 2 --leg-steps 20 --cpu-frames 0 > $O/trace.log 2>&1 || { echo "trace failed"; tail -5 $O/trace.log; exit 1; }
 i=0
 for set in "FETCH_SIZE" "WRITE_SIZE" "SQ_INSTS_VALU SQ_WAVES SQ_INSTS_SALU SQ_INSTS_LDS" "SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES GRBM_GUI_ACTIVE"; do
   i=$((i+1))
-  timeout -k 10 300 rocprofv3 --pmc $set --output-format csv -d $O/pmc$i -- python3 $R/bench.py --gpus 1 --config c2 --steps 3 --warmup 1 --cpu-frames 0 > $O/pmc$i.log 2>&1 || { echo "pmc pass $i ($set) failed"; tail -3 $O/pmc$i.log; }
+  timeout -k 10 300 rocprofv3 --pmc $set --output-format csv -d $O/pmc$i -- python3 $R/bench.py --gpus 1 --full --config c2 --steps 3 --warmup 1 --cpu-frames 0 > $O/pmc$i.log 2>&1 || { echo "pmc pass $i ($set) failed"; tail -3 $O/pmc$i.log; }
 done
 tail -c 400 $O/bench.json
 # 4. one mask lane alone (where a pass spends its time) and the Winograd kernel's counters on the largest layer

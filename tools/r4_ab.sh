@@ -6,7 +6,7 @@ N=$1; shift
 for i in $(seq $N); do
   for v in "$@"; do
     if [ "$v" = base ]; then unset AMOS_FRONTEND_LIB; else export AMOS_FRONTEND_LIB=$R/amos-slam_amd/csrc/build/libamos_frontend_$v.so; fi
-    timeout -k 10 200 python3 $R/bench.py --config c2 --steps 40 --warmup 3 --cpu-frames 0 ${BENCH_EXTRA:-} 2>/dev/null | python3 -c "
+    timeout -k 10 200 python3 $R/bench.py --full --config c2 --steps 40 --warmup 3 --cpu-frames 0 ${BENCH_EXTRA:-} 2>/dev/null | python3 -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 while [ $# -ge 2 ]; do
   s=$1; b=$2; shift 2
-  timeout -k 10 300 python3 $R/bench.py --streams $s --batch $b --steps 10 --warmup 2 --leg-steps 0 --cpu-frames 0 2>/dev/null | python3 -c "
+  timeout -k 10 300 python3 $R/bench.py --full --streams $s --batch $b --steps 10 --warmup 2 --leg-steps 0 --cpu-frames 0 2>/dev/null | python3 -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):
