@@ -32,7 +32,7 @@ EXPORTS = [
     "amos_orb_stream", "amos_orb_timing_enable", "amos_orb_timing_collect", "amos_match_create", "amos_match_destroy", "amos_match_sync", "amos_match_stream",
     "amos_match_distances", "amos_match_list_distances", "amos_match_list_best2", "amos_match_bruteforce_best2",
     "amos_match_bruteforce_best2_batch_device", "amos_match_set_bruteforce_kernel", "amos_slic_center_count", "amos_slic_create", "amos_slic_destroy", "amos_slic_stream",
-    "amos_slic_run", "amos_slic_batch_device", "amos_cluster_kmeans_batch_device", "amos_cluster_kmeans", "amos_cluster_bgr2lab_batch_device", "amos_flow_check_device", "amos_flow_epipolar_device", "amos_flow_scene_flow_device", "amos_flow_fundamental_score_device", "amos_flow_pnp_score_device", "amos_lk_create", "amos_lk_destroy", "amos_lk_stream", "amos_lk_levels", "amos_lk_track_device", "amos_mask_pre_create", "amos_mask_pre_destroy", "amos_mask_pre_stream", "amos_mask_preprocess_batch_device", "amos_mask_bias_act_device", "amos_mask_bias_relu_maxpool_device", "amos_mask_stem_weight_floats", "amos_mask_stem_weights_device", "amos_mask_stem_device", "amos_mask_conv1x1_supported", "amos_mask_conv1x1_device", "amos_mask_conv_supported", "amos_mask_conv_device", "amos_mask_conv_workspace_bytes", "amos_mask_conv_ws_device", "amos_mask_conv_tile_mode", "amos_mask_conv_kernel_name", "amos_corners_create", "amos_corners_destroy", "amos_corners_stream", "amos_corners_good_features_device", "amos_corners_candidate_count", "amos_corners_subpix_device", "amos_mask_winograd_supported", "amos_mask_winograd_weight_floats", "amos_mask_winograd_weights_device", "amos_mask_winograd_conv_device", "amos_mask_winograd24_weight_floats", "amos_mask_winograd24_weights_device", "amos_mask_winograd24_conv_device", "amos_mask_winograd24_conv_layout_device", "amos_mask_winograd24_persistent_mode", "amos_mask_winograd24_narrow_mode", "amos_mask_bilinear_nhwc_device", "amos_mask_bilinear_nhwc_act_device", "amos_mask_bilinear_x2_mode", "amos_mask_nms_column_max_device", "amos_mask_class_scores_device", "amos_mask_person_mask_device", "amos_mask_head_outputs_device", "amos_mask_head_outputs_scores_device", "amos_mask_person_masks_scores_device", "amos_mask_topk_rows_device", "amos_mask_topk_rows_sparse_device", "amos_mask_post_workspace_bytes", "amos_mask_person_masks_device", "amos_orb_detect_color_with_mask_pre_batch_device",
+    "amos_slic_run", "amos_slic_batch_device", "amos_cluster_kmeans_batch_device", "amos_cluster_kmeans", "amos_cluster_bgr2lab_batch_device", "amos_flow_check_device", "amos_flow_epipolar_device", "amos_flow_scene_flow_device", "amos_flow_fundamental_score_device", "amos_flow_pnp_score_device", "amos_lk_create", "amos_lk_destroy", "amos_lk_stream", "amos_lk_levels", "amos_lk_track_device", "amos_mask_pre_create", "amos_mask_pre_destroy", "amos_mask_pre_stream", "amos_mask_preprocess_batch_device", "amos_mask_bias_act_device", "amos_mask_bias_relu_maxpool_device", "amos_mask_stem_weight_floats", "amos_mask_stem_weights_device", "amos_mask_stem_device", "amos_mask_conv1x1_supported", "amos_mask_conv1x1_device", "amos_mask_conv_supported", "amos_mask_conv_device", "amos_mask_conv_workspace_bytes", "amos_mask_conv_ws_device", "amos_mask_conv_tile_mode", "amos_mask_conv_kernel_name", "amos_corners_create", "amos_corners_destroy", "amos_corners_stream", "amos_corners_good_features_device", "amos_corners_candidate_count", "amos_corners_subpix_device", "amos_fmat_create", "amos_fmat_destroy", "amos_fmat_stream", "amos_fmat_ransac_device", "amos_fmat_scene_flow_pair_device", "amos_fmat_ransac", "amos_mask_winograd_supported", "amos_mask_winograd_weight_floats", "amos_mask_winograd_weights_device", "amos_mask_winograd_conv_device", "amos_mask_winograd24_weight_floats", "amos_mask_winograd24_weights_device", "amos_mask_winograd24_conv_device", "amos_mask_winograd24_conv_layout_device", "amos_mask_winograd24_persistent_mode", "amos_mask_winograd24_narrow_mode", "amos_mask_bilinear_nhwc_device", "amos_mask_bilinear_nhwc_act_device", "amos_mask_bilinear_x2_mode", "amos_mask_nms_column_max_device", "amos_mask_class_scores_device", "amos_mask_person_mask_device", "amos_mask_head_outputs_device", "amos_mask_head_outputs_scores_device", "amos_mask_person_masks_scores_device", "amos_mask_topk_rows_device", "amos_mask_topk_rows_sparse_device", "amos_mask_post_workspace_bytes", "amos_mask_person_masks_device", "amos_orb_detect_color_with_mask_pre_batch_device",
 ]
 
 
@@ -848,3 +848,51 @@ class CornerDetector:
         _check(self.L.amos_corners_subpix_device(self.h, C.c_void_p(gray_ptr), C.c_size_t(stride), C.c_int(width), C.c_int(height), C.c_void_p(xy_ptr),
                                                  C.c_void_p(count_ptr), C.c_int(n), C.c_int(win), C.c_int(max_count), C.c_double(epsilon)),
                "amos_corners_subpix_device")
+
+
+class FundamentalRansac:
+    """amos_fmat_*: cv::findFundamentalMat(p1, p2, FM_RANSAC, threshold, confidence) of Tracking::GetSceneFlowObj (Tracking.cc:927, 945) on the
+    device (restated, parity with OpenCV unpinned).  status = (result, inliers, iterations, points): result 1 model, 0 none, -1 for
+    7 <= points < 15 (OpenCV's LMeDS branch, not built), -2 sampler cap, -3 count out of range."""
+
+    def __init__(self, max_points=4096, max_problems=64, device=0, stream=None):
+        self.L = lib()
+        self.L.amos_fmat_stream.restype = C.c_void_p
+        self.L.amos_fmat_stream.argtypes = [C.c_void_p]
+        self.L.amos_fmat_destroy.restype = None
+        self.L.amos_fmat_destroy.argtypes = [C.c_void_p]
+        h = C.c_void_p()
+        _check(self.L.amos_fmat_create(C.c_int(device), C.c_void_p(stream), C.c_int(max_points), C.c_int(max_problems), C.byref(h)), "amos_fmat_create")
+        self.h = h
+        self.max_points = max_points
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.amos_fmat_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    @property
+    def stream(self):
+        return self.L.amos_fmat_stream(self.h)
+
+    def ransac(self, p1, p2, threshold=0.1, confidence=0.99, max_iters=1000):
+        """One problem from host arrays [n][2]: returns (F [3][3] float64, mask [n] uint8, status [4] int32)."""
+        p1 = np.ascontiguousarray(p1, np.float32).reshape(-1, 2)
+        p2 = np.ascontiguousarray(p2, np.float32).reshape(-1, 2)
+        assert len(p1) == len(p2)
+        F, mask, status = np.zeros(9), np.zeros(len(p1), np.uint8), np.zeros(4, np.int32)
+        _check(self.L.amos_fmat_ransac(self.h, C.c_int(len(p1)), _p(p1), _p(p2), C.c_double(threshold), C.c_double(confidence), C.c_int(max_iters),
+                                       _p(F), _p(mask), _p(status)), "amos_fmat_ransac")
+        return F.reshape(3, 3), mask, status
+
+    def ransac_device(self, n_problems, d_p1, d_p2, d_offsets, d_counts, d_select, d_F, d_status, d_mask=None, threshold=0.1, confidence=0.99, max_iters=1000):
+        _check(self.L.amos_fmat_ransac_device(self.h, C.c_int(n_problems), C.c_void_p(d_p1), C.c_void_p(d_p2), C.c_void_p(d_offsets), C.c_void_p(d_counts),
+                                              C.c_void_p(d_select), C.c_double(threshold), C.c_double(confidence), C.c_int(max_iters), C.c_void_p(d_F),
+                                              C.c_void_p(d_status), C.c_void_p(d_mask)), "amos_fmat_ransac_device")
+
+    def scene_flow_pair_device(self, d_pre, d_next, d_state, d_n, d_F1, d_F2, d_keep, d_status):
+        """Tracking.cc:927-945: F1 on state != 0, keep = dd <= 0.5 under F1, F2 on keep; d_status [2][4]."""
+        _check(self.L.amos_fmat_scene_flow_pair_device(self.h, C.c_void_p(d_pre), C.c_void_p(d_next), C.c_void_p(d_state), C.c_void_p(d_n), C.c_void_p(d_F1),
+                                                       C.c_void_p(d_F2), C.c_void_p(d_keep), C.c_void_p(d_status)), "amos_fmat_scene_flow_pair_device")

@@ -1,0 +1,355 @@
+// amos_fmat.hip -- cv::findFundamentalMat(p1, p2, FM_RANSAC, 0.1, 0.99) of Tracking::GetSceneFlowObj (src/Tracking.cc:927, 945) on the
+// device: the whole RANSAC (sampler, 7-point solver, scoring, best-model rule, iteration-count update) for n >= 15 correspondences.
+// The arithmetic is amos_fmat_core.h (restated; parity with OpenCV unpinned).
+//   k_fmat_ransac   ONE WORK-GROUP PER PROBLEM (a batch of problems is one launch).  The selected points go to LDS (16 B each), then
+//                   rounds of up to 64 iterations: wave 0 runs the serial RNG (every lane the same state, collinearity pairs over the
+//                   lanes) and draws the next subsets; one lane per subset solves run7Point; all waves score the up to 192 models over all
+//                   points (counts by wave reduction, no atomics); one lane replays the sequential loop in iteration order (best model,
+//                   niters).  The RNG consumption depends only on the points, never on the scores, so drawing ahead changes nothing.
+//   k_fmat_keep     Tracking.cc:928-944: keep = state != 0 && dd <= 0.5 under the first F (k_epipolar's arithmetic)
+#include "amos_common.h"
+#include "amos_fmat_core.h"
+
+namespace amos {
+
+constexpr int kFmatMaxPoints = 4096;
+constexpr int kFmatThreads = 512, kFmatWaves = kFmatThreads / 64;
+constexpr int kFmatRound = 64;
+
+struct FmatArgs {
+    const float2 *p1, *p2;
+    const int *offsets, *counts;
+    const uint8_t *select;
+    int maxPoints, maxIters;
+    float thresh2;
+    double confidence;
+    double *F;
+    int *status;
+    uint8_t *mask;
+};
+
+// the selected points of a problem in input order: calls f(input index i, compact index c or -1) for i < cnt (block-wide, in order)
+template <typename Fn>
+__device__ __forceinline__ int fmat_scan(const uint8_t *select, int off, int cnt, int *sWave, Fn f)
+{
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    int total = 0;
+    for (int base = 0; base < cnt; base += kFmatThreads) {
+        const int i = base + t;
+        const bool sel = i < cnt && (!select || select[off + i] != 0);
+        const unsigned long long b = __ballot(sel);
+        if (lane == 0) sWave[wv] = (int)__popcll(b);
+        __syncthreads();
+        int before = total, all = total;
+        for (int w = 0; w < kFmatWaves; w++) {
+            if (w < wv) before += sWave[w];
+            all += sWave[w];
+        }
+        if (i < cnt) f(i, sel ? before + (int)__popcll(b & ((1ull << lane) - 1ull)) : -1);
+        __syncthreads();
+        total = all;
+    }
+    return total;
+}
+
+__global__ __launch_bounds__(kFmatThreads) void k_fmat_ransac(const FmatArgs a)
+{
+    __shared__ float4 sPts[kFmatMaxPoints];                 // (x1, y1, x2, y2) of the selected points
+    __shared__ double sModel[kFmatRound * 3][9];
+    __shared__ int sCount[kFmatRound * 3], sNModels[kFmatRound], sSub[kFmatRound][7];
+    __shared__ double sBest[9];
+    __shared__ int sWave[kFmatWaves];
+    __shared__ int sDrawn, sStop, sResult, sIter, sNiters, sMaxGood;
+    const int p = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int off = a.offsets ? a.offsets[p] : p * a.maxPoints, cnt = a.counts[p];
+    double *Fout = a.F + (size_t)p * 9;
+    int *st = a.status + (size_t)p * 4;
+    if (cnt < 0 || cnt > a.maxPoints) {  // out of range: nothing is read, no mask written
+        if (t < 9) Fout[t] = 0.0;
+        if (t == 0) { st[0] = -3; st[1] = 0; st[2] = 0; st[3] = 0; }
+        return;
+    }
+    const int n = fmat_scan(a.select, off, cnt, sWave, [&](int i, int c) {
+        if (c >= 0) sPts[c] = make_float4(a.p1[off + i].x, a.p1[off + i].y, a.p2[off + i].x, a.p2[off + i].y);
+    });
+    if (t == 0) { sStop = 0; sResult = 0; sIter = 0; sNiters = a.maxIters; sMaxGood = 0; }
+    if (n < 15) {  // n < 7: no model; 7 <= n < 15: OpenCV's LMeDS / 7-point branches (not built here)
+        if (t < 9) Fout[t] = 0.0;
+        if (t == 0) { st[0] = n < 7 ? 0 : -1; st[1] = 0; st[2] = 0; st[3] = n; }
+        if (a.mask) for (int i = t; i < cnt; i += kFmatThreads) a.mask[off + i] = 0;
+        return;
+    }
+    __syncthreads();
+    uint64_t rng = ~0ull;  // cv::RNG rng((uint64)-1), wave 0's lanes hold identical copies
+    for (;;) {
+        const int iter0 = sIter, limit = min(kFmatRound, sNiters - iter0);
+        // ---- draw the subsets of iterations iter0 .. iter0 + limit - 1 (getSubset, maxAttempts 10000)
+        if (wv == 0) {
+            int drawn = 0, stop = 0;
+            for (int slot = 0; slot < limit; slot++) {
+                int idx[7];
+                bool found = false, cap = false;
+                for (int attempt = 0; attempt < fm::kMaxAttempts && !found && !cap; attempt++) {
+#pragma unroll
+                    for (int i = 0; i < 7; i++) {
+                        for (uint32_t draws = 1;; draws++) {
+                            const int v = (int)(fm::rng_next(rng) % (uint32_t)n);
+                            bool dup = false;
+#pragma unroll
+                            for (int j = 0; j < i; j++) dup |= v == idx[j];
+                            idx[i] = v;
+                            if (!dup) break;
+                            if (draws >= fm::kRedrawCap) { cap = true; break; }
+                        }
+                        if (cap) break;
+                    }
+                    if (cap) break;
+                    bool col = false;  // FMEstimatorCallback::checkSubset: lanes 0..14 set 1, 15..29 set 2
+                    if (lane < 30) {
+                        const int q = lane < 15 ? lane : lane - 15, j = FM_PAIR_J(q), k = FM_PAIR_K(q);
+                        int ij = idx[0], ik = idx[0];
+#pragma unroll
+                        for (int u = 1; u < 6; u++) { ij = u == j ? idx[u] : ij; ik = u == k ? idx[u] : ik; }
+                        const float4 Pj = sPts[ij], Pk = sPts[ik], Pi = sPts[idx[6]];
+                        col = lane < 15 ? fm::collinear3(Pj.x, Pj.y, Pk.x, Pk.y, Pi.x, Pi.y) : fm::collinear3(Pj.z, Pj.w, Pk.z, Pk.w, Pi.z, Pi.w);
+                    }
+                    found = __ballot(col) == 0ull;
+                }
+                if (cap) { stop = 2; break; }
+                if (!found) { stop = 1; break; }
+                if (lane < 7) {
+                    int v = idx[0];
+#pragma unroll
+                    for (int u = 1; u < 7; u++) v = u == lane ? idx[u] : v;
+                    sSub[slot][lane] = v;
+                }
+                drawn++;
+            }
+            if (lane == 0) { sDrawn = drawn; sStop = stop; }
+        }
+        __syncthreads();
+        const int drawn = sDrawn;
+        // ---- run7Point, one lane per subset
+        if (t < drawn) {
+            float x0[7], y0[7], x1[7], y1[7];
+#pragma unroll
+            for (int i = 0; i < 7; i++) {
+                const float4 P = sPts[sSub[t][i]];
+                x0[i] = P.x; y0[i] = P.y; x1[i] = P.z; y1[i] = P.w;
+            }
+            double F[27];
+            const int nm = fm::run7point(x0, y0, x1, y1, F);
+            sNModels[t] = nm;
+            for (int m = 0; m < nm; m++)
+#pragma unroll
+                for (int k = 0; k < 9; k++) sModel[3 * t + m][k] = F[9 * m + k];
+        }
+        __syncthreads();
+        // ---- scoring: model m = 3 * slot + root on wave m % kFmatWaves, points over the lanes
+        for (int m = wv; m < 3 * drawn; m += kFmatWaves) {
+            if (m % 3 >= sNModels[m / 3]) continue;  // wave-uniform
+            double F[9];
+#pragma unroll
+            for (int k = 0; k < 9; k++) F[k] = sModel[m][k];
+            int count = 0;
+            for (int i = lane; i < n; i += 64) {
+                const float4 P = sPts[i];
+                count += fm::point_error(F, P.x, P.y, P.z, P.w) <= a.thresh2 ? 1 : 0;
+            }
+            for (int d = 32; d > 0; d >>= 1) count += __shfl_xor(count, d, 64);
+            if (lane == 0) sCount[m] = count;
+        }
+        __syncthreads();
+        // ---- the sequential loop of RANSACPointSetRegistrator::run over this round's iterations
+        if (t == 0) {
+            int iter = iter0, niters = sNiters, maxGood = sMaxGood, stop = 0;
+            for (int slot = 0;; slot++) {
+                if (iter >= niters) break;
+                if (slot == drawn) {  // the sampler stopped here (or the round is used up)
+                    if (sStop == 2) { sResult = -2; stop = 1; }
+                    else if (sStop == 1) { stop = 1; if (iter == 0) maxGood = 0; }
+                    break;
+                }
+                for (int m = 0; m < sNModels[slot]; m++) {
+                    const int good = sCount[3 * slot + m];
+                    if (good > max(maxGood, fm::kModelPoints - 1)) {
+                        for (int k = 0; k < 9; k++) sBest[k] = sModel[3 * slot + m][k];
+                        maxGood = good;
+                        niters = fm::update_num_iters(a.confidence, fm::dvd((double)(n - good), (double)n), niters);
+                    }
+                }
+                iter++;
+            }
+            sIter = iter; sNiters = niters; sMaxGood = maxGood;
+            if (iter >= niters) stop = 1;
+            sStop = stop ? 3 : 0;
+        }
+        __syncthreads();
+        if (sStop == 3) break;
+    }
+    // ---- result, F, mask of the best model
+    const int result = sResult == -2 ? -2 : (sMaxGood > 0 ? 1 : 0), maxGood = result == 1 ? sMaxGood : 0;
+    if (t < 9) Fout[t] = result == 1 ? sBest[t] : 0.0;
+    if (t == 0) { st[0] = result; st[1] = maxGood; st[2] = sIter; st[3] = n; }
+    if (a.mask) {
+        double F[9];
+#pragma unroll
+        for (int k = 0; k < 9; k++) F[k] = sBest[k];
+        fmat_scan(a.select, off, cnt, sWave, [&](int i, int c) {
+            uint8_t v = 0;
+            if (c >= 0 && result == 1) {
+                const float4 P = sPts[c];
+                v = fm::point_error(F, P.x, P.y, P.z, P.w) <= a.thresh2 ? 1 : 0;
+            }
+            a.mask[off + i] = v;
+        });
+    }
+}
+
+// keep[i] = state[i] != 0 && dd[i] <= 0.5 with dd of Tracking.cc:930-935 under F1; all 0 when F1 is no model
+__global__ __launch_bounds__(256) void k_fmat_keep(const float2 *__restrict__ pre, const float2 *__restrict__ next, const uint8_t *__restrict__ state,
+                                                  const int *__restrict__ dN, int maxPoints, const double *__restrict__ F, const int *__restrict__ status1,
+                                                  uint8_t *__restrict__ keep)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x, n = *dN;
+    if (n < 0 || n > maxPoints || i >= n) return;
+    uint8_t k = 0;
+    if (status1[0] == 1 && state[i] != 0) {
+        const double px = pre[i].x, py = pre[i].y, qx = next[i].x, qy = next[i].y;
+        const double A = __dadd_rn(__dadd_rn(__dmul_rn(F[0], px), __dmul_rn(F[1], py)), F[2]);
+        const double B = __dadd_rn(__dadd_rn(__dmul_rn(F[3], px), __dmul_rn(F[4], py)), F[5]);
+        const double C = __dadd_rn(__dadd_rn(__dmul_rn(F[6], px), __dmul_rn(F[7], py)), F[8]);
+        const double num = fabs(__dadd_rn(__dadd_rn(__dmul_rn(A, qx), __dmul_rn(B, qy)), C));
+        k = __ddiv_rn(num, __dsqrt_rn(__dadd_rn(__dmul_rn(A, A), __dmul_rn(B, B)))) <= 0.5 ? 1 : 0;
+    }
+    keep[i] = k;
+}
+
+}  // namespace amos
+
+using namespace amos;
+
+struct amos_fmat {
+    int device = 0, maxPoints = 0, maxProblems = 0;
+    hipStream_t stream = nullptr;
+    bool ownStream = false;
+    float2 *dP1 = nullptr, *dP2 = nullptr;
+    int *dInt = nullptr;  // [0] zero offset, [1] count of the synchronous call, [2..5] its status
+    double *dF = nullptr;
+    uint8_t *dMask = nullptr;
+};
+
+static bool fmat_params_ok(double threshold, double confidence, int max_iters)
+{
+    return threshold > 0 && confidence > 0 && confidence < 1 && max_iters >= 1 && max_iters <= (1 << 20);
+}
+
+static int fmat_launch(amos_fmat *h, int n_problems, const float *d_p1, const float *d_p2, const int *d_offsets, const int *d_counts, const uint8_t *d_select,
+                       double threshold, double confidence, int max_iters, double *d_F, int *d_status, uint8_t *d_mask)
+{
+    FmatArgs a;
+    a.p1 = (const float2 *)d_p1; a.p2 = (const float2 *)d_p2;
+    a.offsets = d_offsets; a.counts = d_counts; a.select = d_select;
+    a.maxPoints = h->maxPoints; a.maxIters = max_iters;
+    a.thresh2 = (float)(threshold * threshold);  // findInliers: float t = (float)(thresh * thresh)
+    a.confidence = confidence;
+    a.F = d_F; a.status = d_status; a.mask = d_mask;
+    hipLaunchKernelGGL(k_fmat_ransac, dim3(n_problems), dim3(kFmatThreads), 0, h->stream, a);
+    AMOS_HIP_CHECK(hipGetLastError());
+    return AMOS_OK;
+}
+
+extern "C" {
+
+int amos_fmat_create(int device, void *stream, int max_points, int max_problems, amos_fmat **out)
+{
+    if (!out || max_points < 1 || max_points > kFmatMaxPoints || max_problems < 1) {
+        set_error("amos_fmat_create: invalid argument (1 <= max_points <= %d, max_problems >= 1)", kFmatMaxPoints);
+        return AMOS_ERR_INVALID;
+    }
+    *out = nullptr;
+    AMOS_HIP_CHECK(hipSetDevice(device));
+    amos_fmat *h = new amos_fmat();
+    h->device = device; h->maxPoints = max_points; h->maxProblems = max_problems;
+    if (stream) h->stream = (hipStream_t)stream;
+    else {
+        if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { set_error("hipStreamCreate failed"); delete h; return AMOS_ERR_DEVICE; }
+        h->ownStream = true;
+    }
+    hipError_t e = hipMalloc((void **)&h->dP1, sizeof(float2) * max_points);
+    if (e == hipSuccess) e = hipMalloc((void **)&h->dP2, sizeof(float2) * max_points);
+    if (e == hipSuccess) e = hipMalloc((void **)&h->dInt, sizeof(int) * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&h->dF, sizeof(double) * 9);
+    if (e == hipSuccess) e = hipMalloc((void **)&h->dMask, max_points);
+    if (e == hipSuccess) e = hipMemsetAsync(h->dInt, 0, sizeof(int) * 8, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) { set_error("amos_fmat_create: %s", hipGetErrorString(e)); amos_fmat_destroy(h); return AMOS_ERR_DEVICE; }
+    *out = h;
+    return AMOS_OK;
+}
+
+void amos_fmat_destroy(amos_fmat *h)
+{
+    if (!h) return;
+    (void)hipSetDevice(h->device);
+    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    for (void *q : {(void *)h->dP1, (void *)h->dP2, (void *)h->dInt, (void *)h->dF, (void *)h->dMask}) if (q) (void)hipFree(q);
+    if (h->ownStream && h->stream) (void)hipStreamDestroy(h->stream);
+    delete h;
+}
+
+void *amos_fmat_stream(amos_fmat *h) { return h ? (void *)h->stream : nullptr; }
+
+int amos_fmat_ransac_device(amos_fmat *h, int n_problems, const float *d_p1_xy, const float *d_p2_xy, const int32_t *d_offsets, const int32_t *d_counts,
+                            const uint8_t *d_select, double threshold, double confidence, int max_iters, double *d_F, int32_t *d_status, uint8_t *d_mask)
+{
+    if (!h || n_problems < 0 || n_problems > h->maxProblems || !d_p1_xy || !d_p2_xy || !d_counts || !d_F || !d_status ||
+        !fmat_params_ok(threshold, confidence, max_iters)) {
+        set_error("amos_fmat_ransac_device: invalid argument");
+        return AMOS_ERR_INVALID;
+    }
+    if (n_problems == 0) return AMOS_OK;
+    AMOS_HIP_CHECK(hipSetDevice(h->device));
+    return fmat_launch(h, n_problems, d_p1_xy, d_p2_xy, d_offsets, d_counts, d_select, threshold, confidence, max_iters, d_F, d_status, d_mask);
+}
+
+int amos_fmat_scene_flow_pair_device(amos_fmat *h, const float *d_pre_xy, const float *d_next_xy, const uint8_t *d_state, const int32_t *d_n, double *d_F1,
+                                     double *d_F2, uint8_t *d_keep, int32_t *d_status)
+{
+    if (!h || !d_pre_xy || !d_next_xy || !d_state || !d_n || !d_F1 || !d_F2 || !d_keep || !d_status) {
+        set_error("amos_fmat_scene_flow_pair_device: invalid argument");
+        return AMOS_ERR_INVALID;
+    }
+    AMOS_HIP_CHECK(hipSetDevice(h->device));
+    int rc = fmat_launch(h, 1, d_pre_xy, d_next_xy, h->dInt, d_n, d_state, 0.1, 0.99, 1000, d_F1, d_status, nullptr);
+    if (rc != AMOS_OK) return rc;
+    hipLaunchKernelGGL(k_fmat_keep, dim3((h->maxPoints + 255) / 256), dim3(256), 0, h->stream, (const float2 *)d_pre_xy, (const float2 *)d_next_xy, d_state, d_n,
+                       h->maxPoints, d_F1, d_status, d_keep);
+    AMOS_HIP_CHECK(hipGetLastError());
+    return fmat_launch(h, 1, d_pre_xy, d_next_xy, h->dInt, d_n, d_keep, 0.1, 0.99, 1000, d_F2, d_status + 4, nullptr);
+}
+
+int amos_fmat_ransac(amos_fmat *h, int n, const float *p1_xy, const float *p2_xy, double threshold, double confidence, int max_iters, double *F,
+                     uint8_t *mask, int32_t *status)
+{
+    if (!h || n < 0 || n > h->maxPoints || (n > 0 && (!p1_xy || !p2_xy)) || !F || !status || !fmat_params_ok(threshold, confidence, max_iters)) {
+        set_error("amos_fmat_ransac: invalid argument (n <= max_points)");
+        return AMOS_ERR_INVALID;
+    }
+    AMOS_HIP_CHECK(hipSetDevice(h->device));
+    if (n > 0) {
+        AMOS_HIP_CHECK(hipMemcpyAsync(h->dP1, p1_xy, sizeof(float2) * n, hipMemcpyHostToDevice, h->stream));
+        AMOS_HIP_CHECK(hipMemcpyAsync(h->dP2, p2_xy, sizeof(float2) * n, hipMemcpyHostToDevice, h->stream));
+    }
+    AMOS_HIP_CHECK(hipMemcpyAsync(h->dInt + 1, &n, sizeof(int), hipMemcpyHostToDevice, h->stream));
+    const int rc = fmat_launch(h, 1, (const float *)h->dP1, (const float *)h->dP2, h->dInt, h->dInt + 1, nullptr, threshold, confidence, max_iters, h->dF,
+                               h->dInt + 2, h->dMask);
+    if (rc != AMOS_OK) return rc;
+    AMOS_HIP_CHECK(hipMemcpyAsync(F, h->dF, sizeof(double) * 9, hipMemcpyDeviceToHost, h->stream));
+    AMOS_HIP_CHECK(hipMemcpyAsync(status, h->dInt + 2, sizeof(int) * 4, hipMemcpyDeviceToHost, h->stream));
+    if (mask && n > 0) AMOS_HIP_CHECK(hipMemcpyAsync(mask, h->dMask, n, hipMemcpyDeviceToHost, h->stream));
+    AMOS_HIP_CHECK(hipStreamSynchronize(h->stream));
+    return AMOS_OK;
+}
+
+}  // extern "C"

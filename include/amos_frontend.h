@@ -585,7 +585,7 @@ int amos_cluster_kmeans(amos_slic *s, amos_slic_center *centers, int n_centers, 
 
 /* The reference's own per-point arithmetic inside Tracking::GetSceneFlowObj (src/Tracking.cc:850-1186), between its
  * OpenCV calls (goodFeaturesToTrack, cornerSubPix, calcOpticalFlowPyrLK, findFundamentalMat, solvePnPRansac stay with
- * the caller).  Points are interleaved (x, y) float pairs; all pointers are device pointers; asynchronous on `stream`.
+ * the caller; device forms of the first four: amos_corners_*, amos_lk_*, amos_fmat_* below).  Points are interleaved (x, y) float pairs; all pointers are device pointers; asynchronous on `stream`.
  *
  * amos_flow_check_device (:902-925): state_out[i] = 0 when either position lies within 5 px of the image edge or the
  * 3 x 3 sum of absolute gray differences between (last, pre) and (cur, next) exceeds 2520; else state_in[i].  The
@@ -657,6 +657,41 @@ int amos_corners_good_features_device(amos_corners *c, const uint8_t *d_gray, si
 int amos_corners_candidate_count(amos_corners *c, int *count);
 int amos_corners_subpix_device(amos_corners *c, const uint8_t *d_gray, size_t stride, int width, int height, float *d_xy,
                                const int *d_count /* or NULL */, int n, int win, int max_count, double epsilon);
+
+/* cv::findFundamentalMat(p1, p2, FM_RANSAC, threshold, confidence) of Tracking::GetSceneFlowObj (Tracking.cc:927, 945) on the device:
+ * OpenCV 4.5's classic RANSAC (cv::RNG((uint64)-1) local to the call, getSubset with 10 000 attempts and the collinearity check,
+ * run7Point, FMEstimatorCallback::computeError, best model when inliers > max(best, 6), RANSACUpdateNumIters; no refit) restated
+ * from the published algorithm, written from memory: PARITY WITH OPENCV UNPINNED.  The SVD, the cubic solver and the log of the
+ * iteration count are replaced by + - * / sqrt constructions (amos_fmat_core.h), so the last bits differ
+ * from OpenCV's; the duplicate redraw of the sampler, unbounded in OpenCV, stops after 2^20 draws of one slot (status -2).
+ * One work-group per problem; a batch of problems is one launch; asynchronous on the handle's stream, no host synchronisation.
+ *
+ * amos_fmat_ransac_device: problem p reads the input points [d_offsets[p], d_offsets[p] + d_counts[p]) of d_p1_xy / d_p2_xy
+ * ((x, y) float pairs; d_offsets NULL: p * max_points) and uses those with d_select[i] != 0 (d_select NULL: all), in order --
+ * OpenCV's input list.  d_counts[p] <= max_points (else status -3).  Outputs: d_F [p][9] (row-major, F[8] = 1 or 0; zeros without
+ * a model), d_status [p][4] = {result, inliers, iterations run, points used} with result 1 = model, 0 = no model (fewer than 7
+ * points, or no subset passes the sampler at the first iteration), -1 = 7 <= points < 15 (OpenCV's LMeDS / 7-point branches,
+ * not built: keep OpenCV there), -2 = sampler redraw cap hit, -3 = count out of range; d_mask (or NULL) indexed like the input,
+ * 1 for the inliers of the returned model, 0 elsewhere and for points not selected.  threshold > 0, 0 < confidence < 1,
+ * 1 <= max_iters <= 2^20 (OpenCV: 0.1, 0.99, 1000 in the reference); n_problems <= max_problems.
+ *
+ * amos_fmat_scene_flow_pair_device: Tracking.cc:927-945 as one call on n = *d_n tracked points (n <= max_points): F1 on the points
+ * with d_state != 0; d_keep[i] = state != 0 && dd <= 0.5 under F1 (amos_flow_epipolar_device's arithmetic) -- the F_prepoint
+ * selection; F2 on the kept points.  d_status [2][4] (F1, F2).  Where F1 has no model the reference would fail on F.at(); here keep
+ * is all 0 and F2 is "no model" (result 0).
+ *
+ * amos_fmat_ransac: one problem from host pointers (n <= max_points), synchronous; mask (or NULL) [n], status [4]. */
+typedef struct amos_fmat amos_fmat;
+int amos_fmat_create(int device, void *stream, int max_points /* <= 4096 */, int max_problems, amos_fmat **out);
+void amos_fmat_destroy(amos_fmat *h);
+void *amos_fmat_stream(amos_fmat *h);
+int amos_fmat_ransac_device(amos_fmat *h, int n_problems, const float *d_p1_xy, const float *d_p2_xy, const int32_t *d_offsets,
+                            const int32_t *d_counts, const uint8_t *d_select, double threshold, double confidence, int max_iters,
+                            double *d_F, int32_t *d_status, uint8_t *d_mask);
+int amos_fmat_scene_flow_pair_device(amos_fmat *h, const float *d_pre_xy, const float *d_next_xy, const uint8_t *d_state,
+                                     const int32_t *d_n, double *d_F1, double *d_F2, uint8_t *d_keep, int32_t *d_status);
+int amos_fmat_ransac(amos_fmat *h, int n, const float *p1_xy, const float *p2_xy, double threshold, double confidence, int max_iters,
+                     double *F, uint8_t *mask, int32_t *status);
 
 #ifdef __cplusplus
 }
