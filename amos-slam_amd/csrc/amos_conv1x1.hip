@@ -48,14 +48,22 @@ struct ConvGemmArgs {
     int splits, stagesPerSplit;
     float *partial;              // [splits][mTiles * nTiles][BM * BN]
     unsigned *counters;          // [mTiles * nTiles], zero before the launch and after it
+    // kShortcut: a bottleneck's projection shortcut D = X0 * Wd + bd (1 x 1, stride sStride, input [.][sInH][sInW][sK]) computed by the same
+    // work-group before the main GEMM, over the same output tile; it stays in registers and is the residual of the epilogue
+    const float *sx, *sw, *sbias;
+    int sK, sStride, sInW, sInH;
 };
 
 // kTaps: a kh x kw convolution as an implicit GEMM.  The weight is [cout][kh][kw][cin] (a channels-last Conv2d weight), so the W tile
 // of stage s is simply 32 more floats along each row; the X tile of a stage belongs to ONE tap (cin % 32 == 0): row m reads input
 // pixel (oy * stride - pad + dy, ox * stride - pad + dx), or zeros outside the image.
-template <int WM, int WN, int TI, bool kTaps>  // waves along m and n; a wave's tile is 32 TI x 64
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_conv_gemm(const ConvGemmArgs a)  // LDS admits two groups per CU: 256 registers
+// kShortcut (1 x 1 only, no split-K): the first block of a ResNet stage as ONE launch -- y = relu((X * W + b) + D) with the projection
+// shortcut D = (X0 * Wd + bd) + 0 computed first over the same tile by the same k loop (the bits amos_mask_conv_device stores for D and then
+// reads back as the residual), so D never goes through memory.
+template <int WM, int WN, int TI, bool kTaps, bool kShortcut = false>  // waves along m and n; a wave's tile is 32 TI x 64
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_conv_gemm(const ConvGemmArgs args)  // LDS admits two groups per CU: 256 registers
 {
+    static_assert(!(kShortcut && kTaps), "the shortcut form is a pair of 1 x 1 GEMMs");
     constexpr int BM = 32 * TI * WM, BN = 64 * WN;
     constexpr int XP = BM / 32, WP = BN / 32;  // 16-byte pieces per thread and stage
     constexpr int kStage = (BM + BN) * kGemmPitch;  // floats of one stage: the X tile, then the W tile
@@ -67,12 +75,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
     // (split-K launches are small: there blockIdx.x IS the tile, so that consecutive tiles go to consecutive XCDs -- three m tiles would
     // otherwise put all work on three of the eight -- and the splits of a tile, blockIdx.y, still share one)
     const int xcd = blockIdx.x & 7, seq = blockIdx.x >> 3;
-    const int nt = a.splits > 1 ? (int)blockIdx.x % a.nTiles : seq % a.nTiles;
-    const int mt = a.splits > 1 ? (int)blockIdx.x / a.nTiles : (seq / a.nTiles) * 8 + xcd;
-    if (mt >= a.mTiles) return;
+    const int nt = args.splits > 1 ? (int)blockIdx.x % args.nTiles : seq % args.nTiles;
+    const int mt = args.splits > 1 ? (int)blockIdx.x / args.nTiles : (seq / args.nTiles) * 8 + xcd;
+    if (mt >= args.mTiles) return;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int wm = wave / WN, wn = wave % WN;
     const int pc = t & 7, pr = t >> 3;  // piece column (4 floats), first row of this thread's pieces
+    f32x16 acc[TI][2];
+    f32x16 dres[kShortcut ? TI : 1][2];  // kShortcut: the shortcut tile D, in the accumulators' layout
+    // phase 0 (kShortcut only): D over the shortcut's input and weight; phase 1: the convolution itself
+    for (int phase = kShortcut ? 0 : 1; phase < 2; phase++) {
+    ConvGemmArgs a = args;
+    if (kShortcut && phase == 0) {
+        a.x = args.sx; a.w = args.sw; a.K = args.sK; a.stride = args.sStride; a.inW = args.sInW; a.inH = args.sInH;
+    }
     const float *xsrc[XP];
     int iy0[XP], ix0[XP];  // kTaps: input coordinates of tap (0, 0)
 #pragma unroll
@@ -212,7 +228,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
         __builtin_amdgcn_sched_group_barrier(0x008, kMfmas, 0);                           \
         __builtin_amdgcn_sched_barrier(0);                                                \
     }
-    f32x16 acc[TI][2];
 #pragma unroll
     for (int i = 0; i < TI; i++)
 #pragma unroll
@@ -250,10 +265,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
 #undef AMOS_GEMM_MFMAS
 #undef AMOS_GEMM_INTERLEAVE
 #undef AMOS_GEMM_STAGE
+    if (kShortcut && phase == 0) {
+        // D as amos_mask_conv_device stores it without a residual and without the ReLU: (acc + bias) + 0
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            const float bd = args.sbias[nt * BN + wn * 64 + j * 32 + (lane & 31)];
+#pragma unroll
+            for (int i = 0; i < TI; i++)
+#pragma unroll
+                for (int r = 0; r < 16; r++) dres[i][j][r] = (acc[i][j][r] + bd) + 0.f;
+        }
+        __syncthreads();  // every wave is done with the LDS of phase 0 before phase 1 stages its first tiles there
+    }
+    }  // phase
+    const ConvGemmArgs &a = args;
     // epilogue.  Accumulator register r of a 32 x 32 tile is row (r & 3) + 8 (r >> 2) + 4 (lane >> 5), column lane & 31: the tile goes
     // through LDS (row-major, BN floats per row; a half-wave writes 32 consecutive floats) so that every thread then handles
     // 16-byte pieces of output rows: bias, residual and ReLU on float4, one coalesced residual load and one store per piece.
     __syncthreads();  // every wave is done with the last stage's operands
+    if constexpr (!kShortcut) {
 #pragma unroll
     for (int i = 0; i < TI; i++)
 #pragma unroll
@@ -261,11 +291,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
 #pragma unroll
             for (int r = 0; r < 16; r++)
                 smem[(wm * 32 * TI + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * BN + wn * 64 + j * 32 + (lane & 31)] = acc[i][j][r];
+    } else {
+        // the whole epilogue in the accumulators' layout, the operations of the piece loop below: ((acc + bias) + D), then the ReLU; the
+        // piece loop then only stores
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            const float b = a.bias[nt * BN + wn * 64 + j * 32 + (lane & 31)];
+#pragma unroll
+            for (int i = 0; i < TI; i++)
+#pragma unroll
+                for (int r = 0; r < 16; r++)
+                    smem[(wm * 32 * TI + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * BN + wn * 64 + j * 32 + (lane & 31)] =
+                        fmaxf((acc[i][j][r] + b) + dres[i][j][r], 0.f);
+        }
+    }
     __syncthreads();
     constexpr int kCols = BN / 4, kRowsPerPass = 256 / kCols, kPasses = BM / kRowsPerPass;  // float4 columns; rows per sweep of the group
     const int oc = t % kCols, orow = t / kCols;
     const int n0 = nt * BN + 4 * oc;
-    if (a.splits > 1) {
+    if (!kShortcut && a.splits > 1) {
         // this split's tile -> partial[split][tile] (tile-contiguous: every store instruction writes whole lines); the last group to arrive
         // sums the splits in order into the LDS tile and falls through to the ordinary epilogue.
         // Visibility.  The 8 XCDs of the chip have an L2 each, so a device-wide release / acquire pair (__threadfence) writes an L2 back and
@@ -329,8 +373,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
             const int row = (p0 + q) * kRowsPerPass + orow, m = mt * BM + row;
             if (m >= a.M) continue;
             float4 v = *reinterpret_cast<const float4 *>(&smem[row * BN + 4 * oc]);
-            v.x = (v.x + bv.x) + rv[q].x; v.y = (v.y + bv.y) + rv[q].y; v.z = (v.z + bv.z) + rv[q].z; v.w = (v.w + bv.w) + rv[q].w;
-            if (a.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+            if constexpr (!kShortcut) {
+                v.x = (v.x + bv.x) + rv[q].x; v.y = (v.y + bv.y) + rv[q].y; v.z = (v.z + bv.z) + rv[q].z; v.w = (v.w + bv.w) + rv[q].w;
+                if (a.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+            }
             *reinterpret_cast<float4 *>(a.y + (size_t)m * a.N + n0) = v;
         }
     }
@@ -449,6 +495,8 @@ int amos_mask_conv_ws_device(void *stream, const float *d_x, const float *d_w, c
     a.stagesPerSplit = 0;
     a.partial = nullptr;
     a.counters = nullptr;
+    a.sx = a.sw = a.sbias = nullptr;
+    a.sK = a.sStride = a.sInW = a.sInH = 0;
     if (d_workspace) {  // split-K when the plan for this shape says so and the caller brought the scratch for it
         const int stages = (cin / kGemmBK) * kh * kw, splits = gemm_splits(M, cout, stages, wide);
         const size_t need = (size_t)kSplitCounterBytes + (size_t)splits * a.mTiles * a.nTiles * BM * BN * sizeof(float);
@@ -466,6 +514,46 @@ int amos_mask_conv_ws_device(void *stream, const float *d_x, const float *d_w, c
     else if (wide) hipLaunchKernelGGL((k_conv_gemm<2, 2, 2, false>), grid, block, 0, st, a);
     else if (taps) hipLaunchKernelGGL((k_conv_gemm<4, 1, 1, true>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((k_conv_gemm<4, 1, 1, false>), grid, block, 0, st, a);
+    AMOS_HIP_CHECK(hipGetLastError());
+    return AMOS_OK;
+}
+
+// The first block of a ResNet stage, projection shortcut and expanding 1 x 1 convolution in one launch (k_conv_gemm<2, 2, 2, false, true>):
+// only where amos_mask_conv_device would run both as 128 x 128 tiles without split-K, so that every output is the same float.
+int amos_mask_conv_chain_supported(int batch, int in_h, int in_w, int cin, int planes, int cout, int stride)
+{
+    if (batch < 1 || in_h < 1 || in_w < 1 || amos_mask_conv_supported(cin, cout, 1, 1, stride, 0) != AMOS_OK || amos_mask_conv_supported(planes, cout, 1, 1, 1, 0) != AMOS_OK)
+        return AMOS_ERR_INVALID;
+    const long long M = (long long)batch * ((in_h - 1) / stride + 1) * ((in_w - 1) / stride + 1);
+    if (M > 0x7fffffffLL / 4 || (long long)batch * in_h * in_w * cin > 0x7fffffffffLL) return AMOS_ERR_INVALID;
+    return gemm_wide_tiles(M, cout) ? AMOS_OK : AMOS_ERR_INVALID;
+}
+
+int amos_mask_conv_chain_device(void *stream, const float *d_x, const float *d_wd, const float *d_bd, const float *d_yc, const float *d_w3, const float *d_b3,
+                                float *d_y, int batch, int in_h, int in_w, int cin, int planes, int cout, int stride)
+{
+    if (!d_x || !d_wd || !d_bd || !d_yc || !d_w3 || !d_b3 || !d_y || amos_mask_conv_chain_supported(batch, in_h, in_w, cin, planes, cout, stride) != AMOS_OK ||
+        ((uintptr_t)d_x | (uintptr_t)d_wd | (uintptr_t)d_yc | (uintptr_t)d_w3 | (uintptr_t)d_b3 | (uintptr_t)d_y) % 16 != 0) {
+        set_error("amos_mask_conv_chain_device: invalid argument (amos_mask_conv_chain_supported, both biases, 16-byte aligned channels-last tensors)");
+        return AMOS_ERR_INVALID;
+    }
+    const int oh = (in_h - 1) / stride + 1, ow = (in_w - 1) / stride + 1;
+    const long long M = (long long)batch * oh * ow;
+    ConvGemmArgs a;
+    a.x = d_yc; a.w = d_w3; a.bias = d_b3; a.res = nullptr; a.y = d_y;  // the residual is the shortcut, in registers
+    a.M = (int)M; a.N = cout; a.K = planes;
+    a.outW = ow; a.outHW = oh * ow; a.inW = ow; a.inH = oh;
+    a.stride = 1; a.relu = 1; a.kh = a.kw = 1; a.pad = 0;
+    a.mTiles = (int)((M + 127) / 128);
+    a.nTiles = cout / 128;
+    a.splits = 1;
+    a.stagesPerSplit = 0;
+    a.partial = nullptr;
+    a.counters = nullptr;
+    a.sx = d_x; a.sw = d_wd; a.sbias = d_bd;
+    a.sK = cin; a.sStride = stride; a.sInW = in_w; a.sInH = in_h;
+    const dim3 grid((unsigned)(((a.mTiles + 7) / 8) * 8 * a.nTiles)), block(256);
+    hipLaunchKernelGGL((k_conv_gemm<2, 2, 2, false, true>), grid, block, 0, (hipStream_t)stream, a);
     AMOS_HIP_CHECK(hipGetLastError());
     return AMOS_OK;
 }

@@ -360,6 +360,31 @@ def _fold(conv, bn):
     return fused
 
 
+def shortcut_fusion(block, x, y):
+    """Does the stage's first block `block` run its projection shortcut and its conv3 as ONE launch (amos_mask_conv_chain_device: the
+    shortcut's output stays on chip instead of going to memory and being read back as conv3's residual)?  x: the block's input, y: conv2's
+    output (shapes and devices only are read, so meta tensors answer too).  Only where both convolutions would otherwise be 128 x 128-tile
+    amos_mask_conv_device launches under the automatic rule -- the fused kernel computes exactly their floats -- with the batch norms
+    folded.  AMOS_MASK_BOTTLENECK_FUSION=0 turns it off; a forced AMOS_MASK_CONV1X1 does too."""
+    if os.environ.get("AMOS_MASK_BOTTLENECK_FUSION", "1") == "0" or os.environ.get("AMOS_MASK_CONV1X1", "auto") != "auto":
+        return False
+    if block.downsample is None or block.conv3.bias is None or block.downsample[0].bias is None:
+        return False
+    down, conv3 = block.downsample[0], block.conv3
+    if down.kernel_size != (1, 1) or down.padding != (0, 0) or down.stride[0] != down.stride[1] or conv3.kernel_size != (1, 1) or conv3.stride != (1, 1):
+        return False
+    if not (x.dtype == y.dtype == down.weight.dtype == conv3.weight.dtype == torch.float32) or x.device.type == "cpu" or torch.is_autocast_enabled():
+        return False
+    b, c, h, w = x.shape
+    s = down.stride[0]
+    if c != down.in_channels or tuple(y.shape) != (b, conv3.in_channels, (h - 1) // s + 1, (w - 1) // s + 1) or down.out_channels != conv3.out_channels:
+        return False
+    if not (_gemm_conv(down, x) and _gemm_conv(conv3, y)):
+        return False
+    from .. import mask_conv_chain_supported
+    return mask_conv_chain_supported(b, h, w, c, conv3.in_channels, conv3.out_channels, s)
+
+
 class Bottleneck(nn.Module):
     expansion = 4
 
@@ -380,6 +405,16 @@ class Bottleneck(nn.Module):
         if self.conv1.bias is not None:  # batch norms folded: conv -> fused (bias, residual, ReLU)
             y = conv_bias_act(self.conv1, x, True)
             y = conv_bias_act(self.conv2, y, True)
+            cl = torch.channels_last
+            if shortcut_fusion(self, x, y) and x.is_contiguous(memory_format=cl) and y.is_contiguous(memory_format=cl) and all(
+                    c.weight.is_contiguous() or c.weight.is_contiguous(memory_format=cl) for c in (self.downsample[0], self.conv3)):
+                from .. import mask_conv_chain
+                down, b, _, h, w = self.downsample[0], *x.shape
+                out = torch.empty((b, self.conv3.out_channels, y.shape[2], y.shape[3]), device=x.device, dtype=torch.float32, memory_format=cl)
+                mask_conv_chain(torch.cuda.current_stream(x.device).cuda_stream, x.data_ptr(), down.weight.data_ptr(), down.bias.data_ptr(), y.data_ptr(),
+                                self.conv3.weight.data_ptr(), self.conv3.bias.data_ptr(), out.data_ptr(), b, h, w, down.in_channels, self.conv3.in_channels,
+                                self.conv3.out_channels, down.stride[0])
+                return out
             identity = x if self.downsample is None else conv_bias_act(self.downsample[0], x, False)
             return conv_bias_act(self.conv3, y, True, residual=identity)
         y = F.relu(self.bn1(self.conv1(x)))

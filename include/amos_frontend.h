@@ -399,6 +399,16 @@ int amos_mask_conv_ws_device(void *stream, const float *d_x, const float *d_w, c
 int amos_mask_conv_tile_mode(int mode);
 int amos_mask_conv_kernel_name(int batch, int in_h, int in_w, int cin, int cout, int kh, int kw, int stride, int pad, char *name,
                                int name_len);
+/* The first block of a ResNet stage, its projection shortcut fused into its expanding 1 x 1 convolution (one launch):
+ *   d = (conv1x1(x, wd, stride) + bd) + 0      x [batch][in_h][in_w][cin], wd [cout][cin]
+ *   y = relu((conv1x1(yc, w3) + b3) + d)        yc [batch][oh][ow][planes], w3 [cout][planes], y [batch][oh][ow][cout]
+ * with oh = (in_h - 1) / stride + 1 (ow alike).  d stays on chip.  Every value of y is the float the two amos_mask_conv_device calls
+ * (d stored, then read back as the residual) produce.  amos_mask_conv_chain_supported: AMOS_OK where amos_mask_conv_device would run
+ * both as 128 x 128 tiles without split-K (amos_mask_conv_tile_mode taken into account), AMOS_ERR_INVALID otherwise, and then
+ * amos_mask_conv_chain_device refuses the call too.  Asynchronous on `stream`; 16-byte aligned channels-last float32 tensors. */
+int amos_mask_conv_chain_supported(int batch, int in_h, int in_w, int cin, int planes, int cout, int stride);
+int amos_mask_conv_chain_device(void *stream, const float *d_x, const float *d_wd, const float *d_bd, const float *d_yc, const float *d_w3,
+                                const float *d_b3, float *d_y, int batch, int in_h, int in_w, int cin, int planes, int cout, int stride);
 int amos_mask_conv1x1_supported(int cin, int cout, int stride);
 
 /* The same convolution for 3 x 3 kernels with stride 1 and pad 1 (the prototype network, the prediction head, the FPN's prediction layers
