@@ -32,7 +32,7 @@ EXPORTS = [
     "amos_orb_stream", "amos_orb_timing_enable", "amos_orb_timing_collect", "amos_match_create", "amos_match_destroy", "amos_match_sync", "amos_match_stream",
     "amos_match_distances", "amos_match_list_distances", "amos_match_list_best2", "amos_match_bruteforce_best2",
     "amos_match_bruteforce_best2_batch_device", "amos_match_set_bruteforce_kernel", "amos_slic_center_count", "amos_slic_create", "amos_slic_destroy", "amos_slic_stream",
-    "amos_slic_run", "amos_slic_batch_device", "amos_cluster_kmeans_batch_device", "amos_cluster_kmeans", "amos_cluster_bgr2lab_batch_device", "amos_flow_check_device", "amos_flow_epipolar_device", "amos_flow_scene_flow_device", "amos_flow_fundamental_score_device", "amos_flow_pnp_score_device", "amos_lk_create", "amos_lk_destroy", "amos_lk_stream", "amos_lk_levels", "amos_lk_track_device", "amos_mask_pre_create", "amos_mask_pre_destroy", "amos_mask_pre_stream", "amos_mask_preprocess_batch_device", "amos_mask_bias_act_device", "amos_mask_bias_relu_maxpool_device", "amos_mask_stem_weight_floats", "amos_mask_stem_weights_device", "amos_mask_stem_device", "amos_mask_conv1x1_supported", "amos_mask_conv1x1_device", "amos_mask_conv_supported", "amos_mask_conv_device", "amos_mask_conv_workspace_bytes", "amos_mask_conv_ws_device", "amos_mask_conv_tile_mode", "amos_mask_conv_kernel_name", "amos_mask_conv_chain_supported", "amos_mask_conv_chain_device", "amos_corners_create", "amos_corners_destroy", "amos_corners_stream", "amos_corners_good_features_device", "amos_corners_candidate_count", "amos_corners_subpix_device", "amos_fmat_create", "amos_fmat_destroy", "amos_fmat_stream", "amos_fmat_ransac_device", "amos_fmat_scene_flow_pair_device", "amos_fmat_ransac", "amos_mask_winograd_supported", "amos_mask_winograd_weight_floats", "amos_mask_winograd_weights_device", "amos_mask_winograd_conv_device", "amos_mask_winograd24_weight_floats", "amos_mask_winograd24_weights_device", "amos_mask_winograd24_conv_device", "amos_mask_winograd24_conv_layout_device", "amos_mask_winograd24_persistent_mode", "amos_mask_winograd24_narrow_mode", "amos_mask_bilinear_nhwc_device", "amos_mask_bilinear_nhwc_act_device", "amos_mask_bilinear_x2_mode", "amos_mask_nms_column_max_device", "amos_mask_class_scores_device", "amos_mask_person_mask_device", "amos_mask_head_outputs_device", "amos_mask_head_outputs_scores_device", "amos_mask_person_masks_scores_device", "amos_mask_topk_rows_device", "amos_mask_topk_rows_sparse_device", "amos_mask_post_workspace_bytes", "amos_mask_person_masks_device", "amos_orb_detect_color_with_mask_pre_batch_device",
+    "amos_slic_run", "amos_slic_batch_device", "amos_cluster_kmeans_batch_device", "amos_cluster_kmeans", "amos_cluster_bgr2lab_batch_device", "amos_flow_check_device", "amos_flow_epipolar_device", "amos_flow_scene_flow_device", "amos_flow_fundamental_score_device", "amos_flow_pnp_score_device", "amos_lk_create", "amos_lk_destroy", "amos_lk_stream", "amos_lk_levels", "amos_lk_track_device", "amos_mask_pre_create", "amos_mask_pre_destroy", "amos_mask_pre_stream", "amos_mask_preprocess_batch_device", "amos_mask_bias_act_device", "amos_mask_bias_relu_maxpool_device", "amos_mask_stem_weight_floats", "amos_mask_stem_weights_device", "amos_mask_stem_device", "amos_mask_conv1x1_supported", "amos_mask_conv1x1_device", "amos_mask_conv_supported", "amos_mask_conv_device", "amos_mask_conv_workspace_bytes", "amos_mask_conv_ws_device", "amos_mask_conv_tile_mode", "amos_mask_conv_kernel_name", "amos_mask_conv_chain_supported", "amos_mask_conv_chain_device", "amos_corners_create", "amos_corners_destroy", "amos_corners_stream", "amos_corners_good_features_device", "amos_corners_candidate_count", "amos_corners_subpix_device", "amos_fmat_create", "amos_fmat_destroy", "amos_fmat_stream", "amos_fmat_ransac_device", "amos_fmat_scene_flow_pair_device", "amos_fmat_ransac", "amos_pnp_create", "amos_pnp_destroy", "amos_pnp_stream", "amos_pnp_ransac_device", "amos_pnp_scene_flow_device", "amos_pnp_ransac", "amos_mask_winograd_supported", "amos_mask_winograd_weight_floats", "amos_mask_winograd_weights_device", "amos_mask_winograd_conv_device", "amos_mask_winograd24_weight_floats", "amos_mask_winograd24_weights_device", "amos_mask_winograd24_conv_device", "amos_mask_winograd24_conv_layout_device", "amos_mask_winograd24_persistent_mode", "amos_mask_winograd24_narrow_mode", "amos_mask_bilinear_nhwc_device", "amos_mask_bilinear_nhwc_act_device", "amos_mask_bilinear_x2_mode", "amos_mask_nms_column_max_device", "amos_mask_class_scores_device", "amos_mask_person_mask_device", "amos_mask_head_outputs_device", "amos_mask_head_outputs_scores_device", "amos_mask_person_masks_scores_device", "amos_mask_topk_rows_device", "amos_mask_topk_rows_sparse_device", "amos_mask_post_workspace_bytes", "amos_mask_person_masks_device", "amos_orb_detect_color_with_mask_pre_batch_device",
 ]
 
 
@@ -910,3 +910,59 @@ class FundamentalRansac:
         """Tracking.cc:927-945: F1 on state != 0, keep = dd <= 0.5 under F1, F2 on keep; d_status [2][4]."""
         _check(self.L.amos_fmat_scene_flow_pair_device(self.h, C.c_void_p(d_pre), C.c_void_p(d_next), C.c_void_p(d_state), C.c_void_p(d_n), C.c_void_p(d_F1),
                                                        C.c_void_p(d_F2), C.c_void_p(d_keep), C.c_void_p(d_status)), "amos_fmat_scene_flow_pair_device")
+
+
+class PnpRansac:
+    """amos_pnp_*: cv::solvePnPRansac(obj, img, K, 0, ..., SOLVEPNP_P3P) of Tracking::GetSceneFlowObj (Tracking.cc:1006) on the device: the
+    RANSAC over P3P samples, then the EPnP refit on its inliers (restated, parity with OpenCV unpinned).  status = (result, inliers,
+    iterations, points, refit): result 1 model, 0 none, -1 fewer than 4 points, -2 sampler cap, -3 count out of range; refit 1 EPnP
+    refit returned, -1 refit not finite (the RANSAC model returned), 0 none.  Poses are R | t: R row-major, then t."""
+
+    def __init__(self, max_points=4096, max_problems=64, device=0, stream=None):
+        self.L = lib()
+        self.L.amos_pnp_stream.restype = C.c_void_p
+        self.L.amos_pnp_stream.argtypes = [C.c_void_p]
+        self.L.amos_pnp_destroy.restype = None
+        self.L.amos_pnp_destroy.argtypes = [C.c_void_p]
+        h = C.c_void_p()
+        _check(self.L.amos_pnp_create(C.c_int(device), C.c_void_p(stream), C.c_int(max_points), C.c_int(max_problems), C.byref(h)), "amos_pnp_create")
+        self.h = h
+        self.max_points = max_points
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.amos_pnp_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    @property
+    def stream(self):
+        return self.L.amos_pnp_stream(self.h)
+
+    def ransac(self, obj, img, fx, fy, cx, cy, reprojection_error=0.4, confidence=0.98, max_iters=500):
+        """One problem from host arrays obj [n][3], img [n][2]: returns (Rt [12] float64, mask [n] uint8, status [5] int32)."""
+        obj = np.ascontiguousarray(obj, np.float32).reshape(-1, 3)
+        img = np.ascontiguousarray(img, np.float32).reshape(-1, 2)
+        assert len(obj) == len(img)
+        Rt, mask, status = np.zeros(12), np.zeros(len(obj), np.uint8), np.zeros(5, np.int32)
+        _check(self.L.amos_pnp_ransac(self.h, C.c_int(len(obj)), _p(obj), _p(img), C.c_double(fx), C.c_double(fy), C.c_double(cx), C.c_double(cy),
+                                      C.c_double(reprojection_error), C.c_double(confidence), C.c_int(max_iters), _p(Rt), _p(mask), _p(status)),
+               "amos_pnp_ransac")
+        return Rt, mask, status
+
+    def ransac_device(self, n_problems, d_obj, d_img, d_offsets, d_counts, d_select, fx, fy, cx, cy, d_Rt, d_status, d_mask=None,
+                      reprojection_error=0.4, confidence=0.98, max_iters=500):
+        _check(self.L.amos_pnp_ransac_device(self.h, C.c_int(n_problems), C.c_void_p(d_obj), C.c_void_p(d_img), C.c_void_p(d_offsets), C.c_void_p(d_counts),
+                                             C.c_void_p(d_select), C.c_double(fx), C.c_double(fy), C.c_double(cx), C.c_double(cy),
+                                             C.c_double(reprojection_error), C.c_double(confidence), C.c_int(max_iters), C.c_void_p(d_Rt),
+                                             C.c_void_p(d_status), C.c_void_p(d_mask)), "amos_pnp_ransac_device")
+
+    def scene_flow_device(self, d_pre, d_next, d_state, d_n, d_depth_last, last_stride, d_depth_cur, cur_stride, width, height, cam, fx, fy,
+                          d_Rt, d_status, d_mask=None):
+        """Tracking.cc:955-1007: the point lists (pre_3d -> next where both depths > 0, (0,0,0) -> (0,0) elsewhere) over state != 0, then
+        solvePnPRansac(500, 0.4, 0.98); strides in floats; cam a SceneFlowCamera; d_Rt [12], d_status [5]."""
+        _check(self.L.amos_pnp_scene_flow_device(self.h, C.c_void_p(d_pre), C.c_void_p(d_next), C.c_void_p(d_state), C.c_void_p(d_n),
+                                                 C.c_void_p(d_depth_last), C.c_size_t(last_stride), C.c_void_p(d_depth_cur), C.c_size_t(cur_stride),
+                                                 C.c_int(width), C.c_int(height), C.byref(cam), C.c_double(fx), C.c_double(fy), C.c_void_p(d_Rt),
+                                                 C.c_void_p(d_status), C.c_void_p(d_mask)), "amos_pnp_scene_flow_device")

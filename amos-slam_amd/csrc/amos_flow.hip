@@ -5,9 +5,11 @@
 //   k_epipolar        :928-946, 1141-1152   distance of the tracked position from the epipolar line F * p (doubles)
 //   k_scene_flow_3d   :955-990, 1153-1183   back-projection of a match with the two depth maps, last / current camera to
 //                                world (cv::Mat expressions: one gemm = double accumulation, one rounding), 3-D flow norm
-// goodFeaturesToTrack, cornerSubPix, calcOpticalFlowPyrLK, findFundamentalMat and solvePnPRansac are OpenCV (the two
-// RANSACs draw from OpenCV's RNG): they stay with the caller -- DESIGN.md section 7.
+// goodFeaturesToTrack, cornerSubPix, calcOpticalFlowPyrLK, findFundamentalMat and solvePnPRansac are OpenCV calls; their device forms
+// are amos_corners.hip, the LK tracker below, amos_fmat.hip and amos_pnp.hip -- DESIGN.md section 7.
 #include "amos_common.h"
+#include "amos_pnp_core.h"
+#include "amos_scene_flow.h"
 
 #include <algorithm>
 
@@ -56,8 +58,8 @@ __global__ __launch_bounds__(256) void k_epipolar(const double *__restrict__ F, 
 }
 
 // ---- hypothesis scoring for the RANSACs of GetSceneFlowObj (Tracking.cc:927, 945: cv::findFundamentalMat(..., FM_RANSAC, 0.1, 0.99);
-// :1006: cv::solvePnPRansac(..., 500, 0.4, 0.98, inliers, SOLVEPNP_P3P)).  The minimal solvers, the sampling and the iteration-count
-// update stay with the caller; what the device takes is the part that touches every point: the error of every
+// :1006: cv::solvePnPRansac(..., 500, 0.4, 0.98, inliers, SOLVEPNP_P3P)) for a caller that runs its own RANSAC loop (the whole RANSACs are
+// amos_fmat.hip and amos_pnp.hip): the part that touches every point: the error of every
 // correspondence under every hypothesis, the inlier test and the inlier counts -- one work-group per hypothesis, counts by a reduction
 // (no atomics: deterministic, nothing to zero).
 //
@@ -110,22 +112,12 @@ __global__ __launch_bounds__(256) void k_pnp_score(const double *__restrict__ Rt
     __shared__ int sCount[4];
     const int h = blockIdx.x, t = threadIdx.x;
     const double *M = Rts + (size_t)h * 12;
-    double R[9], T[3];
+    double Rt[12];
 #pragma unroll
-    for (int k = 0; k < 9; k++) R[k] = M[k];
-#pragma unroll
-    for (int k = 0; k < 3; k++) T[k] = M[9 + k];
+    for (int k = 0; k < 12; k++) Rt[k] = M[k];
     int count = 0;
     for (int i = t; i < n; i += 256) {
-        const double X = obj[3 * i], Y = obj[3 * i + 1], Z = obj[3 * i + 2];
-        const double xc = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(R[0], X), __dmul_rn(R[1], Y)), __dmul_rn(R[2], Z)), T[0]);
-        const double yc = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(R[3], X), __dmul_rn(R[4], Y)), __dmul_rn(R[5], Z)), T[1]);
-        double zc = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(R[6], X), __dmul_rn(R[7], Y)), __dmul_rn(R[8], Z)), T[2]);
-        zc = zc != 0.0 ? __ddiv_rn(1.0, zc) : 1.0;  // cvProjectPoints2: z = z ? 1. / z : 1
-        const double xn = __dmul_rn(xc, zc), yn = __dmul_rn(yc, zc);
-        const float u = (float)__dadd_rn(__dmul_rn(xn, fx), cx), v = (float)__dadd_rn(__dmul_rn(yn, fy), cy);
-        const float dx = __fsub_rn(img[i].x, u), dy = __fsub_rn(img[i].y, v);
-        const float e = __fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy));
+        const float e = pnp::point_error(Rt, obj[3 * i], obj[3 * i + 1], obj[3 * i + 2], img[i].x, img[i].y, fx, fy, cx, cy);
         const bool in = e <= thresh2;
         if (err) err[(size_t)h * n + i] = e;
         if (mask) mask[(size_t)h * n + i] = in ? 1 : 0;
@@ -135,17 +127,6 @@ __global__ __launch_bounds__(256) void k_pnp_score(const double *__restrict__ Rt
     if ((t & 63) == 0) sCount[t >> 6] = count;
     __syncthreads();
     if (t == 0) inliers[h] = sCount[0] + sCount[1] + sCount[2] + sCount[3];
-}
-
-struct SceneFlowArgs {
-    float cx, cy, invfx, invfy;
-    float Rwl[9], twl[3];  // last camera -> world (Rlw^T, -Rlw^T tlw as floats, Tracking.cc:970-973)
-    float Rwc[9], Ow[3];   // current camera -> world (Frame::mRwc, mOw)
-};
-
-__device__ __forceinline__ float gemm_row(const float *R, int r, float x, float y, float z, float t)
-{
-    return (float)((double)R[3 * r] * x + (double)R[3 * r + 1] * y + (double)R[3 * r + 2] * z + (double)t);
 }
 
 // out per match: pre_3d (3), cur_3d (3), sf_norm, valid (z1 > 0 && z2 > 0)
@@ -163,10 +144,8 @@ __global__ __launch_bounds__(256) void k_scene_flow_3d(const float *__restrict__
         for (int k = 0; k < 8; k++) o[k] = 0.f;
         return;
     }
-    // :960-961
-    const float xl = __fmul_rn(__fmul_rn(__fsub_rn(matchPre[i].x, a.cx), z1), a.invfx);
-    const float yl = __fmul_rn(__fmul_rn(__fsub_rn(matchPre[i].y, a.cy), z1), a.invfy);
-    const float p0 = gemm_row(a.Rwl, 0, xl, yl, z1, a.twl[0]), p1 = gemm_row(a.Rwl, 1, xl, yl, z1, a.twl[1]), p2 = gemm_row(a.Rwl, 2, xl, yl, z1, a.twl[2]);
+    float p0, p1, p2;  // :960-973
+    scene_flow_pre3d(a, matchPre[i].x, matchPre[i].y, z1, p0, p1, p2);
     // :1160-1164 (the reference scales the CURRENT pixel by z1 and stacks z2: restated as written)
     const float xc = __fmul_rn(__fmul_rn(__fsub_rn(matchCur[i].x, a.cx), z1), a.invfx);
     const float yc = __fmul_rn(__fmul_rn(__fsub_rn(matchCur[i].y, a.cy), z1), a.invfy);
@@ -446,15 +425,7 @@ int amos_flow_scene_flow_device(void *stream, const float *d_depth_last, size_t 
 {
     if (!d_depth_last || !d_depth_cur || !d_match_pre_xy || !d_match_cur_xy || !cam || !d_out || n < 0) { set_error("amos_flow_scene_flow_device: invalid argument"); return AMOS_ERR_INVALID; }
     if (n == 0) return AMOS_OK;
-    SceneFlowArgs a;
-    a.cx = cam->cx; a.cy = cam->cy; a.invfx = cam->invfx; a.invfy = cam->invfy;
-    // Rwl = Rlw^T, twl = -Rlw^T * tlw (one gemm, alpha = -1: double accumulation, one rounding)
-    for (int r = 0; r < 3; r++) {
-        for (int c = 0; c < 3; c++) a.Rwl[3 * r + c] = cam->Tlw[4 * c + r];
-        a.twl[r] = (float)(-((double)cam->Tlw[r] * cam->Tlw[3] + (double)cam->Tlw[4 + r] * cam->Tlw[7] + (double)cam->Tlw[8 + r] * cam->Tlw[11]));
-    }
-    for (int k = 0; k < 9; k++) a.Rwc[k] = cam->Rwc[k];
-    for (int k = 0; k < 3; k++) a.Ow[k] = cam->Ow[k];
+    const SceneFlowArgs a = scene_flow_args(cam);
     hipLaunchKernelGGL(k_scene_flow_3d, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_depth_last, d_depth_cur, last_stride, cur_stride,
                        (const FlowPoint *)d_match_pre_xy, (const FlowPoint *)d_match_cur_xy, n, a, d_out);
     AMOS_HIP_CHECK(hipGetLastError());

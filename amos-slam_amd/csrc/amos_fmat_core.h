@@ -244,15 +244,15 @@ FM_HD int round_even(double x)
     return (int)r;
 }
 
-// RANSACUpdateNumIters(p, ep, 7, maxIters)
-FM_HD int update_num_iters(double p, double ep, int maxIters)
+// RANSACUpdateNumIters(p, ep, modelPoints, maxIters); (1 - ep)^modelPoints as a fixed multiplication chain: 7 -> ((q^2 q)^2) q, 4 -> q^2 q^2
+FM_HD int update_num_iters(double p, double ep, int maxIters, int modelPoints = kModelPoints)
 {
     p = p < 0 ? 0 : (p > 1 ? 1 : p);
     ep = ep < 0 ? 0 : (ep > 1 ? 1 : ep);
     double num = sub(1.0, p);
     if (num < kDblMin) num = kDblMin;
     const double q = sub(1.0, ep), q2 = mul(q, q), q3 = mul(q2, q), q6 = mul(q3, q3), q7 = mul(q6, q);
-    double denom = sub(1.0, q7);
+    double denom = sub(1.0, modelPoints == 4 ? mul(q2, q2) : q7);
     if (denom < kDblMin) return 0;
     num = log_(num);
     denom = log_(denom);

@@ -1,0 +1,524 @@
+// amos_pnp.hip -- cv::solvePnPRansac(pre_3d, cur_2d, K, 0, rvec, tvec, false, 500, 0.4, 0.98, inliers, SOLVEPNP_P3P) of
+// Tracking::GetSceneFlowObj (src/Tracking.cc:1006) on the device: the RANSAC over P3P samples and the EPnP refit on its inliers.
+// The arithmetic is amos_pnp_core.h (restated; parity with OpenCV unpinned).
+//   k_pnp_ransac   ONE WORK-GROUP PER PROBLEM (a batch of problems is one launch).  The selected points go to LDS (20 B each), then
+//                  rounds of up to 64 iterations: lane 0 runs the serial RNG and draws the subsets (PnPRansacCallback has no
+//                  checkSubset, so every draw of 4 distinct indices is a subset); one lane per subset runs P3P; all waves score the up to
+//                  64 models over all points (counts by wave reduction, no atomics); lane 0 replays the sequential loop in iteration order
+//                  (best model, niters).  The RNG consumption depends only on the point count, so drawing ahead changes nothing.  Then
+//                  the EPnP refit in the same launch: every sum over the inliers is owned by one lane and runs in inlier order; the
+//                  per-inlier alphas and image points go through a global scratch row of the problem; the small dense steps (PCA,
+//                  pseudo-inverse, 12 x 12 Jacobi, betas, Gauss-Newton, R and t) run on one lane.
+//   k_pnp_points   Tracking.cc:955-990: the N-point lists of the reference (pre_3d, cur_2d), (0, 0, 0) -> (0, 0) where a depth is missing
+#include "amos_common.h"
+#include "amos_pnp_core.h"
+#include "amos_scene_flow.h"
+
+namespace amos {
+
+constexpr int kPnpMaxPoints = 4096;
+constexpr int kPnpThreads = 512, kPnpWaves = kPnpThreads / 64;
+constexpr int kPnpRound = 64;
+constexpr int kPnpStatus = 5;
+constexpr int kPnpScratch = 6;  // doubles per inlier: alphas[4], u, v
+
+struct PnpArgs {
+    const float *obj, *img;
+    const int *offsets, *counts;
+    const uint8_t *select;
+    int maxPoints, maxIters;
+    float thresh2;
+    double confidence, fx, fy, cx, cy;
+    double *Rt;
+    int *status;
+    uint8_t *mask;
+    double *scratch;  // [problem][maxPoints][kPnpScratch]
+};
+
+// calls f(index i, compact index c or -1) for i < cnt, c counting the i with sel_of(i) in order (block-wide)
+template <typename Sel, typename Fn>
+__device__ __forceinline__ int block_scan(int cnt, int *sWave, Sel sel_of, Fn f)
+{
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    int total = 0;
+    for (int base = 0; base < cnt; base += kPnpThreads) {
+        const int i = base + t;
+        const bool sel = i < cnt && sel_of(i);
+        const unsigned long long b = __ballot(sel);
+        if (lane == 0) sWave[wv] = (int)__popcll(b);
+        __syncthreads();
+        int before = total, all = total;
+        for (int w = 0; w < kPnpWaves; w++) {
+            if (w < wv) before += sWave[w];
+            all += sWave[w];
+        }
+        if (i < cnt) f(i, sel ? before + (int)__popcll(b & ((1ull << lane) - 1ull)) : -1);
+        __syncthreads();
+        total = all;
+    }
+    return total;
+}
+
+__global__ __launch_bounds__(kPnpThreads) void k_pnp_ransac(const PnpArgs a)
+{
+    __shared__ float4 sP[kPnpMaxPoints];  // (X, Y, Z, u) of the selected points
+    __shared__ float sV[kPnpMaxPoints];   // v
+    __shared__ uint16_t sIdx[kPnpMaxPoints];  // compact indices of the refit's inliers
+    __shared__ double sModel[kPnpRound][12];
+    __shared__ int sOk[kPnpRound], sCount[kPnpRound], sSub[kPnpRound][4];
+    __shared__ double sBest[12];
+    __shared__ double sM[144], sE[144];   // 12 x 12 MtM and its eigenvectors
+    __shared__ double sS[9], sCw[4][3], sCi[9];
+    __shared__ double sCcs[3][4][3], sSum[3][6], sAbt[3][9], sRt[3][12], sRep[3];
+    __shared__ int sNeg[3];
+    __shared__ int sWave[kPnpWaves];
+    __shared__ int sDrawn, sStop, sResult, sIter, sNiters, sMaxGood;
+    const int p = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int off = a.offsets ? a.offsets[p] : p * a.maxPoints, cnt = a.counts[p];
+    double *Rout = a.Rt + (size_t)p * 12;
+    int *st = a.status + (size_t)p * kPnpStatus;
+    if (cnt < 0 || cnt > a.maxPoints) {  // out of range: nothing is read, no mask written
+        if (t < 12) Rout[t] = 0.0;
+        if (t == 0) { st[0] = -3; st[1] = 0; st[2] = 0; st[3] = 0; st[4] = 0; }
+        return;
+    }
+    const float *obj = a.obj, *img = a.img;
+    const uint8_t *select = a.select;
+    const int n = block_scan(cnt, sWave, [&](int i) { return !select || select[off + i] != 0; }, [&](int i, int c) {
+        if (c >= 0) {
+            const size_t g = (size_t)(off + i);
+            sP[c] = make_float4(obj[3 * g], obj[3 * g + 1], obj[3 * g + 2], img[2 * g]);
+            sV[c] = img[2 * g + 1];
+        }
+    });
+    const double fx = a.fx, fy = a.fy, cx = a.cx, cy = a.cy;
+    if (n < pnp::kModelPoints) {  // OpenCV asserts: no model, too few points
+        if (t < 12) Rout[t] = 0.0;
+        if (t == 0) { st[0] = -1; st[1] = 0; st[2] = 0; st[3] = n; st[4] = 0; }
+        if (a.mask) for (int i = t; i < cnt; i += kPnpThreads) a.mask[off + i] = 0;
+        return;
+    }
+    if (t == 0) { sStop = 0; sResult = 0; sIter = 0; sNiters = a.maxIters; sMaxGood = 0; }
+    if (n == pnp::kModelPoints) {  // solvePnPRansac's direct call: solvePnP(P3P) on the four points, all of them inliers
+        if (t == 0) {
+            float o[12], im[8];
+            for (int i = 0; i < 4; i++) {
+                o[3 * i] = sP[i].x; o[3 * i + 1] = sP[i].y; o[3 * i + 2] = sP[i].z;
+                im[2 * i] = sP[i].w; im[2 * i + 1] = sV[i];
+            }
+            double M[12];
+            const bool ok = pnp::p3p4(o, im, fx, fy, cx, cy, M);
+            for (int k = 0; k < 12; k++) sBest[k] = ok ? M[k] : 0.0;
+            sResult = ok ? 1 : 0;
+        }
+        __syncthreads();
+        const int ok = sResult;
+        if (t < 12) Rout[t] = sBest[t];
+        if (t == 0) { st[0] = ok; st[1] = ok ? 4 : 0; st[2] = 0; st[3] = n; st[4] = 0; }
+        if (a.mask) block_scan(cnt, sWave, [&](int i) { return !select || select[off + i] != 0; }, [&](int i, int c) { a.mask[off + i] = c >= 0 && ok ? 1 : 0; });
+        return;
+    }
+    __syncthreads();
+    uint64_t rng = ~0ull;  // cv::RNG rng((uint64)-1), lane 0's copy
+    for (;;) {
+        const int iter0 = sIter, limit = min(kPnpRound, sNiters - iter0);
+        // ---- draw the subsets of iterations iter0 .. iter0 + limit - 1 (getSubset: 4 distinct indices)
+        if (t == 0) {
+            int drawn = 0, stop = 0;
+            for (int slot = 0; slot < limit && !stop; slot++) {
+                int idx[4];
+                for (int i = 0; i < 4 && !stop; i++) {
+                    for (uint32_t draws = 1;; draws++) {
+                        const int v = (int)(fm::rng_next(rng) % (uint32_t)n);
+                        bool dup = false;
+                        for (int j = 0; j < i; j++) dup |= v == idx[j];
+                        idx[i] = v;
+                        if (!dup) break;
+                        if (draws >= fm::kRedrawCap) { stop = 2; break; }
+                    }
+                }
+                if (stop) break;
+                for (int i = 0; i < 4; i++) sSub[slot][i] = idx[i];
+                drawn++;
+            }
+            sDrawn = drawn; sStop = stop;
+        }
+        __syncthreads();
+        const int drawn = sDrawn;
+        // ---- P3P, one lane per subset
+        if (t < drawn) {
+            float o[12], im[8];
+            for (int i = 0; i < 4; i++) {
+                const int c = sSub[t][i];
+                const float4 P = sP[c];
+                o[3 * i] = P.x; o[3 * i + 1] = P.y; o[3 * i + 2] = P.z;
+                im[2 * i] = P.w; im[2 * i + 1] = sV[c];
+            }
+            double M[12];
+            const bool ok = pnp::p3p4(o, im, fx, fy, cx, cy, M);
+            sOk[t] = ok ? 1 : 0;
+            for (int k = 0; k < 12; k++) sModel[t][k] = M[k];
+        }
+        __syncthreads();
+        // ---- scoring: model m on wave m % kPnpWaves, points over the lanes
+        for (int m = wv; m < drawn; m += kPnpWaves) {
+            if (!sOk[m]) continue;  // wave-uniform
+            double M[12];
+            for (int k = 0; k < 12; k++) M[k] = sModel[m][k];
+            int count = 0;
+            for (int i = lane; i < n; i += 64) {
+                const float4 P = sP[i];
+                count += pnp::point_error(M, P.x, P.y, P.z, P.w, sV[i], fx, fy, cx, cy) <= a.thresh2 ? 1 : 0;
+            }
+            for (int d = 32; d > 0; d >>= 1) count += __shfl_xor(count, d, 64);
+            if (lane == 0) sCount[m] = count;
+        }
+        __syncthreads();
+        // ---- the sequential loop of RANSACPointSetRegistrator::run over this round's iterations
+        if (t == 0) {
+            int iter = iter0, niters = sNiters, maxGood = sMaxGood, stop = 0;
+            for (int slot = 0;; slot++) {
+                if (iter >= niters) break;
+                if (slot == drawn) {
+                    if (sStop == 2) { sResult = -2; stop = 1; }
+                    break;
+                }
+                if (sOk[slot]) {
+                    const int good = sCount[slot];
+                    if (good > max(maxGood, pnp::kModelPoints - 1)) {
+                        for (int k = 0; k < 12; k++) sBest[k] = sModel[slot][k];
+                        maxGood = good;
+                        niters = pnp::update_num_iters(a.confidence, fm::dvd((double)(n - good), (double)n), niters);
+                    }
+                }
+                iter++;
+            }
+            sIter = iter; sNiters = niters; sMaxGood = maxGood;
+            if (iter >= niters) stop = 1;
+            sStop = stop ? 3 : 0;
+        }
+        __syncthreads();
+        if (sStop == 3) break;
+    }
+    const int result = sResult == -2 ? -2 : (sMaxGood > 0 ? 1 : 0);
+    if (result != 1) {
+        if (t < 12) Rout[t] = 0.0;
+        if (t == 0) { st[0] = result; st[1] = 0; st[2] = sIter; st[3] = n; st[4] = 0; }
+        if (a.mask) for (int i = t; i < cnt; i += kPnpThreads) a.mask[off + i] = 0;
+        return;
+    }
+    // ---- the RANSAC mask, the inlier list in order
+    double B[12];
+    for (int k = 0; k < 12; k++) B[k] = sBest[k];
+    auto inlier = [&](int c) {
+        const float4 P = sP[c];
+        return pnp::point_error(B, P.x, P.y, P.z, P.w, sV[c], fx, fy, cx, cy) <= a.thresh2;
+    };
+    const int m = block_scan(n, sWave, inlier, [&](int i, int c) { if (c >= 0) sIdx[c] = (uint16_t)i; });
+    if (a.mask) {
+        block_scan(cnt, sWave, [&](int i) { return !select || select[off + i] != 0; }, [&](int i, int c) { a.mask[off + i] = c >= 0 && inlier(c) ? 1 : 0; });
+    }
+    // ---- EPnP on the m inliers (m = maxGood >= 4)
+    double *scr = a.scratch + (size_t)p * a.maxPoints * kPnpScratch;
+    auto pw_of = [&](int j, double *pw) {
+        const float4 P = sP[sIdx[j]];
+        pw[0] = P.x; pw[1] = P.y; pw[2] = P.z;
+    };
+    const double dm = (double)m;
+    if (t < 3) {  // control point 0: the centroid
+        double acc = 0.0, pw[3];
+        for (int j = 0; j < m; j++) { pw_of(j, pw); acc = acc + pw[t]; }
+        sCw[0][t] = fm::dvd(acc, dm);
+    }
+    __syncthreads();
+    if (t < 6) {  // PW0^T PW0, upper triangle (0,0) (0,1) (0,2) (1,1) (1,2) (2,2)
+        const int r = t < 3 ? 0 : (t < 5 ? 1 : 2), c = t < 3 ? t : (t < 5 ? t - 2 : 2);
+        double acc = 0.0, pw[3];
+        for (int j = 0; j < m; j++) { pw_of(j, pw); acc = acc + (pw[r] - sCw[0][r]) * (pw[c] - sCw[0][c]); }
+        sS[3 * r + c] = acc;
+        sS[3 * c + r] = acc;
+    }
+    __syncthreads();
+    if (t == 0) {
+        double S[9], cw[4][3], ci[9];
+        for (int k = 0; k < 9; k++) S[k] = sS[k];
+        for (int k = 0; k < 3; k++) cw[0][k] = sCw[0][k];
+        pnp::control_points(S, m, cw, ci);
+        for (int i = 1; i < 4; i++) for (int k = 0; k < 3; k++) sCw[i][k] = cw[i][k];
+        for (int k = 0; k < 9; k++) sCi[k] = ci[k];
+    }
+    __syncthreads();
+    for (int j = t; j < m; j += kPnpThreads) {  // per inlier: alphas and the refit's image point
+        double pw[3], al[4], cw0[3] = {sCw[0][0], sCw[0][1], sCw[0][2]}, ci[9];
+        for (int k = 0; k < 9; k++) ci[k] = sCi[k];
+        pw_of(j, pw);
+        pnp::alphas(ci, cw0, pw[0], pw[1], pw[2], al);
+        double u, v;
+        pnp::pixel_refit(sP[sIdx[j]].w, sV[sIdx[j]], fx, fy, cx, cy, u, v);
+        double *o = scr + (size_t)j * kPnpScratch;
+        o[0] = al[0]; o[1] = al[1]; o[2] = al[2]; o[3] = al[3]; o[4] = u; o[5] = v;
+    }
+    __syncthreads();
+    if (t < 78) {  // MtM, one lane per upper-triangle entry (r, c), rows of M in order
+        int r = 0, k = t;
+        while (k >= 12 - r) { k -= 12 - r; r++; }
+        const int c = r + k;
+        double acc = 0.0;
+        for (int j = 0; j < m; j++) {
+            const double *o = scr + (size_t)j * kPnpScratch;
+            double r1, r2, c1, c2;
+            pnp::m_entries(o, o[4], o[5], fx, fy, cx, cy, r, r1, r2);
+            pnp::m_entries(o, o[4], o[5], fx, fy, cx, cy, c, c1, c2);
+            acc = acc + r1 * c1;
+            acc = acc + r2 * c2;
+        }
+        sM[12 * r + c] = acc;
+        sM[12 * c + r] = acc;
+    }
+    __syncthreads();
+    if (t == 0) {
+        pnp::jacobi_sym(sM, sE, 12);
+        int order[12];
+        pnp::eig_order(sM, 12, false, order);
+        double v[4][12], cw[4][3], L[60], rho[6];
+        for (int i = 0; i < 4; i++) for (int k = 0; k < 12; k++) v[i][k] = sE[12 * k + order[i]];
+        for (int i = 0; i < 4; i++) for (int k = 0; k < 3; k++) cw[i][k] = sCw[i][k];
+        pnp::l6x10_rho(v, cw, L, rho);
+        const double *o0 = scr;  // the first inlier decides solve_for_sign
+        for (int w = 0; w < 3; w++) {
+            double betas[4], ccs[4][3], pc[3];
+            pnp::betas_for(L, rho, w + 1, betas);
+            pnp::ccs_of(betas, v, ccs);
+            pnp::pc_of(o0, ccs, false, pc);
+            sNeg[w] = pc[2] < 0.0 ? 1 : 0;
+            for (int i = 0; i < 4; i++) for (int k = 0; k < 3; k++) sCcs[w][i][k] = ccs[i][k];
+        }
+    }
+    __syncthreads();
+    if (t < 18) {  // sums of pc (3) and pw (3) per beta set
+        const int w = t / 6, q = t % 6;
+        double ccs[4][3];
+        for (int i = 0; i < 4; i++) for (int k = 0; k < 3; k++) ccs[i][k] = sCcs[w][i][k];
+        double acc = 0.0;
+        for (int j = 0; j < m; j++) {
+            double x;
+            if (q < 3) {
+                double pc[3];
+                pnp::pc_of(scr + (size_t)j * kPnpScratch, ccs, sNeg[w] != 0, pc);
+                x = pc[q];
+            } else {
+                double pw[3];
+                pw_of(j, pw);
+                x = pw[q - 3];
+            }
+            acc = acc + x;
+        }
+        sSum[w][q] = fm::dvd(acc, dm);
+    }
+    __syncthreads();
+    if (t < 27) {  // ABt per beta set
+        const int w = t / 9, e = t % 9, r = e / 3, c = e % 3;
+        double ccs[4][3];
+        for (int i = 0; i < 4; i++) for (int k = 0; k < 3; k++) ccs[i][k] = sCcs[w][i][k];
+        double acc = 0.0;
+        for (int j = 0; j < m; j++) {
+            double pc[3], pw[3];
+            pnp::pc_of(scr + (size_t)j * kPnpScratch, ccs, sNeg[w] != 0, pc);
+            pw_of(j, pw);
+            acc = acc + (pc[r] - sSum[w][r]) * (pw[c] - sSum[w][3 + c]);
+        }
+        sAbt[w][e] = acc;
+    }
+    __syncthreads();
+    if (t < 3) {  // R, t and the mean reprojection error per beta set
+        double H[9], Rt[12];
+        for (int k = 0; k < 9; k++) H[k] = sAbt[t][k];
+        pnp::r_and_t(H, &sSum[t][0], &sSum[t][3], Rt);
+        double acc = 0.0;
+        for (int j = 0; j < m; j++) {
+            const double *o = scr + (size_t)j * kPnpScratch;
+            double pw[3];
+            pw_of(j, pw);
+            acc = acc + pnp::reproj_term(Rt, pw, o[4], o[5], fx, fy, cx, cy);
+        }
+        sRep[t] = fm::dvd(acc, dm);
+        for (int k = 0; k < 12; k++) sRt[t][k] = Rt[k];
+    }
+    __syncthreads();
+    if (t == 0) {
+        int N = 0;
+        if (sRep[1] < sRep[0]) N = 1;
+        if (sRep[2] < sRep[N]) N = 2;
+        bool ok = true;
+        for (int k = 0; k < 12; k++) ok = ok && pnp::finite_(sRt[N][k]);
+        for (int k = 0; k < 12; k++) Rout[k] = ok ? sRt[N][k] : sBest[k];
+        st[0] = 1; st[1] = sMaxGood; st[2] = sIter; st[3] = n; st[4] = ok ? 1 : -1;
+    }
+}
+
+// the reference's N-point lists (Tracking.cc:955-990) for i < *d_n: pre_3d / cur_2d where z1 > 0 && z2 > 0, (0, 0, 0) / (0, 0) elsewhere
+// (entries with state 0 are written too and not selected).  A pixel outside the depth map counts as a missing depth.
+__global__ __launch_bounds__(256) void k_pnp_points(const float2 *__restrict__ pre, const float2 *__restrict__ next, const int *__restrict__ dN, int maxPoints,
+                                                    const float *__restrict__ depthLast, size_t lastStride, const float *__restrict__ depthCur,
+                                                    size_t curStride, int width, int height, const SceneFlowArgs sa, float *__restrict__ obj,
+                                                    float *__restrict__ img)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x, n = *dN;
+    if (n < 0 || n > maxPoints || i >= n) return;
+    const float2 P = pre[i], Q = next[i];
+    const int x1 = (int)P.x, y1 = (int)P.y, x2 = (int)Q.x, y2 = (int)Q.y;
+    const bool in1 = P.x >= 0 && P.y >= 0 && x1 < width && y1 < height, in2 = Q.x >= 0 && Q.y >= 0 && x2 < width && y2 < height;
+    const float z1 = in1 ? depthLast[(size_t)y1 * lastStride + x1] : 0.f;
+    const float z2 = in2 ? depthCur[(size_t)y2 * curStride + x2] : 0.f;
+    float o0 = 0.f, o1 = 0.f, o2 = 0.f, u = 0.f, v = 0.f;
+    if (z1 > 0 && z2 > 0) {
+        scene_flow_pre3d(sa, P.x, P.y, z1, o0, o1, o2);
+        u = Q.x;
+        v = Q.y;
+    }
+    obj[3 * i] = o0; obj[3 * i + 1] = o1; obj[3 * i + 2] = o2;
+    img[2 * i] = u; img[2 * i + 1] = v;
+}
+
+}  // namespace amos
+
+using namespace amos;
+
+struct amos_pnp {
+    int device = 0, maxPoints = 0, maxProblems = 0;
+    hipStream_t stream = nullptr;
+    bool ownStream = false;
+    float *dObj = nullptr, *dImg = nullptr;
+    int *dInt = nullptr;  // [0] zero offset, [1] count of the synchronous call, [2..6] its status
+    double *dRt = nullptr, *dScratch = nullptr;
+    uint8_t *dMask = nullptr;
+};
+
+static bool pnp_params_ok(double reprojection_error, double confidence, int max_iters)
+{
+    return reprojection_error > 0 && confidence > 0 && confidence < 1 && max_iters >= 1 && max_iters <= (1 << 20);
+}
+
+static bool pnp_camera_ok(double fx, double fy, double cx, double cy)
+{
+    return fx > 0 && fy > 0 && cx - cx == 0 && cy - cy == 0 && fx - fx == 0 && fy - fy == 0;
+}
+
+static int pnp_launch(amos_pnp *h, int n_problems, const float *d_obj, const float *d_img, const int *d_offsets, const int *d_counts, const uint8_t *d_select,
+                      double fx, double fy, double cx, double cy, double reprojection_error, double confidence, int max_iters, double *d_Rt, int *d_status,
+                      uint8_t *d_mask)
+{
+    PnpArgs a;
+    a.obj = d_obj; a.img = d_img;
+    a.offsets = d_offsets; a.counts = d_counts; a.select = d_select;
+    a.maxPoints = h->maxPoints; a.maxIters = max_iters;
+    a.thresh2 = (float)(reprojection_error * reprojection_error);  // findInliers: float t = (float)(thresh * thresh)
+    a.confidence = confidence;
+    a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy;
+    a.Rt = d_Rt; a.status = d_status; a.mask = d_mask;
+    a.scratch = h->dScratch;
+    hipLaunchKernelGGL(k_pnp_ransac, dim3(n_problems), dim3(kPnpThreads), 0, h->stream, a);
+    AMOS_HIP_CHECK(hipGetLastError());
+    return AMOS_OK;
+}
+
+extern "C" {
+
+int amos_pnp_create(int device, void *stream, int max_points, int max_problems, amos_pnp **out)
+{
+    if (!out || max_points < 1 || max_points > kPnpMaxPoints || max_problems < 1 || max_problems > 65535) {
+        set_error("amos_pnp_create: invalid argument (1 <= max_points <= %d, 1 <= max_problems <= 65535)", kPnpMaxPoints);
+        return AMOS_ERR_INVALID;
+    }
+    *out = nullptr;
+    AMOS_HIP_CHECK(hipSetDevice(device));
+    amos_pnp *h = new amos_pnp();
+    h->device = device; h->maxPoints = max_points; h->maxProblems = max_problems;
+    if (stream) h->stream = (hipStream_t)stream;
+    else {
+        if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { set_error("hipStreamCreate failed"); delete h; return AMOS_ERR_DEVICE; }
+        h->ownStream = true;
+    }
+    hipError_t e = hipMalloc((void **)&h->dObj, sizeof(float) * 3 * max_points);
+    if (e == hipSuccess) e = hipMalloc((void **)&h->dImg, sizeof(float) * 2 * max_points);
+    if (e == hipSuccess) e = hipMalloc((void **)&h->dInt, sizeof(int) * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&h->dRt, sizeof(double) * 12);
+    if (e == hipSuccess) e = hipMalloc((void **)&h->dScratch, sizeof(double) * kPnpScratch * (size_t)max_points * max_problems);
+    if (e == hipSuccess) e = hipMalloc((void **)&h->dMask, max_points);
+    if (e == hipSuccess) e = hipMemsetAsync(h->dInt, 0, sizeof(int) * 8, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) { set_error("amos_pnp_create: %s", hipGetErrorString(e)); amos_pnp_destroy(h); return AMOS_ERR_DEVICE; }
+    *out = h;
+    return AMOS_OK;
+}
+
+void amos_pnp_destroy(amos_pnp *h)
+{
+    if (!h) return;
+    (void)hipSetDevice(h->device);
+    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    for (void *q : {(void *)h->dObj, (void *)h->dImg, (void *)h->dInt, (void *)h->dRt, (void *)h->dScratch, (void *)h->dMask}) if (q) (void)hipFree(q);
+    if (h->ownStream && h->stream) (void)hipStreamDestroy(h->stream);
+    delete h;
+}
+
+void *amos_pnp_stream(amos_pnp *h) { return h ? (void *)h->stream : nullptr; }
+
+int amos_pnp_ransac_device(amos_pnp *h, int n_problems, const float *d_object_xyz, const float *d_image_xy, const int32_t *d_offsets, const int32_t *d_counts,
+                           const uint8_t *d_select, double fx, double fy, double cx, double cy, double reprojection_error, double confidence, int max_iters,
+                           double *d_Rt, int32_t *d_status, uint8_t *d_mask)
+{
+    if (!h || n_problems < 0 || n_problems > h->maxProblems || !d_object_xyz || !d_image_xy || !d_counts || !d_Rt || !d_status ||
+        !pnp_params_ok(reprojection_error, confidence, max_iters) || !pnp_camera_ok(fx, fy, cx, cy)) {
+        set_error("amos_pnp_ransac_device: invalid argument");
+        return AMOS_ERR_INVALID;
+    }
+    if (n_problems == 0) return AMOS_OK;
+    AMOS_HIP_CHECK(hipSetDevice(h->device));
+    return pnp_launch(h, n_problems, d_object_xyz, d_image_xy, d_offsets, d_counts, d_select, fx, fy, cx, cy, reprojection_error, confidence, max_iters, d_Rt,
+                      d_status, d_mask);
+}
+
+int amos_pnp_scene_flow_device(amos_pnp *h, const float *d_pre_xy, const float *d_next_xy, const uint8_t *d_state, const int32_t *d_n,
+                               const float *d_depth_last, size_t last_stride, const float *d_depth_cur, size_t cur_stride, int width, int height,
+                               const amos_scene_flow_camera *cam, double fx, double fy, double *d_Rt, int32_t *d_status, uint8_t *d_mask)
+{
+    if (!h || !d_pre_xy || !d_next_xy || !d_state || !d_n || !d_depth_last || !d_depth_cur || !cam || !d_Rt || !d_status || width < 1 || height < 1 ||
+        last_stride < (size_t)width || cur_stride < (size_t)width || !pnp_camera_ok(fx, fy, cam->cx, cam->cy)) {
+        set_error("amos_pnp_scene_flow_device: invalid argument");
+        return AMOS_ERR_INVALID;
+    }
+    AMOS_HIP_CHECK(hipSetDevice(h->device));
+    const SceneFlowArgs sa = scene_flow_args(cam);
+    hipLaunchKernelGGL(k_pnp_points, dim3((h->maxPoints + 255) / 256), dim3(256), 0, h->stream, (const float2 *)d_pre_xy, (const float2 *)d_next_xy, d_n,
+                       h->maxPoints, d_depth_last, last_stride, d_depth_cur, cur_stride, width, height, sa, h->dObj, h->dImg);
+    AMOS_HIP_CHECK(hipGetLastError());
+    // camera_mat of Tracking.cc:999-1004: fx, fy, cx, cy of mK (floats) as doubles; 500 iterations, 0.4 px, confidence 0.98
+    return pnp_launch(h, 1, h->dObj, h->dImg, h->dInt, d_n, d_state, fx, fy, (double)cam->cx, (double)cam->cy, 0.4, 0.98, 500, d_Rt, d_status, d_mask);
+}
+
+int amos_pnp_ransac(amos_pnp *h, int n, const float *object_xyz, const float *image_xy, double fx, double fy, double cx, double cy, double reprojection_error,
+                    double confidence, int max_iters, double *Rt, uint8_t *mask, int32_t *status)
+{
+    if (!h || n < 0 || n > h->maxPoints || (n > 0 && (!object_xyz || !image_xy)) || !Rt || !status || !pnp_params_ok(reprojection_error, confidence, max_iters) ||
+        !pnp_camera_ok(fx, fy, cx, cy)) {
+        set_error("amos_pnp_ransac: invalid argument (n <= max_points)");
+        return AMOS_ERR_INVALID;
+    }
+    AMOS_HIP_CHECK(hipSetDevice(h->device));
+    if (n > 0) {
+        AMOS_HIP_CHECK(hipMemcpyAsync(h->dObj, object_xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, h->stream));
+        AMOS_HIP_CHECK(hipMemcpyAsync(h->dImg, image_xy, sizeof(float) * 2 * n, hipMemcpyHostToDevice, h->stream));
+    }
+    AMOS_HIP_CHECK(hipMemcpyAsync(h->dInt + 1, &n, sizeof(int), hipMemcpyHostToDevice, h->stream));
+    const int rc = pnp_launch(h, 1, h->dObj, h->dImg, h->dInt, h->dInt + 1, nullptr, fx, fy, cx, cy, reprojection_error, confidence, max_iters, h->dRt, h->dInt + 2,
+                              h->dMask);
+    if (rc != AMOS_OK) return rc;
+    AMOS_HIP_CHECK(hipMemcpyAsync(Rt, h->dRt, sizeof(double) * 12, hipMemcpyDeviceToHost, h->stream));
+    AMOS_HIP_CHECK(hipMemcpyAsync(status, h->dInt + 2, sizeof(int) * kPnpStatus, hipMemcpyDeviceToHost, h->stream));
+    if (mask && n > 0) AMOS_HIP_CHECK(hipMemcpyAsync(mask, h->dMask, n, hipMemcpyDeviceToHost, h->stream));
+    AMOS_HIP_CHECK(hipStreamSynchronize(h->stream));
+    return AMOS_OK;
+}
+
+}  // extern "C"

@@ -10,6 +10,7 @@
 #include <type_traits>
 
 #include "amos_common.h"
+#include "amos_undistort.h"
 #include "../../include/amos_orb_pattern.h"
 #include "../../include/amos_host_types.h"
 
@@ -1691,34 +1692,6 @@ __global__ __launch_bounds__(256) void k_gate(const Geom *__restrict__ g, amos_k
         if (tid == 0) lvCount[frame * g->nLevels + level] = keepBase;
     }
     if (tid == 0) nRemoved[frame] = remBase;
-}
-
-// cv::undistortPoints(pts, pts, K, distCoef, Mat(), K) for one point, as Frame::UndistortKeyPoints and
-// Frame::ComputeImageBounds call it (Frame.cc:1052-1118, 1121-1170): OpenCV 4.5 cvUndistortPointsInternal
-// with its default criteria (exactly 5 fixed-point iterations, no epsilon test), double arithmetic,
-// k = (k1, k2, p1, p2, k3) and the remaining coefficients zero, R = I, P = K.  Shared by the device
-// kernel and the host-side image bounds.
-__host__ __device__ inline void undistort_point(float u, float v, double fx, double fy, double cx, double cy, const double (&k)[5],
-                                                float &xo, float &yo)
-{
-    const double ifx = 1. / fx, ify = 1. / fy;
-    double x = ((double)u - cx) * ifx, y = ((double)v - cy) * ify;
-    const double x0 = x, y0 = y;
-    for (int j = 0; j < 5; j++) {
-        const double r2 = x * x + y * y;
-        const double icdist = 1. / (1 + ((k[4] * r2 + k[1]) * r2 + k[0]) * r2);
-        if (icdist < 0) {  // OpenCV gives up and returns the normalised input point
-            x = ((double)u - cx) * ifx;
-            y = ((double)v - cy) * ify;
-            break;
-        }
-        const double deltaX = 2 * k[2] * x * y + k[3] * (r2 + 2 * x * x);
-        const double deltaY = k[2] * (r2 + 2 * y * y) + 2 * k[3] * x * y;
-        x = (x0 - deltaX) * icdist;
-        y = (y0 - deltaY) * icdist;
-    }
-    xo = (float)(fx * x + cx);  // RR = K * I; ww = 1
-    yo = (float)(fy * y + cy);
 }
 
 struct UndistortArgs {

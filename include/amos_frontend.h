@@ -594,8 +594,8 @@ int amos_cluster_kmeans(amos_slic *s, amos_slic_center *centers, int n_centers, 
 /* ---------------------------------------------------------------- scene flow, point arithmetic (8f-3) ---- */
 
 /* The reference's own per-point arithmetic inside Tracking::GetSceneFlowObj (src/Tracking.cc:850-1186), between its
- * OpenCV calls (goodFeaturesToTrack, cornerSubPix, calcOpticalFlowPyrLK, findFundamentalMat, solvePnPRansac stay with
- * the caller; device forms of the first four: amos_corners_*, amos_lk_*, amos_fmat_* below).  Points are interleaved (x, y) float pairs; all pointers are device pointers; asynchronous on `stream`.
+ * OpenCV calls (goodFeaturesToTrack, cornerSubPix, calcOpticalFlowPyrLK, findFundamentalMat, solvePnPRansac; their device
+ * forms: amos_corners_*, amos_lk_*, amos_fmat_*, amos_pnp_* below).  Points are interleaved (x, y) float pairs; all pointers are device pointers; asynchronous on `stream`.
  *
  * amos_flow_check_device (:902-925): state_out[i] = 0 when either position lies within 5 px of the image edge or the
  * 3 x 3 sum of absolute gray differences between (last, pre) and (cur, next) exceeds 2520; else state_in[i].  The
@@ -619,8 +619,8 @@ int amos_flow_scene_flow_device(void *stream, const float *d_depth_last, size_t 
                                 size_t cur_stride, const float *d_match_pre_xy, const float *d_match_cur_xy, int n,
                                 const amos_scene_flow_camera *cam, float *d_out);
 /* Hypothesis scoring for the three RANSACs of GetSceneFlowObj (Tracking.cc:927, 945: cv::findFundamentalMat(pre, cur, FM_RANSAC, 0.1, 0.99);
- * :1006: cv::solvePnPRansac(pre_3d, cur_2d, K, 0, rvec, tvec, false, 500, 0.4, 0.98, inliers, SOLVEPNP_P3P)).  The minimal solvers (7- / 8-point,
- * P3P), the sampling and the iteration-count update stay with the caller; the device takes what touches every point: the error of every
+ * :1006: cv::solvePnPRansac(pre_3d, cur_2d, K, 0, rvec, tvec, false, 500, 0.4, 0.98, inliers, SOLVEPNP_P3P)).  For a caller that runs its own RANSAC loop
+ * (the whole RANSACs: amos_fmat_* and amos_pnp_* below): the device takes what touches every point: the error of every
  * correspondence under every hypothesis (OpenCV's FMEstimatorCallback / PnPRansacCallback::computeError restated -- symmetric squared epipolar
  * distance in doubles; squared reprojection error of cv::projectPoints without distortion), the inlier test `err <= (float)(threshold^2)` and
  * the inlier count per hypothesis.  d_F: n_hypotheses x 9 doubles (row-major 3 x 3); d_Rt: n_hypotheses x 12 doubles (R row-major, then t);
@@ -702,6 +702,47 @@ int amos_fmat_scene_flow_pair_device(amos_fmat *h, const float *d_pre_xy, const 
                                      const int32_t *d_n, double *d_F1, double *d_F2, uint8_t *d_keep, int32_t *d_status);
 int amos_fmat_ransac(amos_fmat *h, int n, const float *p1_xy, const float *p2_xy, double threshold, double confidence, int max_iters,
                      double *F, uint8_t *mask, int32_t *status);
+
+/* cv::solvePnPRansac(obj, img, K, 0, rvec, tvec, false, max_iters, reprojection_error, confidence, inliers, SOLVEPNP_P3P) of
+ * Tracking::GetSceneFlowObj (Tracking.cc:1006) on the device: OpenCV 4.5's RANSAC with 4-point samples (cv::RNG((uint64)-1) local to
+ * the call, getSubset without a subset check, P3P (Gao et al.) choosing among its solutions by the 4th point, PnPRansacCallback::
+ * computeError, best model when inliers > max(best, 3), RANSACUpdateNumIters(p, ep, 4, n)), then solvePnP(SOLVEPNP_EPNP) on the RANSAC
+ * inliers (Lepetit et al.), restated from the published algorithms, written from memory: PARITY WITH OPENCV UNPINNED.  Every SVD, the
+ * quartic and the logarithm are replaced by + - * / sqrt constructions (amos_pnp_core.h); the pose is R | t, not
+ * OpenCV's R -> rvec -> R round trip.  Zero distortion.  One work-group per problem; a batch of problems is one launch; asynchronous on
+ * the handle's stream, no host synchronisation.
+ *
+ * amos_pnp_ransac_device: problem p reads the points [d_offsets[p], d_offsets[p] + d_counts[p]) of d_object_xyz ((x, y, z) float
+ * triples) and d_image_xy ((u, v) float pairs, pixels) (d_offsets NULL: p * max_points) and uses those with d_select[i] != 0
+ * (d_select NULL: all), in order.  d_counts[p] <= max_points (else status -3).  Outputs: d_Rt [p][12] (R row-major, then t: the
+ * layout amos_flow_pnp_score_device takes; zeros without a model); d_status [p][5] = {result, inliers, iterations run, points used,
+ * refit} with result 1 = model, 0 = no model, -1 = fewer than 4 points (OpenCV asserts), -2 = sampler redraw cap hit, -3 = count out
+ * of range; refit 1 = the EPnP refit on the inliers is returned, -1 = the refit was not finite and the RANSAC model is returned, 0 = no
+ * refit (no model, or exactly 4 points: OpenCV's direct P3P call, all four inliers, 0 iterations); d_mask (or NULL) indexed like the
+ * input: the RANSAC inliers of the returned result (OpenCV's _inliers), 0 elsewhere and for points not selected.  fx, fy > 0;
+ * reprojection_error > 0, 0 < confidence < 1, 1 <= max_iters <= 2^20 (the reference: 0.4, 0.98, 500); n_problems <= max_problems.
+ *
+ * amos_pnp_scene_flow_device: Tracking.cc:955-1007 as one call on n = *d_n tracked points (n <= max_points): the reference's point
+ * lists over the points with d_state != 0, in order -- where z1 > 0 && z2 > 0 (depth of the last frame at pre, of the current one at
+ * next; a pixel outside the width x height maps counts as no depth) the entry is pre_3d (amos_flow_scene_flow_device's arithmetic)
+ * -> next, elsewhere (0, 0, 0) -> (0, 0), kept in the list -- then the RANSAC with 500 iterations, 0.4 px, confidence 0.98 and
+ * K = (fx, fy, cam->cx, cam->cy) (the reference's camera_mat from mK).  d_Rt [12], d_status [5], d_mask (or NULL) [n].  No host
+ * synchronisation: capturable in a graph.
+ *
+ * amos_pnp_ransac: one problem from host pointers (n <= max_points), synchronous; Rt [12], mask (or NULL) [n], status [5]. */
+typedef struct amos_pnp amos_pnp;
+int amos_pnp_create(int device, void *stream, int max_points /* <= 4096 */, int max_problems, amos_pnp **out);
+void amos_pnp_destroy(amos_pnp *h);
+void *amos_pnp_stream(amos_pnp *h);
+int amos_pnp_ransac_device(amos_pnp *h, int n_problems, const float *d_object_xyz, const float *d_image_xy, const int32_t *d_offsets,
+                           const int32_t *d_counts, const uint8_t *d_select, double fx, double fy, double cx, double cy,
+                           double reprojection_error, double confidence, int max_iters, double *d_Rt, int32_t *d_status, uint8_t *d_mask);
+int amos_pnp_scene_flow_device(amos_pnp *h, const float *d_pre_xy, const float *d_next_xy, const uint8_t *d_state, const int32_t *d_n,
+                               const float *d_depth_last, size_t last_stride, const float *d_depth_cur, size_t cur_stride, int width,
+                               int height, const amos_scene_flow_camera *cam, double fx, double fy, double *d_Rt, int32_t *d_status,
+                               uint8_t *d_mask);
+int amos_pnp_ransac(amos_pnp *h, int n, const float *object_xyz, const float *image_xy, double fx, double fy, double cx, double cy,
+                    double reprojection_error, double confidence, int max_iters, double *Rt, uint8_t *mask, int32_t *status);
 
 #ifdef __cplusplus
 }
