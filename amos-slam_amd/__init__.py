@@ -32,7 +32,7 @@ EXPORTS = [
     "amos_orb_stream", "amos_orb_timing_enable", "amos_orb_timing_collect", "amos_match_create", "amos_match_destroy", "amos_match_sync", "amos_match_stream",
     "amos_match_distances", "amos_match_list_distances", "amos_match_list_best2", "amos_match_bruteforce_best2",
     "amos_match_bruteforce_best2_batch_device", "amos_match_set_bruteforce_kernel", "amos_slic_center_count", "amos_slic_create", "amos_slic_destroy", "amos_slic_stream",
-    "amos_slic_run", "amos_slic_batch_device", "amos_cluster_kmeans_batch_device", "amos_cluster_kmeans", "amos_cluster_bgr2lab_batch_device", "amos_flow_check_device", "amos_flow_epipolar_device", "amos_flow_scene_flow_device", "amos_flow_fundamental_score_device", "amos_flow_pnp_score_device", "amos_lk_create", "amos_lk_destroy", "amos_lk_stream", "amos_lk_levels", "amos_lk_track_device", "amos_mask_pre_create", "amos_mask_pre_destroy", "amos_mask_pre_stream", "amos_mask_preprocess_batch_device", "amos_mask_bias_act_device", "amos_mask_bias_relu_maxpool_device", "amos_mask_stem_weight_floats", "amos_mask_stem_weights_device", "amos_mask_stem_device", "amos_mask_conv1x1_supported", "amos_mask_conv1x1_device", "amos_mask_conv_supported", "amos_mask_conv_device", "amos_mask_conv_workspace_bytes", "amos_mask_conv_ws_device", "amos_mask_conv_tile_mode", "amos_mask_conv_kernel_name", "amos_mask_conv_chain_supported", "amos_mask_conv_chain_device", "amos_corners_create", "amos_corners_destroy", "amos_corners_stream", "amos_corners_good_features_device", "amos_corners_candidate_count", "amos_corners_subpix_device", "amos_fmat_create", "amos_fmat_destroy", "amos_fmat_stream", "amos_fmat_ransac_device", "amos_fmat_scene_flow_pair_device", "amos_fmat_ransac", "amos_pnp_create", "amos_pnp_destroy", "amos_pnp_stream", "amos_pnp_ransac_device", "amos_pnp_scene_flow_device", "amos_pnp_ransac", "amos_mask_winograd_supported", "amos_mask_winograd_weight_floats", "amos_mask_winograd_weights_device", "amos_mask_winograd_conv_device", "amos_mask_winograd24_weight_floats", "amos_mask_winograd24_weights_device", "amos_mask_winograd24_conv_device", "amos_mask_winograd24_conv_layout_device", "amos_mask_winograd24_persistent_mode", "amos_mask_winograd24_narrow_mode", "amos_mask_bilinear_nhwc_device", "amos_mask_bilinear_nhwc_act_device", "amos_mask_bilinear_x2_mode", "amos_mask_nms_column_max_device", "amos_mask_class_scores_device", "amos_mask_person_mask_device", "amos_mask_head_outputs_device", "amos_mask_head_outputs_scores_device", "amos_mask_person_masks_scores_device", "amos_mask_topk_rows_device", "amos_mask_topk_rows_sparse_device", "amos_mask_post_workspace_bytes", "amos_mask_person_masks_device", "amos_orb_detect_color_with_mask_pre_batch_device",
+    "amos_slic_run", "amos_slic_batch_device", "amos_cluster_kmeans_batch_device", "amos_cluster_kmeans", "amos_cluster_bgr2lab_batch_device", "amos_flow_check_device", "amos_flow_epipolar_device", "amos_flow_scene_flow_device", "amos_flow_fundamental_score_device", "amos_flow_pnp_score_device", "amos_lk_create", "amos_lk_destroy", "amos_lk_stream", "amos_lk_levels", "amos_lk_track_device", "amos_mask_pre_create", "amos_mask_pre_destroy", "amos_mask_pre_stream", "amos_mask_preprocess_batch_device", "amos_mask_bias_act_device", "amos_mask_bias_relu_maxpool_device", "amos_mask_stem_weight_floats", "amos_mask_stem_weights_device", "amos_mask_stem_device", "amos_mask_conv1x1_supported", "amos_mask_conv1x1_device", "amos_mask_conv_supported", "amos_mask_conv_device", "amos_mask_conv_workspace_bytes", "amos_mask_conv_ws_device", "amos_mask_conv_tile_mode", "amos_mask_conv_kernel_name", "amos_mask_conv_chain_supported", "amos_mask_conv_chain_device", "amos_corners_create", "amos_corners_destroy", "amos_corners_stream", "amos_corners_good_features_device", "amos_corners_candidate_count", "amos_corners_subpix_device", "amos_fmat_create", "amos_fmat_destroy", "amos_fmat_stream", "amos_fmat_ransac_device", "amos_fmat_scene_flow_pair_device", "amos_fmat_ransac", "amos_pnp_create", "amos_pnp_destroy", "amos_pnp_stream", "amos_pnp_ransac_device", "amos_pnp_scene_flow_device", "amos_pnp_ransac", "amos_orb_gate_labels_batch_device", "amos_dyna_create", "amos_dyna_destroy", "amos_dyna_stream", "amos_dyna_results_device", "amos_dyna_tail_device", "amos_dyna_reset_frame_device", "amos_dyna_decide_batch_device", "amos_dyna_scene_flow_obj_device", "amos_dyna_copy_to_host", "amos_mask_winograd_supported", "amos_mask_winograd_weight_floats", "amos_mask_winograd_weights_device", "amos_mask_winograd_conv_device", "amos_mask_winograd24_weight_floats", "amos_mask_winograd24_weights_device", "amos_mask_winograd24_conv_device", "amos_mask_winograd24_conv_layout_device", "amos_mask_winograd24_persistent_mode", "amos_mask_winograd24_narrow_mode", "amos_mask_bilinear_nhwc_device", "amos_mask_bilinear_nhwc_act_device", "amos_mask_bilinear_x2_mode", "amos_mask_nms_column_max_device", "amos_mask_class_scores_device", "amos_mask_person_mask_device", "amos_mask_head_outputs_device", "amos_mask_head_outputs_scores_device", "amos_mask_person_masks_scores_device", "amos_mask_topk_rows_device", "amos_mask_topk_rows_sparse_device", "amos_mask_post_workspace_bytes", "amos_mask_person_masks_device", "amos_orb_detect_color_with_mask_pre_batch_device",
 ]
 
 
@@ -251,6 +251,16 @@ class OrbExtractor:
     def gate_batch_device(self, d_masks, mask_frame_stride, mask_row_stride):
         _check(self.L.amos_orb_gate_batch_device(self.h, C.c_void_p(d_masks), C.c_size_t(mask_frame_stride),
                                                  C.c_size_t(mask_row_stride)), "amos_orb_gate_batch_device")
+
+    def gate_labels_batch_device(self, d_masks, mask_frame_stride, mask_row_stride, d_labels, label_frame_stride, label_row_stride, d_centers,
+                                 centers_frame_stride, n_centers, d_rm, rm_frame_stride, n_rm, d_status):
+        """MovingKeyPoints with CalDyna's label gate per frame (Frame.cc:633): labels float64 [frames][h][w], centres amos_slic_center
+        records (.id read), rm int32 [frames][n_rm]; strides in elements (records for the centres).  d_status int32 [n_frames]."""
+        _check(self.L.amos_orb_gate_labels_batch_device(self.h, C.c_void_p(d_masks), C.c_size_t(mask_frame_stride), C.c_size_t(mask_row_stride),
+                                                        C.c_void_p(d_labels), C.c_size_t(label_frame_stride), C.c_size_t(label_row_stride),
+                                                        C.c_void_p(d_centers), C.c_size_t(centers_frame_stride), C.c_int(n_centers), C.c_void_p(d_rm),
+                                                        C.c_size_t(rm_frame_stride), C.c_int(n_rm), C.c_void_p(d_status)),
+               "amos_orb_gate_labels_batch_device")
 
     def describe_batch_device(self):
         _check(self.L.amos_orb_describe_batch_device(self.h), "amos_orb_describe_batch_device")
@@ -966,3 +976,112 @@ class PnpRansac:
                                                  C.c_void_p(d_depth_last), C.c_size_t(last_stride), C.c_void_p(d_depth_cur), C.c_size_t(cur_stride),
                                                  C.c_int(width), C.c_int(height), C.byref(cam), C.c_double(fx), C.c_double(fy), C.c_void_p(d_Rt),
                                                  C.c_void_p(d_status), C.c_void_p(d_mask)), "amos_pnp_scene_flow_device")
+
+
+DYNA_MAX_K, DYNA_COUNTS = 64, 6
+DYNA_NO_PNP, DYNA_NO_F2, DYNA_BAD_N, DYNA_RESET = 1, 2, 4, 8
+DYNA_BAD_MATCH_LABEL, DYNA_BAD_TM_LABEL, DYNA_BAD_ID = 1, 2, 4
+
+
+class DynaPoses(C.Structure):
+    """amos_dyna_poses: MotionModel and computeMtcwUseLK's mTcw as rows of [R | t] (3 x 4 floats)."""
+    _fields_ = [("motion", C.c_float * 12), ("lk", C.c_float * 12), ("has_lk", C.c_int32)]
+
+    @classmethod
+    def of(cls, motion, lk=None):
+        p = cls()
+        for i, v in enumerate(np.asarray(motion, np.float32).reshape(-1)[:12]):
+            p.motion[i] = float(v)
+        if lk is not None:
+            for i, v in enumerate(np.asarray(lk, np.float32).reshape(-1)[:12]):
+                p.lk[i] = float(v)
+            p.has_lk = 1
+        return p
+
+
+class DynaResults(C.Structure):
+    """amos_dyna_results: device addresses of the per-slot arrays (see include/amos_frontend.h)."""
+    _fields_ = [("max_points", C.c_int32), ("max_frames", C.c_int32)] + [(k, C.c_void_p) for k in (
+        "pose", "rwc", "ow", "choice", "counts", "match_xy", "rpe", "epipolar", "tm_xy", "flow", "status", "ave_rpe", "ep_num", "decide_status",
+        "pre_xy", "next_xy", "state", "n", "F1", "F2", "fmat_status", "Rt", "pnp_status")]
+
+
+class SceneFlowDyna:
+    """amos_dyna_*: the tail of Tracking::GetSceneFlowObj (Tracking.cc:1012-1184: both poses' reprojection errors, the choice, SetPose,
+    mvepipolar / T_M under F2, vFlow_3d) and CalDyna's moving-cluster decision (Frame.cc:552-628) on the device, per result slot."""
+
+    def __init__(self, max_points=4096, max_frames=64, device=0, stream=None):
+        self.L = lib()
+        self.L.amos_dyna_stream.restype = C.c_void_p
+        self.L.amos_dyna_stream.argtypes = [C.c_void_p]
+        self.L.amos_dyna_destroy.restype = None
+        self.L.amos_dyna_destroy.argtypes = [C.c_void_p]
+        h = C.c_void_p()
+        _check(self.L.amos_dyna_create(C.c_int(device), C.c_void_p(stream), C.c_int(max_points), C.c_int(max_frames), C.byref(h)), "amos_dyna_create")
+        self.h = h
+        self.max_points, self.max_frames = max_points, max_frames
+        self.results = DynaResults()
+        _check(self.L.amos_dyna_results_device(self.h, C.byref(self.results)), "amos_dyna_results_device")
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.amos_dyna_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    @property
+    def stream(self):
+        return self.L.amos_dyna_stream(self.h)
+
+    def tail_device(self, frame, d_pre, d_next, d_state, d_n, d_F2, d_fmat_status, d_Rt, d_pnp_status, d_depth_last, last_stride, d_depth_cur,
+                    cur_stride, width, height, cam, fx, fy, poses):
+        """Tracking.cc:1012-1184 into slot `frame`; strides in floats; cam a SceneFlowCamera, poses a DynaPoses."""
+        _check(self.L.amos_dyna_tail_device(self.h, C.c_int(frame), C.c_void_p(d_pre), C.c_void_p(d_next), C.c_void_p(d_state), C.c_void_p(d_n),
+                                            C.c_void_p(d_F2), C.c_void_p(d_fmat_status), C.c_void_p(d_Rt), C.c_void_p(d_pnp_status),
+                                            C.c_void_p(d_depth_last), C.c_size_t(last_stride), C.c_void_p(d_depth_cur), C.c_size_t(cur_stride),
+                                            C.c_int(width), C.c_int(height), C.byref(cam), C.c_double(fx), C.c_double(fy), C.byref(poses)),
+               "amos_dyna_tail_device")
+
+    def reset_frame_device(self, frame):
+        _check(self.L.amos_dyna_reset_frame_device(self.h, C.c_int(frame)), "amos_dyna_reset_frame_device")
+
+    def decide_batch_device(self, n_frames, d_labels, label_frame_stride, label_row_stride, width, height, d_centers, centers_frame_stride, n_centers,
+                            k, d_rm, rm_frame_stride):
+        """Frame.cc:552-628 for slots 0 .. n_frames - 1: rm int32 [n_frames][rm_frame_stride] (k entries); strides in elements."""
+        _check(self.L.amos_dyna_decide_batch_device(self.h, C.c_int(n_frames), C.c_void_p(d_labels), C.c_size_t(label_frame_stride),
+                                                    C.c_size_t(label_row_stride), C.c_int(width), C.c_int(height), C.c_void_p(d_centers),
+                                                    C.c_size_t(centers_frame_stride), C.c_int(n_centers), C.c_int(k), C.c_void_p(d_rm),
+                                                    C.c_size_t(rm_frame_stride)), "amos_dyna_decide_batch_device")
+
+    def scene_flow_obj_device(self, frame, corners, lk, fmat, pnp, d_imlast, last_gray_stride, d_gray, gray_stride, width, height, d_depth_last,
+                              last_stride, d_depth_cur, cur_stride, cam, fx, fy, poses):
+        """The whole of GetSceneFlowObj (Tracking.cc:894-1184) as one call on the four handles (same stream as this one)."""
+        _check(self.L.amos_dyna_scene_flow_obj_device(self.h, C.c_int(frame), corners.h, lk.k, fmat.h, pnp.h, C.c_void_p(d_imlast),
+                                                      C.c_size_t(last_gray_stride), C.c_void_p(d_gray), C.c_size_t(gray_stride), C.c_int(width),
+                                                      C.c_int(height), C.c_void_p(d_depth_last), C.c_size_t(last_stride), C.c_void_p(d_depth_cur),
+                                                      C.c_size_t(cur_stride), C.byref(cam), C.c_double(fx), C.c_double(fy), C.byref(poses)),
+               "amos_dyna_scene_flow_obj_device")
+
+    def _get(self, addr, dtype, count, offset=0):
+        out = np.zeros(count, dtype)
+        if count:
+            _check(self.L.amos_dyna_copy_to_host(self.h, C.c_void_p(out.ctypes.data), C.c_void_p(addr + offset * np.dtype(dtype).itemsize),
+                                                 C.c_size_t(out.nbytes)), "amos_dyna_copy_to_host")
+        return out
+
+    def fetch(self, frame, n_tracked=0, k=0):
+        """Slot `frame` copied to the host (synchronous): a dict of numpy arrays, lists cut to their counts; mvepipolar has n_tracked
+        entries, AveClusterRpe / epNum k (from the last decide)."""
+        r, P = self.results, self.max_points
+        counts = self._get(r.counts, np.int32, DYNA_COUNTS, DYNA_COUNTS * frame)
+        N, V, _, _, T, F = (int(c) for c in counts)
+        return dict(
+            counts=counts, pose=self._get(r.pose, np.float32, 12, 12 * frame), rwc=self._get(r.rwc, np.float32, 9, 9 * frame),
+            ow=self._get(r.ow, np.float32, 3, 3 * frame), choice=int(self._get(r.choice, np.int32, 1, frame)[0]),
+            status=int(self._get(r.status, np.int32, 1, frame)[0]),
+            match=self._get(r.match_xy, np.float32, 2 * V, 2 * P * frame).reshape(-1, 2), rpe=self._get(r.rpe, np.float32, V, P * frame),
+            epipolar=self._get(r.epipolar, np.float64, n_tracked, P * frame), tm=self._get(r.tm_xy, np.float32, 2 * T, 2 * P * frame).reshape(-1, 2),
+            flow=self._get(r.flow, np.float32, 3 * F, 3 * P * frame).reshape(-1, 3),
+            ave_rpe=self._get(r.ave_rpe, np.float32, k, DYNA_MAX_K * frame), ep_num=self._get(r.ep_num, np.int32, k, DYNA_MAX_K * frame),
+            decide_status=int(self._get(r.decide_status, np.int32, 1, frame)[0]))

@@ -1011,6 +1011,41 @@ int amos_orb_gate_batch_device(amos_orb *h, const uint8_t *d_masks, size_t mask_
     return AMOS_OK;
 }
 
+int amos_orb_gate_labels_batch_device(amos_orb *h, const uint8_t *d_masks, size_t mask_frame_stride, size_t mask_row_stride, const double *d_labels,
+                                      size_t label_frame_stride, size_t label_row_stride, const amos_slic_center *d_centers,
+                                      size_t centers_frame_stride, int n_centers, const int32_t *d_rm, size_t rm_frame_stride, int n_rm, int32_t *d_status)
+{
+    if (!h || !d_masks || mask_row_stride < 1 || !d_labels || !d_centers || !d_rm || !d_status || n_centers < 1 || n_rm < 1 ||
+        label_row_stride > (size_t)INT32_MAX) {
+        set_error("amos_orb_gate_labels_batch_device: invalid argument");
+        return AMOS_ERR_INVALID;
+    }
+    if (!h->detected) { set_error("amos_orb_gate_labels_batch_device before detect"); return AMOS_ERR_STATE; }
+    const Geom &g = h->geom;
+    if (label_row_stride < (size_t)g.W) { set_error("amos_orb_gate_labels_batch_device: label rows shorter than the frame"); return AMOS_ERR_INVALID; }
+    AMOS_HIP_CHECK(hipSetDevice(h->device));
+    const size_t planeStride = (size_t)h->maskPitch * h->maxH;
+    dim3 grid((g.W + kMorphTileW - 1) / kMorphTileW, (g.H + kMorphTileH - 1) / kMorphTileH, h->nFrames);
+    AMOS_HIP_CHECK(hipMemsetAsync(d_status, 0, sizeof(int32_t) * h->nFrames, h->stream));
+    hipLaunchKernelGGL(k_morph31<true>, grid, dim3(256), 0, h->stream, d_masks, mask_frame_stride, (int)mask_row_stride, h->dMaskTmp, planeStride,
+                       h->maskPitch, g.W, g.H);
+    hipLaunchKernelGGL(k_morph31<false>, grid, dim3(256), 0, h->stream, h->dMaskTmp, planeStride, h->maskPitch, h->dMaskClosed, planeStride,
+                       h->maskPitch, g.W, g.H);
+    GateLabelStrides ls;
+    constexpr int kRecInts = (int)(sizeof(amos_slic_center) / sizeof(int32_t));
+    ls.labelFrame = label_frame_stride;
+    ls.centerFrame = centers_frame_stride * kRecInts;
+    ls.rmFrame = rm_frame_stride;
+    ls.errFrame = 1;
+    ls.centerStride = kRecInts;
+    const int *ids = (const int *)d_centers + offsetof(amos_slic_center, id) / sizeof(int32_t);
+    hipLaunchKernelGGL(k_gate, dim3(h->nFrames), dim3(256), 0, h->stream, h->dGeom, h->dLvKps, h->dLvCount, h->dMaskClosed, planeStride, h->maskPitch,
+                       d_labels, (int)label_row_stride, ids, n_centers, (const int *)d_rm, n_rm, h->dRemoved, h->dNRemoved, (int *)d_status, ls);
+    AMOS_HIP_CHECK(hipGetLastError());
+    h->gated = true;
+    return AMOS_OK;
+}
+
 int amos_orb_describe_batch_device(amos_orb *h)
 {
     if (!h || !h->detected) { set_error("amos_orb_describe_batch_device before detect"); return AMOS_ERR_STATE; }

@@ -1633,21 +1633,33 @@ __global__ __launch_bounds__(256) void k_morph31(const uint8_t *__restrict__ src
     }
 }
 
+// Per-frame offsets of the label gate's inputs (elements) and the element stride of the centre ids: the defaults are the single shared
+// label map / id array / rm vector / error word of amos_orb_gate and amos_orb_gate_batch_device; amos_orb_gate_labels_batch_device reads
+// one of each per frame and the ids straight out of amos_slic_center records.
+struct GateLabelStrides {
+    size_t labelFrame = 0, centerFrame = 0, rmFrame = 0, errFrame = 0;
+    int centerStride = 1;
+};
+
 // One work-group per frame walks the levels in order; kept keypoints are compacted in place
 // (order preserved), removed ones appended to `removed` in the reference's order.
 __global__ __launch_bounds__(256) void k_gate(const Geom *__restrict__ g, amos_keypoint *__restrict__ lvKps,
                                              int *__restrict__ lvCount, const uint8_t *__restrict__ closedBase,
-                                             size_t closedFrameStride, int maskStride, const double *__restrict__ labels,
+                                             size_t closedFrameStride, int maskStride, const double *__restrict__ labelBase,
                                              int labelStride,
-                                             const int *__restrict__ centerIds, int nCenters,
-                                             const int *__restrict__ rm, int nRm,
+                                             const int *__restrict__ centerIdBase, int nCenters,
+                                             const int *__restrict__ rmBase, int nRm,
                                              amos_keypoint *__restrict__ removed, int *__restrict__ nRemoved,
-                                             int *__restrict__ errFlag)
+                                             int *__restrict__ errBase, const GateLabelStrides ls = GateLabelStrides())
 {
     __shared__ int wkeep[4], wrem[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int frame = blockIdx.x;
     const uint8_t *closed = closedBase + (size_t)frame * closedFrameStride;
+    const double *labels = labelBase ? labelBase + (size_t)frame * ls.labelFrame : nullptr;
+    const int *centerIds = centerIdBase ? centerIdBase + (size_t)frame * ls.centerFrame : nullptr;
+    const int *rm = rmBase ? rmBase + (size_t)frame * ls.rmFrame : nullptr;
+    int *errFlag = errBase + (size_t)frame * ls.errFrame;
     int remBase = 0;
     for (int level = 0; level < g->nLevels; level++) {
         const LevelGeom &lg = g->lv[level];
@@ -1669,7 +1681,7 @@ __global__ __launch_bounds__(256) void k_gate(const Geom *__restrict__ g, amos_k
                         const long ci = (long)(labels[(size_t)iy * labelStride + ix] - 1);
                         if (ci < 0 || ci >= nCenters) atomicOr(errFlag, 2);
                         else {
-                            const int id = centerIds[ci];
+                            const int id = centerIds[(size_t)ci * ls.centerStride];
                             if (id < 0 || id >= nRm) atomicOr(errFlag, 2);
                             else if (rm[id] == 1) drop = true;
                         }

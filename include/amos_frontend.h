@@ -191,6 +191,16 @@ int amos_orb_detect_batch_device(amos_orb *h, const uint8_t *d_gray, size_t fram
                                  int width, int height, int n_frames);
 int amos_orb_gate_batch_device(amos_orb *h, const uint8_t *d_masks, size_t mask_frame_stride,
                                size_t mask_row_stride);
+/* The same gate with CalDyna's label gate per frame (ORBextractor::MovingKeyPoints with labelMask, centers[].id, rmVector,
+ * Frame.cc:633): a keypoint is also removed where rm[centers[(int) labels(y, x) - 1].id] == 1.  Frame f reads d_labels + f *
+ * label_frame_stride (doubles, rows label_row_stride elements apart), d_centers + f * centers_frame_stride (records; .id is read) and
+ * d_rm + f * rm_frame_stride (n_rm int32).  d_status [n_frames]: 0, or bit 1 a keypoint outside the mask, bit 2 a label outside
+ * [1, n_centers] or an id outside [0, n_rm) (the keypoint is then kept, as amos_orb_gate does).  Follow with amos_orb_describe_batch_device. */
+struct amos_slic_center;
+int amos_orb_gate_labels_batch_device(amos_orb *h, const uint8_t *d_masks, size_t mask_frame_stride, size_t mask_row_stride,
+                                      const double *d_labels, size_t label_frame_stride, size_t label_row_stride,
+                                      const struct amos_slic_center *d_centers, size_t centers_frame_stride, int n_centers,
+                                      const int32_t *d_rm, size_t rm_frame_stride, int n_rm, int32_t *d_status);
 int amos_orb_describe_batch_device(amos_orb *h);
 
 /* ---- callers either side of the path (SURVEY 8f "next" rows), device resident ----
@@ -743,6 +753,100 @@ int amos_pnp_scene_flow_device(amos_pnp *h, const float *d_pre_xy, const float *
                                uint8_t *d_mask);
 int amos_pnp_ransac(amos_pnp *h, int n, const float *object_xyz, const float *image_xy, double fx, double fy, double cx, double cy,
                     double reprojection_error, double confidence, int max_iters, double *Rt, uint8_t *mask, int32_t *status);
+
+/* ---------------------------------------------------------------- dynamic-object test (8f-3 tail, CalDyna) ----
+ * The tail of Tracking::GetSceneFlowObj (src/Tracking.cc:1012-1184) and the decision of Frame::CalDyna (src/Frame.cc:552-628) on the
+ * device, so that GetSceneFlowObj -> cluster -> decision -> labelled gate -> describe is one stream of work without a host
+ * synchronisation (capturable in a graph).  Asynchronous on the handle's stream.  A handle holds max_frames result slots of
+ * max_points (<= 4096) entries each.
+ *
+ * amos_dyna_tail_device: on n = *d_n tracked points (the lists of the reference are the points with d_state != 0, in order; N of them):
+ *   z1 / z2 = depth of the last frame at (int) pre, of the current one at (int) next (outside the width x height maps: no depth);
+ *   pre_3d / cur_2d = (amos_flow_scene_flow_device's pre_3d, next) where z1 > 0 && z2 > 0, else (0, 0, 0) / (0, 0) -- the PnP's lists;
+ *   Mod = d_Rt (R row-major, then t: amos_pnp_scene_flow_device's output) cast to float; MotionModel = poses->motion.
+ *   For every list entry with pre_3d.z > 0 && cur_2d.x != 0 && cur_2d.y != 0 (the mvMatch entries, in order): Rpe under
+ *   (poses->lk if has_lk, else Mod) and under MotionModel -- cv::projectPoints evaluated with R itself (no Rodrigues round trip: the
+ *   pose's floats as doubles, 1 / z or 1 where z == 0, u and v stored as float), Rpe = sqrtf(du^2 + dv^2) in float; an inlier when
+ *   (double) Rpe <= 0.4.  PnP inliers >= motion-model inliers chooses Mod (choice 1; also when has_lk: the LK pose scores, Mod is the
+ *   output), else MotionModel (choice 0); mvRpe is the chosen list.  Frame::SetPose: Rwc = Rcw^T, Ow = -Rcw^T tcw (double accumulation,
+ *   one rounding).  mvepipolar[i] (i < n) = dd under d_F2 (amos_flow_epipolar_device's arithmetic) where state != 0, 0 elsewhere;
+ *   T_M = next[i] where state != 0 && !(dd <= 1), in order.  vFlow_3d = (next.x, next.y, sf_norm) for the list entries with
+ *   z1 > 0 && z2 > 0 and sf_norm > 3, sf_norm as amos_flow_scene_flow_device computes it but with the chosen Rwc / Ow.
+ *   Where the PnP has no model (d_pnp_status[0] != 1; the reference fails in Rodrigues) Mod is the zeros d_Rt holds and
+ *   AMOS_DYNA_NO_PNP is set: the caller keeps its host path there.  Where F2 has no model (d_fmat_status[4] != 1: amos_fmat_scene_flow_pair_device's
+ *   [2][4] status) the zero F gives dd = NaN, so every tracked point is in T_M, and AMOS_DYNA_NO_F2 is set.  Camera, poses: copied at the call.
+ * amos_dyna_reset_frame_device: slot `frame` holds the first frame's empty lists (GetSceneFlowObj is not called, Tracking.cc:377).
+ * amos_dyna_decide_batch_device: frame f of the batch reads slot f and the labels (labelMask, doubles, frame f at d_labels +
+ *   f * label_frame_stride, rows label_row_stride elements apart) and centres (d_centers + f * centers_frame_stride records, center.id
+ *   the k-means cluster) of that frame.  clusterRpe: mvRpe[i] goes to cluster centers[(int) labelMask((int) y, (int) x) - 1].id of
+ *   mvMatch[i]; AveClusterRpe[c] = (float sum in list order) / (float) count (an empty cluster: 0 / 0 = NaN, never removed); epNum[c]
+ *   = the number of distinct superpixels holding a T_M point whose centre has id c; d_rm[f * rm_frame_stride + c] = epNum[c] > 0 &&
+ *   AveClusterRpe[c] >= 3, for c < k (k <= 64).  A label of 0 or above n_centers (the reference reads centers[-1]), a point outside the map or
+ *   an id outside [0, k) is skipped and flagged in the slot's decide status.
+ * amos_dyna_scene_flow_obj_device: the whole of GetSceneFlowObj (Tracking.cc:894-1184) as one call on the four handles (which must share
+ *   the dyna handle's stream): goodFeaturesToTrack(imlast, 1000, 0.01, 8, 3, Harris 0.04) -> cornerSubPix(10 x 10, 20, 0.03) ->
+ *   calcOpticalFlowPyrLK(22 x 22, 20, 0.01) -> the SAD / border check -> the two findFundamentalMat RANSACs -> solvePnPRansac -> the
+ *   tail into slot `frame`.  The working lists stay in the handle (amos_dyna_results_device); LK and the check run on all
+ *   min(1000, max_points) corner slots (the unused ones zeroed), the RANSACs and the tail on the *d_n found.
+ * Invalid arguments: AMOS_ERR_INVALID; create without a device: AMOS_ERR_DEVICE. */
+#define AMOS_DYNA_MAX_K 64
+#define AMOS_DYNA_COUNTS 6       /* N (state != 0), mvMatch, PNP_inlier, MM_inlier, T_M, vFlow_3d */
+#define AMOS_DYNA_NO_PNP 1       /* tail status bits */
+#define AMOS_DYNA_NO_F2 2
+#define AMOS_DYNA_BAD_N 4        /* *d_n outside [0, max_points]: nothing computed, counts 0 */
+#define AMOS_DYNA_RESET 8        /* amos_dyna_reset_frame_device */
+#define AMOS_DYNA_BAD_MATCH_LABEL 1  /* decide status bits */
+#define AMOS_DYNA_BAD_TM_LABEL 2
+#define AMOS_DYNA_BAD_ID 4
+typedef struct amos_dyna amos_dyna;
+typedef struct amos_dyna_poses {
+    float motion[12]; /* MotionModel = mVelocity * mLastFrame.mTcw (or mLastFrame.mTcw), rows of [R | t] */
+    float lk[12];     /* computeMtcwUseLK's mTcw, rows of [R | t], read when has_lk != 0 */
+    int32_t has_lk;
+} amos_dyna_poses;
+typedef struct amos_dyna_results {
+    int32_t max_points, max_frames;
+    float *pose;            /* [frame][12] chosen Tcw, rows of [R | t] */
+    float *rwc, *ow;        /* [frame][9], [frame][3] Frame::mRwc, mOw after SetPose */
+    int32_t *choice;        /* [frame] 1 = PnP (Mod), 0 = motion model */
+    int32_t *counts;        /* [frame][AMOS_DYNA_COUNTS] */
+    float *match_xy;        /* [frame][max_points][2] mvMatch */
+    float *rpe;             /* [frame][max_points] mvRpe */
+    double *epipolar;       /* [frame][max_points] mvepipolar (n entries) */
+    float *tm_xy;           /* [frame][max_points][2] T_M */
+    float *flow;            /* [frame][max_points][3] vFlow_3d */
+    int32_t *status;        /* [frame] tail status bits */
+    float *ave_rpe;         /* [frame][AMOS_DYNA_MAX_K] AveClusterRpe (k entries) */
+    int32_t *ep_num;        /* [frame][AMOS_DYNA_MAX_K] epNum (k entries) */
+    int32_t *decide_status; /* [frame] decide status bits */
+    /* working lists of the last amos_dyna_scene_flow_obj_device call */
+    float *pre_xy, *next_xy; /* [max_points][2] prepoint (sub-pixel corners), nextpoint */
+    uint8_t *state;          /* [max_points] after the SAD / border check */
+    int32_t *n;              /* [1] corner count */
+    double *F1, *F2;         /* [9] each */
+    int32_t *fmat_status;    /* [2][4] */
+    double *Rt;              /* [12] */
+    int32_t *pnp_status;     /* [5] */
+} amos_dyna_results;
+int amos_dyna_create(int device, void *stream, int max_points /* <= 4096 */, int max_frames, amos_dyna **out);
+void amos_dyna_destroy(amos_dyna *h);
+void *amos_dyna_stream(amos_dyna *h);
+int amos_dyna_results_device(amos_dyna *h, amos_dyna_results *out);
+/* Synchronous copy of `bytes` from a result array (d_src, device) to host memory on the handle's stream (callers that need a list on
+ * the host, e.g. a drawer; tests). */
+int amos_dyna_copy_to_host(amos_dyna *h, void *dst, const void *d_src, size_t bytes);
+int amos_dyna_tail_device(amos_dyna *h, int frame, const float *d_pre_xy, const float *d_next_xy, const uint8_t *d_state, const int32_t *d_n,
+                          const double *d_F2, const int32_t *d_fmat_status, const double *d_Rt, const int32_t *d_pnp_status,
+                          const float *d_depth_last, size_t last_stride, const float *d_depth_cur, size_t cur_stride, int width, int height,
+                          const amos_scene_flow_camera *cam, double fx, double fy, const amos_dyna_poses *poses);
+int amos_dyna_reset_frame_device(amos_dyna *h, int frame);
+int amos_dyna_decide_batch_device(amos_dyna *h, int n_frames, const double *d_labels, size_t label_frame_stride, size_t label_row_stride,
+                                  int width, int height, const amos_slic_center *d_centers, size_t centers_frame_stride, int n_centers, int k,
+                                  int32_t *d_rm, size_t rm_frame_stride);
+int amos_dyna_scene_flow_obj_device(amos_dyna *h, int frame, amos_corners *corners, amos_lk *lk, amos_fmat *fmat, amos_pnp *pnp,
+                                    const uint8_t *d_imlast_gray, size_t last_gray_stride, const uint8_t *d_gray, size_t gray_stride, int width,
+                                    int height, const float *d_depth_last, size_t last_stride, const float *d_depth_cur, size_t cur_stride,
+                                    const amos_scene_flow_camera *cam, double fx, double fy, const amos_dyna_poses *poses);
 
 #ifdef __cplusplus
 }
