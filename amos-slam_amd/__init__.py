@@ -833,28 +833,40 @@ class OrbMatcher:
         return self.L.amos_match_stream(self.m)
 
 
-class CornerDetector:
-    """amos_corners_*: cv::goodFeaturesToTrack (Harris) + cv::cornerSubPix of Tracking::GetSceneFlowObj (Tracking.cc:894-895) on
-    device-resident gray frames; the corners stay on the device (feed LkTracker.track_device)."""
+class _Handle:
+    """A stream-owning library handle amos_<kind>_*: .h the handle, .L the library, .stream its HIP stream; close() destroys it."""
+    _kind = None
 
-    def __init__(self, max_width=640, max_height=480, device=0, stream=None):
+    def _open(self, device, stream, *sizes):
+        """amos_<kind>_create(device, stream, *sizes (ints), &handle)"""
         self.L = lib()
-        self.L.amos_corners_stream.restype = C.c_void_p
-        self.L.amos_corners_destroy.restype = None
+        f_create, f_stream, f_destroy = (getattr(self.L, f"amos_{self._kind}_{f}") for f in ("create", "stream", "destroy"))
+        f_stream.restype, f_stream.argtypes = C.c_void_p, [C.c_void_p]
+        f_destroy.restype, f_destroy.argtypes = None, [C.c_void_p]
         h = C.c_void_p()
-        _check(self.L.amos_corners_create(C.c_int(device), C.c_void_p(stream), C.c_int(max_width), C.c_int(max_height), C.byref(h)), "amos_corners_create")
+        _check(f_create(C.c_int(device), C.c_void_p(stream), *(C.c_int(v) for v in sizes), C.byref(h)), f"amos_{self._kind}_create")
         self.h = h
 
     def close(self):
         if getattr(self, "h", None):
-            self.L.amos_corners_destroy(self.h)
+            getattr(self.L, f"amos_{self._kind}_destroy")(self.h)
             self.h = None
 
     __del__ = close
 
     @property
     def stream(self):
-        return self.L.amos_corners_stream(self.h)
+        return getattr(self.L, f"amos_{self._kind}_stream")(self.h)
+
+
+class CornerDetector(_Handle):
+    """amos_corners_*: cv::goodFeaturesToTrack (Harris) + cv::cornerSubPix of Tracking::GetSceneFlowObj (Tracking.cc:894-895) on
+    device-resident gray frames; the corners stay on the device (feed LkTracker.track_device)."""
+
+    _kind = "corners"
+
+    def __init__(self, max_width=640, max_height=480, device=0, stream=None):
+        self._open(device, stream, max_width, max_height)
 
     def good_features_device(self, gray_ptr, stride, width, height, xy_ptr, xy_capacity, count_ptr, max_corners=1000, quality=0.01, min_distance=8.0,
                              harris_k=0.04, response_ptr=None):
@@ -874,32 +886,16 @@ class CornerDetector:
                "amos_corners_subpix_device")
 
 
-class FundamentalRansac:
+class FundamentalRansac(_Handle):
     """amos_fmat_*: cv::findFundamentalMat(p1, p2, FM_RANSAC, threshold, confidence) of Tracking::GetSceneFlowObj (Tracking.cc:927, 945) on the
     device (restated, parity with OpenCV unpinned).  status = (result, inliers, iterations, points): result 1 model, 0 none, -1 for
     7 <= points < 15 (OpenCV's LMeDS branch, not built), -2 sampler cap, -3 count out of range."""
 
+    _kind = "fmat"
+
     def __init__(self, max_points=4096, max_problems=64, device=0, stream=None):
-        self.L = lib()
-        self.L.amos_fmat_stream.restype = C.c_void_p
-        self.L.amos_fmat_stream.argtypes = [C.c_void_p]
-        self.L.amos_fmat_destroy.restype = None
-        self.L.amos_fmat_destroy.argtypes = [C.c_void_p]
-        h = C.c_void_p()
-        _check(self.L.amos_fmat_create(C.c_int(device), C.c_void_p(stream), C.c_int(max_points), C.c_int(max_problems), C.byref(h)), "amos_fmat_create")
-        self.h = h
+        self._open(device, stream, max_points, max_problems)
         self.max_points = max_points
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.amos_fmat_destroy(self.h)
-            self.h = None
-
-    __del__ = close
-
-    @property
-    def stream(self):
-        return self.L.amos_fmat_stream(self.h)
 
     def ransac(self, p1, p2, threshold=0.1, confidence=0.99, max_iters=1000):
         """One problem from host arrays [n][2]: returns (F [3][3] float64, mask [n] uint8, status [4] int32)."""
@@ -922,33 +918,17 @@ class FundamentalRansac:
                                                        C.c_void_p(d_F2), C.c_void_p(d_keep), C.c_void_p(d_status)), "amos_fmat_scene_flow_pair_device")
 
 
-class PnpRansac:
+class PnpRansac(_Handle):
     """amos_pnp_*: cv::solvePnPRansac(obj, img, K, 0, ..., SOLVEPNP_P3P) of Tracking::GetSceneFlowObj (Tracking.cc:1006) on the device: the
     RANSAC over P3P samples, then the EPnP refit on its inliers (restated, parity with OpenCV unpinned).  status = (result, inliers,
     iterations, points, refit): result 1 model, 0 none, -1 fewer than 4 points, -2 sampler cap, -3 count out of range; refit 1 EPnP
     refit returned, -1 refit not finite (the RANSAC model returned), 0 none.  Poses are R | t: R row-major, then t."""
 
+    _kind = "pnp"
+
     def __init__(self, max_points=4096, max_problems=64, device=0, stream=None):
-        self.L = lib()
-        self.L.amos_pnp_stream.restype = C.c_void_p
-        self.L.amos_pnp_stream.argtypes = [C.c_void_p]
-        self.L.amos_pnp_destroy.restype = None
-        self.L.amos_pnp_destroy.argtypes = [C.c_void_p]
-        h = C.c_void_p()
-        _check(self.L.amos_pnp_create(C.c_int(device), C.c_void_p(stream), C.c_int(max_points), C.c_int(max_problems), C.byref(h)), "amos_pnp_create")
-        self.h = h
+        self._open(device, stream, max_points, max_problems)
         self.max_points = max_points
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.amos_pnp_destroy(self.h)
-            self.h = None
-
-    __del__ = close
-
-    @property
-    def stream(self):
-        return self.L.amos_pnp_stream(self.h)
 
     def ransac(self, obj, img, fx, fy, cx, cy, reprojection_error=0.4, confidence=0.98, max_iters=500):
         """One problem from host arrays obj [n][3], img [n][2]: returns (Rt [12] float64, mask [n] uint8, status [5] int32)."""
@@ -1006,33 +986,17 @@ class DynaResults(C.Structure):
         "pre_xy", "next_xy", "state", "n", "F1", "F2", "fmat_status", "Rt", "pnp_status")]
 
 
-class SceneFlowDyna:
+class SceneFlowDyna(_Handle):
     """amos_dyna_*: the tail of Tracking::GetSceneFlowObj (Tracking.cc:1012-1184: both poses' reprojection errors, the choice, SetPose,
     mvepipolar / T_M under F2, vFlow_3d) and CalDyna's moving-cluster decision (Frame.cc:552-628) on the device, per result slot."""
 
+    _kind = "dyna"
+
     def __init__(self, max_points=4096, max_frames=64, device=0, stream=None):
-        self.L = lib()
-        self.L.amos_dyna_stream.restype = C.c_void_p
-        self.L.amos_dyna_stream.argtypes = [C.c_void_p]
-        self.L.amos_dyna_destroy.restype = None
-        self.L.amos_dyna_destroy.argtypes = [C.c_void_p]
-        h = C.c_void_p()
-        _check(self.L.amos_dyna_create(C.c_int(device), C.c_void_p(stream), C.c_int(max_points), C.c_int(max_frames), C.byref(h)), "amos_dyna_create")
-        self.h = h
+        self._open(device, stream, max_points, max_frames)
         self.max_points, self.max_frames = max_points, max_frames
         self.results = DynaResults()
         _check(self.L.amos_dyna_results_device(self.h, C.byref(self.results)), "amos_dyna_results_device")
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.amos_dyna_destroy(self.h)
-            self.h = None
-
-    __del__ = close
-
-    @property
-    def stream(self):
-        return self.L.amos_dyna_stream(self.h)
 
     def tail_device(self, frame, d_pre, d_next, d_state, d_n, d_F2, d_fmat_status, d_Rt, d_pnp_status, d_depth_last, last_stride, d_depth_cur,
                     cur_stride, width, height, cam, fx, fy, poses):

@@ -1,4 +1,5 @@
-// amos_common.h -- shared host/device declarations of the MI355X front-end library.
+// amos_common.h -- shared host/device declarations of the MI355X front-end library: error reporting, the stream-owning handle base and
+// the argument rules of the scene-flow entry points, the ORB geometry.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -49,6 +50,42 @@ inline hipError_t set_max_dynamic_lds(DeviceOnce &once, const void *kernel, int 
     e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     if (e == hipSuccess && tracked) once.done[dev >> 6].fetch_or(bit, std::memory_order_release);
     return e;
+}
+
+// The stream-owning part of a scene-flow handle (corners, LK, fmat, pnp, dyna): the caller's stream, or a non-blocking one of the
+// handle's own.  open() makes the device current; close() does too (the frees that follow it need it), then drains the stream.
+struct StreamHandle {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool ownStream = false;
+    int open(int device_, void *stream_)
+    {
+        AMOS_HIP_CHECK(hipSetDevice(device_));
+        device = device_;
+        if (stream_) stream = (hipStream_t)stream_;
+        else {
+            if (hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) != hipSuccess) { set_error("hipStreamCreate failed"); return AMOS_ERR_DEVICE; }
+            ownStream = true;
+        }
+        return AMOS_OK;
+    }
+    void close()
+    {
+        (void)hipSetDevice(device);
+        if (stream) (void)hipStreamSynchronize(stream);
+        if (ownStream && stream) (void)hipStreamDestroy(stream);
+        stream = nullptr;
+    }
+};
+
+// the RANSAC parameters an entry point accepts; a pinhole camera with finite positive focal lengths and a finite principal point
+inline bool ransac_params_ok(double threshold, double confidence, int max_iters)
+{
+    return threshold > 0 && confidence > 0 && confidence < 1 && max_iters >= 1 && max_iters <= (1 << 20);
+}
+inline bool camera_ok(double fx, double fy, double cx, double cy)
+{
+    return fx > 0 && fy > 0 && cx - cx == 0 && cy - cy == 0 && fx - fx == 0 && fy - fy == 0;
 }
 
 constexpr int kEdge = AMOS_EDGE_THRESHOLD;  // 19, ORBextractor.cc:93

@@ -372,10 +372,8 @@ __global__ __launch_bounds__(64 * kSubpixWavesPerGroup) void k_corner_subpix(con
 
 using namespace amos;
 
-struct amos_corners {
-    int device = 0, w = 0, h = 0;
-    hipStream_t stream = nullptr;
-    bool ownStream = false;
+struct amos_corners : StreamHandle {
+    int w = 0, h = 0;
     float *dEig = nullptr, *dMask = nullptr;
     int maskWin = 0;
     void *dWork = nullptr;
@@ -390,14 +388,10 @@ int amos_corners_create(int device, void *stream, int width, int height, amos_co
         set_error("amos_corners_create: invalid argument");
         return AMOS_ERR_INVALID;
     }
-    AMOS_HIP_CHECK(hipSetDevice(device));
     amos_corners *c = new amos_corners();
-    c->device = device; c->w = width; c->h = height;
-    if (stream) c->stream = (hipStream_t)stream;
-    else {
-        if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { set_error("hipStreamCreate failed"); delete c; return AMOS_ERR_DEVICE; }
-        c->ownStream = true;
-    }
+    c->w = width; c->h = height;
+    const int rc = c->open(device, stream);
+    if (rc != AMOS_OK) { delete c; return rc; }
     const size_t cells = (size_t)width * height + 2;  // cells of >= 1 pixel
     size_t off = 0;
     auto carve = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
@@ -418,10 +412,8 @@ int amos_corners_create(int device, void *stream, int width, int height, amos_co
 void amos_corners_destroy(amos_corners *c)
 {
     if (!c) return;
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    c->close();
     for (void *p : {(void *)c->dWork, (void *)c->dEig, (void *)c->dMask}) if (p) (void)hipFree(p);
-    if (c->ownStream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
 

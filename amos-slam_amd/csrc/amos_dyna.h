@@ -1,6 +1,6 @@
 // amos_dyna.h -- the per-point arithmetic of the tail of Tracking::GetSceneFlowObj (src/Tracking.cc:1012-1184): the reprojection
-// error of a match under a 3 x 4 float pose, Frame::SetPose's camera centre, and the scene flow under the chosen pose.  Shared by
-// k_dyna_tail (amos_dyna.hip); restated once more in tests/dyna_restatement.py.  Plain + - * / sqrt in the written order (the library
+// error of a match under a 3 x 4 float pose, Frame::SetPose's camera centre, and the scene flow under the chosen pose (the depth lookup and
+// the epipolar distance are amos_scene_flow.h).  For k_dyna_tail (amos_dyna.hip); restated once more in tests/dyna_restatement.py.  Plain + - * / sqrt in the written order (the library
 // builds with -ffp-contract=off).
 #pragma once
 #include "amos_common.h"
@@ -31,28 +31,14 @@ __device__ __forceinline__ void set_pose(const float *P, float *Rwc, float *Ow)
 }
 
 // :1153-1183: sf_norm of a match whose two depths are positive, cur_3d through (Rwc, Ow) of the chosen pose; the current pixel is
-// scaled by z1, as the reference writes it (k_scene_flow_3d's arithmetic)
+// scaled by z1, as the reference writes it (the pieces k_scene_flow_3d is made of, amos_scene_flow.h)
 __device__ __forceinline__ float sf_norm(const SceneFlowArgs &a, const float *Rwc, const float *Ow, float px, float py, float qx, float qy,
                                          float z1, float z2)
 {
-    float p0, p1, p2;
+    float p0, p1, p2, c0, c1, c2;
     scene_flow_pre3d(a, px, py, z1, p0, p1, p2);
-    const float xc = __fmul_rn(__fmul_rn(__fsub_rn(qx, a.cx), z1), a.invfx);
-    const float yc = __fmul_rn(__fmul_rn(__fsub_rn(qy, a.cy), z1), a.invfy);
-    const float c0 = gemm_row(Rwc, 0, xc, yc, z2, Ow[0]), c2 = gemm_row(Rwc, 2, xc, yc, z2, Ow[2]);
-    const float fx = __fsub_rn(p0, c0), fz = __fsub_rn(p2, c2);
-    return (float)__dsqrt_rn((double)__fadd_rn(__fmul_rn(fx, fx), __fmul_rn(fz, fz)));
-}
-
-// :1141-1152: dd of one tracked point under F (k_epipolar's arithmetic)
-__device__ __forceinline__ double epipolar(const double *F, float px_, float py_, float qx_, float qy_)
-{
-    const double px = px_, py = py_, qx = qx_, qy = qy_;
-    const double A = __dadd_rn(__dadd_rn(__dmul_rn(F[0], px), __dmul_rn(F[1], py)), F[2]);
-    const double B = __dadd_rn(__dadd_rn(__dmul_rn(F[3], px), __dmul_rn(F[4], py)), F[5]);
-    const double C = __dadd_rn(__dadd_rn(__dmul_rn(F[6], px), __dmul_rn(F[7], py)), F[8]);
-    const double num = fabs(__dadd_rn(__dadd_rn(__dmul_rn(A, qx), __dmul_rn(B, qy)), C));
-    return __ddiv_rn(num, __dsqrt_rn(__dadd_rn(__dmul_rn(A, A), __dmul_rn(B, B))));
+    scene_flow_cur3d(a, Rwc, Ow, qx, qy, z1, z2, c0, c1, c2);
+    return scene_flow_norm(p0, p2, c0, c2);
 }
 
 }  // namespace dyna

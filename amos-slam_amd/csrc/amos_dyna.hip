@@ -1,6 +1,7 @@
 // amos_dyna.hip -- the dynamic-object test of Amos-SLAM after the RANSACs: the tail of Tracking::GetSceneFlowObj (src/Tracking.cc:
 // 1012-1184) and the decision of Frame::CalDyna (src/Frame.cc:552-628), so that the chain GetSceneFlowObj -> cluster -> decision ->
-// labelled gate -> describe needs no host synchronisation.  The per-point arithmetic is amos_dyna.h (restated: DESIGN.md section 2).
+// labelled gate -> describe needs no host synchronisation.  The per-point arithmetic is amos_dyna.h and amos_scene_flow.h (restated:
+// DESIGN.md section 2), the compaction and the sums amos_block.h.
 //   k_dyna_tail    ONE WORK-GROUP PER CALL, 256 threads, n <= max_points (<= 4096).  Order-preserving compactions (the N-point lists,
 //                  mvMatch / mvRpe, T_M, vFlow_3d) by a work-group prefix scan (ballot + per-wave counts, no atomics); both poses' errors
 //                  in parallel; the inlier counts by a reduction; the pose choice and SetPose on one lane; then the scene flow under the
@@ -9,6 +10,7 @@
 //                  lane walking the list in order (the reference's sequential float sum: no tree reduction); the distinct T_M
 //                  superpixels through an LDS bitmap over the labels; epNum by integer LDS atomics (order-free); rm, AveClusterRpe, epNum.
 #include "amos_common.h"
+#include "amos_block.h"
 #include "amos_dyna.h"
 
 #include <cstddef>
@@ -21,42 +23,6 @@ constexpr int kDynaMaxCenters = 1 << 16;  // the decide bitmap (8 KB); 12 288 ce
 constexpr int kDynaMaxCorners = 1000;     // goodFeaturesToTrack's maxCorners (Tracking.cc:894)
 constexpr int kRecInts = (int)(sizeof(amos_slic_center) / sizeof(int32_t));
 constexpr int kIdInt = (int)(offsetof(amos_slic_center, id) / sizeof(int32_t));
-
-// calls f(i, c) for i < cnt with c the compact index among the i with sel_of(i) (in order), or -1; returns the count (block-wide)
-template <typename Sel, typename Fn>
-__device__ __forceinline__ int dyna_scan(int cnt, int *sWave, Sel sel_of, Fn f)
-{
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    int total = 0;
-    for (int base = 0; base < cnt; base += kDynaThreads) {
-        const int i = base + t;
-        const bool sel = i < cnt && sel_of(i);
-        const unsigned long long b = __ballot(sel);
-        if (lane == 0) sWave[wv] = (int)__popcll(b);
-        __syncthreads();
-        int before = total, all = total;
-        for (int w = 0; w < kDynaWaves; w++) {
-            if (w < wv) before += sWave[w];
-            all += sWave[w];
-        }
-        if (i < cnt) f(i, sel ? before + (int)__popcll(b & ((1ull << lane) - 1ull)) : -1);
-        __syncthreads();
-        total = all;
-    }
-    return total;
-}
-
-__device__ __forceinline__ int block_sum(int v, int *sWave)
-{
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    if (lane == 0) sWave[wv] = v;
-    __syncthreads();
-    int s = 0;
-    for (int w = 0; w < kDynaWaves; w++) s += sWave[w];
-    __syncthreads();
-    return s;
-}
 
 struct DynaSlot {  // the outputs of one slot
     float *pose, *rwc, *ow;
@@ -112,8 +78,10 @@ __global__ __launch_bounds__(kDynaThreads) void k_dyna_tail(const DynaTailArgs a
         sMotion[t] = a.motion[t];
     }
     // ---- the N-point lists: the tracked points with state != 0, in order
-    const int N = dyna_scan(n, sWave, [&](int i) { return a.state[i] != 0; }, [&](int i, int c) { if (c >= 0) sIdx[c] = (uint16_t)i; });
+    const int N = block_compact<kDynaThreads>(n, sWave, [&](int i) { return a.state[i] != 0; }, [&](int i, int c) { if (c >= 0) sIdx[c] = (uint16_t)i; });
     const int W = a.width, H = a.height;
+    // scene_flow_depths (amos_scene_flow.h) written out: through the shared helper, in every form tried, the compiler schedules this kernel
+    // differently and the tail measured 23.3 us against 22.6 us (profiles/r07_ransac_core.txt); as written here the code is the parent's
     auto depths = [&](float2 P, float2 Q, float &z1, float &z2) {  // truncated coordinates; outside the maps: no depth
         const int x1 = (int)P.x, y1 = (int)P.y, x2 = (int)Q.x, y2 = (int)Q.y;
         const bool in1 = P.x >= 0 && P.y >= 0 && x1 < W && y1 < H, in2 = Q.x >= 0 && Q.y >= 0 && x2 < W && y2 < H;
@@ -122,7 +90,7 @@ __global__ __launch_bounds__(kDynaThreads) void k_dyna_tail(const DynaTailArgs a
     };
     // ---- loops 1 and 2 (:1028-1110): the entries with pre_3d.z > 0 && cur_2d.x != 0 && cur_2d.y != 0, errors under both poses
     int inP = 0, inM = 0;
-    const int V = dyna_scan(N, sWave,
+    const int V = block_compact<kDynaThreads>(N, sWave,
         [&](int j) {
             const int i = sIdx[j];
             const float2 P = a.pre[i], Q = a.next[i];
@@ -149,7 +117,7 @@ __global__ __launch_bounds__(kDynaThreads) void k_dyna_tail(const DynaTailArgs a
             inP += (double)eP <= 0.4 ? 1 : 0;  // Rpe <= reprojectionError
             inM += (double)eM <= 0.4 ? 1 : 0;
         });
-    const int nP = block_sum(inP, sWave), nM = block_sum(inM, sWave);
+    const int nP = block_sum<kDynaThreads>(inP, sWave), nM = block_sum<kDynaThreads>(inM, sWave);
     // ---- the choice (:1112-1123) and SetPose
     if (t == 0) {
         const int choice = nP >= nM ? 1 : 0;
@@ -166,15 +134,15 @@ __global__ __launch_bounds__(kDynaThreads) void k_dyna_tail(const DynaTailArgs a
     // ---- mvepipolar and T_M under F2 (:1129-1145)
     double F[9];
     for (int k = 0; k < 9; k++) F[k] = a.F2[k];
-    const int T = dyna_scan(n, sWave,
+    const int T = block_compact<kDynaThreads>(n, sWave,
         [&](int i) {
             if (a.state[i] == 0) return false;
             const float2 P = a.pre[i], Q = a.next[i];
-            return !(dyna::epipolar(F, P.x, P.y, Q.x, Q.y) <= 1.0);
+            return !(epipolar_distance(F, P.x, P.y, Q.x, Q.y) <= 1.0);
         },
         [&](int i, int c) {
             const float2 P = a.pre[i], Q = a.next[i];
-            o.epi[i] = a.state[i] != 0 ? dyna::epipolar(F, P.x, P.y, Q.x, Q.y) : 0.0;
+            o.epi[i] = a.state[i] != 0 ? epipolar_distance(F, P.x, P.y, Q.x, Q.y) : 0.0;
             if (c >= 0) o.tm[c] = Q;
         });
     // ---- vFlow_3d under the chosen pose (:1148-1183)
@@ -190,7 +158,7 @@ __global__ __launch_bounds__(kDynaThreads) void k_dyna_tail(const DynaTailArgs a
         sf = dyna::sf_norm(a.sa, Rwc, Ow, P.x, P.y, Q.x, Q.y, z1, z2);
         return sf > 3.f;
     };
-    const int Fl = dyna_scan(N, sWave, [&](int j) { float sf; return flow_of(j, sf); },
+    const int Fl = block_compact<kDynaThreads>(N, sWave, [&](int j) { float sf; return flow_of(j, sf); },
         [&](int j, int c) {
             if (c < 0) return;
             float sf;
@@ -311,10 +279,8 @@ __global__ __launch_bounds__(kDynaThreads) void k_dyna_decide(const DynaDecideAr
 
 using namespace amos;
 
-struct amos_dyna {
-    int device = 0, maxPoints = 0, maxFrames = 0;
-    hipStream_t stream = nullptr;
-    bool ownStream = false;
+struct amos_dyna : StreamHandle {
+    int maxPoints = 0, maxFrames = 0;
     void *mem = nullptr;
     amos_dyna_results r{};
     uint8_t *lkStatus = nullptr, *keep = nullptr;
@@ -336,11 +302,6 @@ static DynaSlot dyna_slot(const amos_dyna *h, int f)
     return o;
 }
 
-static bool dyna_camera_ok(const amos_scene_flow_camera *cam, double fx, double fy)
-{
-    return cam && fx > 0 && fy > 0 && cam->cx - cam->cx == 0 && cam->cy - cam->cy == 0;
-}
-
 extern "C" {
 
 int amos_dyna_create(int device, void *stream, int max_points, int max_frames, amos_dyna **out)
@@ -350,14 +311,10 @@ int amos_dyna_create(int device, void *stream, int max_points, int max_frames, a
         return AMOS_ERR_INVALID;
     }
     *out = nullptr;
-    AMOS_HIP_CHECK(hipSetDevice(device));
     amos_dyna *h = new amos_dyna();
-    h->device = device; h->maxPoints = max_points; h->maxFrames = max_frames;
-    if (stream) h->stream = (hipStream_t)stream;
-    else {
-        if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { set_error("hipStreamCreate failed"); delete h; return AMOS_ERR_DEVICE; }
-        h->ownStream = true;
-    }
+    h->maxPoints = max_points; h->maxFrames = max_frames;
+    const int rc = h->open(device, stream);
+    if (rc != AMOS_OK) { delete h; return rc; }
     // one allocation, every array 256-byte aligned
     const size_t P = (size_t)max_points, Fr = (size_t)max_frames;
     size_t off = 0;
@@ -393,10 +350,8 @@ int amos_dyna_create(int device, void *stream, int max_points, int max_frames, a
 void amos_dyna_destroy(amos_dyna *h)
 {
     if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    h->close();
     if (h->mem) (void)hipFree(h->mem);
-    if (h->ownStream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
 
@@ -426,7 +381,7 @@ int amos_dyna_tail_device(amos_dyna *h, int frame, const float *d_pre_xy, const 
 {
     if (!h || frame < 0 || frame >= h->maxFrames || !d_pre_xy || !d_next_xy || !d_state || !d_n || !d_F2 || !d_fmat_status || !d_Rt || !d_pnp_status ||
         !d_depth_last || !d_depth_cur || width < 1 || height < 1 || last_stride < (size_t)width || cur_stride < (size_t)width || !poses ||
-        !dyna_camera_ok(cam, fx, fy)) {
+        !cam || !camera_ok(fx, fy, cam->cx, cam->cy)) {
         set_error("amos_dyna_tail_device: invalid argument");
         return AMOS_ERR_INVALID;
     }
@@ -489,7 +444,7 @@ int amos_dyna_scene_flow_obj_device(amos_dyna *h, int frame, amos_corners *corne
 {
     if (!h || frame < 0 || frame >= h->maxFrames || !corners || !lk || !fmat || !pnp || !d_imlast_gray || !d_gray || !d_depth_last || !d_depth_cur ||
         width < 1 || height < 1 || last_gray_stride < (size_t)width || gray_stride < (size_t)width || last_stride < (size_t)width ||
-        cur_stride < (size_t)width || !poses || !dyna_camera_ok(cam, fx, fy)) {
+        cur_stride < (size_t)width || !poses || !cam || !camera_ok(fx, fy, cam->cx, cam->cy)) {
         set_error("amos_dyna_scene_flow_obj_device: invalid argument");
         return AMOS_ERR_INVALID;
     }

@@ -8,6 +8,7 @@
 // goodFeaturesToTrack, cornerSubPix, calcOpticalFlowPyrLK, findFundamentalMat and solvePnPRansac are OpenCV calls; their device forms
 // are amos_corners.hip, the LK tracker below, amos_fmat.hip and amos_pnp.hip -- DESIGN.md section 7.
 #include "amos_common.h"
+#include "amos_block.h"
 #include "amos_pnp_core.h"
 #include "amos_scene_flow.h"
 
@@ -48,13 +49,7 @@ __global__ __launch_bounds__(256) void k_epipolar(const double *__restrict__ F, 
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     if (state && state[i] == 0) { dd[i] = -1.0; return; }
-    const double px = pre[i].x, py = pre[i].y, qx = next[i].x, qy = next[i].y;
-    // A = F00 * x + F01 * y + F02 evaluated left to right, no fused multiply-add
-    const double A = __dadd_rn(__dadd_rn(__dmul_rn(F[0], px), __dmul_rn(F[1], py)), F[2]);
-    const double B = __dadd_rn(__dadd_rn(__dmul_rn(F[3], px), __dmul_rn(F[4], py)), F[5]);
-    const double C = __dadd_rn(__dadd_rn(__dmul_rn(F[6], px), __dmul_rn(F[7], py)), F[8]);
-    const double num = fabs(__dadd_rn(__dadd_rn(__dmul_rn(A, qx), __dmul_rn(B, qy)), C));
-    dd[i] = __ddiv_rn(num, __dsqrt_rn(__dadd_rn(__dmul_rn(A, A), __dmul_rn(B, B))));
+    dd[i] = epipolar_distance(F, pre[i].x, pre[i].y, next[i].x, next[i].y);
 }
 
 // ---- hypothesis scoring for the RANSACs of GetSceneFlowObj (Tracking.cc:927, 945: cv::findFundamentalMat(..., FM_RANSAC, 0.1, 0.99);
@@ -66,7 +61,7 @@ __global__ __launch_bounds__(256) void k_epipolar(const double *__restrict__ F, 
 // Fundamental matrix: OpenCV 4.5's FMEstimatorCallback::computeError (modules/calib3d/src/fundam.cpp) restated: in doubles, left to right,
 //   a = F0 x1 + F1 y1 + F2, b = F3 x1 + F4 y1 + F5, c = F6 x1 + F7 y1 + F8;  s2 = 1 / (a a + b b);  d2 = x2 a + y2 b + c;
 //   a = F0 x2 + F3 y2 + F6, b = F1 x2 + F4 y2 + F7, c = F2 x2 + F5 y2 + F8;  s1 = 1 / (a a + b b);  d1 = x1 a + y1 b + c;
-//   err = (float) max(d1 d1 s1, d2 d2 s2);  inlier <=> err <= (float)(threshold * threshold)   (RANSACPointSetRegistrator::findInliers).
+//   err = (float) std::max(d1 d1 s1, d2 d2 s2) (fm::point_error);  inlier <=> err <= (float)(threshold * threshold)   (RANSACPointSetRegistrator::findInliers).
 // OpenCV-derived, hence parity unpinned like the other OpenCV stages; the GPU tests hold it to the numpy restatement bit for bit.
 __global__ __launch_bounds__(256) void k_fundamental_score(const double *__restrict__ Fs, const FlowPoint *__restrict__ p1, const FlowPoint *__restrict__ p2, int n,
                                                           float thresh2, float *__restrict__ err, int *__restrict__ inliers, uint8_t *__restrict__ mask)
@@ -74,31 +69,21 @@ __global__ __launch_bounds__(256) void k_fundamental_score(const double *__restr
     __shared__ int sCount[4];
     const int h = blockIdx.x, t = threadIdx.x;
     const double *F = Fs + (size_t)h * 9;
-    const double F0 = F[0], F1 = F[1], F2 = F[2], F3 = F[3], F4 = F[4], F5 = F[5], F6 = F[6], F7 = F[7], F8 = F[8];
+    double Fh[9];
+#pragma unroll
+    for (int k = 0; k < 9; k++) Fh[k] = F[k];
     int count = 0;
     for (int i = t; i < n; i += 256) {
-        const double x1 = p1[i].x, y1 = p1[i].y, x2 = p2[i].x, y2 = p2[i].y;
-        double a = __dadd_rn(__dadd_rn(__dmul_rn(F0, x1), __dmul_rn(F1, y1)), F2);
-        double b = __dadd_rn(__dadd_rn(__dmul_rn(F3, x1), __dmul_rn(F4, y1)), F5);
-        double c = __dadd_rn(__dadd_rn(__dmul_rn(F6, x1), __dmul_rn(F7, y1)), F8);
-        const double s2 = __ddiv_rn(1.0, __dadd_rn(__dmul_rn(a, a), __dmul_rn(b, b)));
-        const double d2 = __dadd_rn(__dadd_rn(__dmul_rn(x2, a), __dmul_rn(y2, b)), c);
-        a = __dadd_rn(__dadd_rn(__dmul_rn(F0, x2), __dmul_rn(F3, y2)), F6);
-        b = __dadd_rn(__dadd_rn(__dmul_rn(F1, x2), __dmul_rn(F4, y2)), F7);
-        c = __dadd_rn(__dadd_rn(__dmul_rn(F2, x2), __dmul_rn(F5, y2)), F8);
-        const double s1 = __ddiv_rn(1.0, __dadd_rn(__dmul_rn(a, a), __dmul_rn(b, b)));
-        const double d1 = __dadd_rn(__dadd_rn(__dmul_rn(x1, a), __dmul_rn(y1, b)), c);
-        const double e1 = __dmul_rn(__dmul_rn(d1, d1), s1), e2 = __dmul_rn(__dmul_rn(d2, d2), s2);
-        const float e = (float)(e1 > e2 ? e1 : (e2 > e1 ? e2 : (e1 != e1 ? e2 : e1)));  // std::max(a, b) = (a < b) ? b : a
+        // std::max's rule (a NaN first term stays) is a compare and a select where a NaN-skipping maximum is one instruction: 62 SGPRs
+        // against 56 before, the same allocation granule and occupancy (profiles/r07_ransac_core.txt)
+        const float e = fm::point_error(Fh, p1[i].x, p1[i].y, p2[i].x, p2[i].y);
         const bool in = e <= thresh2;
         if (err) err[(size_t)h * n + i] = e;
         if (mask) mask[(size_t)h * n + i] = in ? 1 : 0;
         count += in ? 1 : 0;
     }
-    for (int d = 32; d > 0; d >>= 1) count += __shfl_xor(count, d, 64);
-    if ((t & 63) == 0) sCount[t >> 6] = count;
-    __syncthreads();
-    if (t == 0) inliers[h] = sCount[0] + sCount[1] + sCount[2] + sCount[3];
+    count = block_sum<256>(count, sCount);
+    if (t == 0) inliers[h] = count;
 }
 
 // Pose hypotheses (R | t): OpenCV's PnPRansacCallback::computeError restated for zero distortion: the object point goes through
@@ -123,10 +108,8 @@ __global__ __launch_bounds__(256) void k_pnp_score(const double *__restrict__ Rt
         if (mask) mask[(size_t)h * n + i] = in ? 1 : 0;
         count += in ? 1 : 0;
     }
-    for (int d = 32; d > 0; d >>= 1) count += __shfl_xor(count, d, 64);
-    if ((t & 63) == 0) sCount[t >> 6] = count;
-    __syncthreads();
-    if (t == 0) inliers[h] = sCount[0] + sCount[1] + sCount[2] + sCount[3];
+    count = block_sum<256>(count, sCount);
+    if (t == 0) inliers[h] = count;
 }
 
 // out per match: pre_3d (3), cur_3d (3), sf_norm, valid (z1 > 0 && z2 > 0)
@@ -146,15 +129,10 @@ __global__ __launch_bounds__(256) void k_scene_flow_3d(const float *__restrict__
     }
     float p0, p1, p2;  // :960-973
     scene_flow_pre3d(a, matchPre[i].x, matchPre[i].y, z1, p0, p1, p2);
-    // :1160-1164 (the reference scales the CURRENT pixel by z1 and stacks z2: restated as written)
-    const float xc = __fmul_rn(__fmul_rn(__fsub_rn(matchCur[i].x, a.cx), z1), a.invfx);
-    const float yc = __fmul_rn(__fmul_rn(__fsub_rn(matchCur[i].y, a.cy), z1), a.invfy);
-    const float c0 = gemm_row(a.Rwc, 0, xc, yc, z2, a.Ow[0]), c1 = gemm_row(a.Rwc, 1, xc, yc, z2, a.Ow[1]), c2 = gemm_row(a.Rwc, 2, xc, yc, z2, a.Ow[2]);
-    const float fx = __fsub_rn(p0, c0), fz = __fsub_rn(p2, c2);
+    float c0, c1, c2;
+    scene_flow_cur3d(a, a.Rwc, a.Ow, matchCur[i].x, matchCur[i].y, z1, z2, c0, c1, c2);
     o[0] = p0; o[1] = p1; o[2] = p2; o[3] = c0; o[4] = c1; o[5] = c2;
-    // sf_norm uses x and z only (:1176).  std::sqrt(float) is correctly rounded; the device's single-precision square root is
-    // not, the double one is, and rounding a double square root of a float to float is exact (53 >= 2 * 24 + 2 bits)
-    o[6] = (float)__dsqrt_rn((double)__fadd_rn(__fmul_rn(fx, fx), __fmul_rn(fz, fz)));
+    o[6] = scene_flow_norm(p0, p2, c0, c2);
     o[7] = 1.f;
 }
 
@@ -433,10 +411,8 @@ int amos_flow_scene_flow_device(void *stream, const float *d_depth_last, size_t 
 }
 
 
-struct amos_lk {
-    int device = 0, w = 0, h = 0, win = 22, maxLevel = 5, top = 0, maxPoints = 0;
-    hipStream_t stream = nullptr;
-    bool ownStream = false;
+struct amos_lk : StreamHandle {
+    int w = 0, h = 0, win = 22, maxLevel = 5, top = 0, maxPoints = 0;
     LkArgs args{};
     uint8_t *dPrev = nullptr, *dNext = nullptr;
     short *dDeriv = nullptr;
@@ -449,14 +425,10 @@ int amos_lk_create(int device, void *stream, int width, int height, int win_size
         set_error("amos_lk_create: invalid argument (3 <= win_size <= %d, frame larger than the window)", kLkMaxWin);
         return AMOS_ERR_INVALID;
     }
-    AMOS_HIP_CHECK(hipSetDevice(device));
     amos_lk *k = new amos_lk();
-    k->device = device; k->w = width; k->h = height; k->win = win_size; k->maxLevel = max_level;
-    if (stream) k->stream = (hipStream_t)stream;
-    else {
-        if (hipStreamCreateWithFlags(&k->stream, hipStreamNonBlocking) != hipSuccess) { set_error("hipStreamCreate failed"); delete k; return AMOS_ERR_DEVICE; }
-        k->ownStream = true;
-    }
+    k->w = width; k->h = height; k->win = win_size; k->maxLevel = max_level;
+    const int rc = k->open(device, stream);
+    if (rc != AMOS_OK) { delete k; return rc; }
     size_t off = 0;
     int w = width, h = height, level = 0;
     for (;; level++) {  // buildOpticalFlowPyramid's level count
@@ -485,10 +457,8 @@ int amos_lk_create(int device, void *stream, int width, int height, int win_size
 void amos_lk_destroy(amos_lk *k)
 {
     if (!k) return;
-    (void)hipSetDevice(k->device);
-    if (k->stream) (void)hipStreamSynchronize(k->stream);
+    k->close();
     for (void *p : {(void *)k->dPrev, (void *)k->dNext, (void *)k->dDeriv}) if (p) (void)hipFree(p);
-    if (k->ownStream && k->stream) (void)hipStreamDestroy(k->stream);
     delete k;
 }
 

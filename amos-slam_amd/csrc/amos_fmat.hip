@@ -1,14 +1,17 @@
 // amos_fmat.hip -- cv::findFundamentalMat(p1, p2, FM_RANSAC, 0.1, 0.99) of Tracking::GetSceneFlowObj (src/Tracking.cc:927, 945) on the
 // device: the whole RANSAC (sampler, 7-point solver, scoring, best-model rule, iteration-count update) for n >= 15 correspondences.
-// The arithmetic is amos_fmat_core.h (restated; parity with OpenCV unpinned).
+// The arithmetic is amos_fmat_core.h (restated; parity with OpenCV unpinned); the round's draw, scorer and sequential
+// replay are amos_ransac.h (shared with amos_pnp.hip), the compaction amos_block.h.
 //   k_fmat_ransac   ONE WORK-GROUP PER PROBLEM (a batch of problems is one launch).  The selected points go to LDS (16 B each), then
 //                   rounds of up to 64 iterations: wave 0 runs the serial RNG (every lane the same state, collinearity pairs over the
 //                   lanes) and draws the next subsets; one lane per subset solves run7Point; all waves score the up to 192 models over all
 //                   points (counts by wave reduction, no atomics); one lane replays the sequential loop in iteration order (best model,
 //                   niters).  The RNG consumption depends only on the points, never on the scores, so drawing ahead changes nothing.
-//   k_fmat_keep     Tracking.cc:928-944: keep = state != 0 && dd <= 0.5 under the first F (k_epipolar's arithmetic)
+//   k_fmat_keep     Tracking.cc:928-944: keep = state != 0 && dd <= 0.5 under the first F (epipolar_distance, amos_scene_flow.h)
 #include "amos_common.h"
 #include "amos_fmat_core.h"
+#include "amos_ransac.h"
+#include "amos_scene_flow.h"
 
 namespace amos {
 
@@ -28,30 +31,6 @@ struct FmatArgs {
     uint8_t *mask;
 };
 
-// the selected points of a problem in input order: calls f(input index i, compact index c or -1) for i < cnt (block-wide, in order)
-template <typename Fn>
-__device__ __forceinline__ int fmat_scan(const uint8_t *select, int off, int cnt, int *sWave, Fn f)
-{
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    int total = 0;
-    for (int base = 0; base < cnt; base += kFmatThreads) {
-        const int i = base + t;
-        const bool sel = i < cnt && (!select || select[off + i] != 0);
-        const unsigned long long b = __ballot(sel);
-        if (lane == 0) sWave[wv] = (int)__popcll(b);
-        __syncthreads();
-        int before = total, all = total;
-        for (int w = 0; w < kFmatWaves; w++) {
-            if (w < wv) before += sWave[w];
-            all += sWave[w];
-        }
-        if (i < cnt) f(i, sel ? before + (int)__popcll(b & ((1ull << lane) - 1ull)) : -1);
-        __syncthreads();
-        total = all;
-    }
-    return total;
-}
-
 __global__ __launch_bounds__(kFmatThreads) void k_fmat_ransac(const FmatArgs a)
 {
     __shared__ float4 sPts[kFmatMaxPoints];                 // (x1, y1, x2, y2) of the selected points
@@ -59,50 +38,41 @@ __global__ __launch_bounds__(kFmatThreads) void k_fmat_ransac(const FmatArgs a)
     __shared__ int sCount[kFmatRound * 3], sNModels[kFmatRound], sSub[kFmatRound][7];
     __shared__ double sBest[9];
     __shared__ int sWave[kFmatWaves];
-    __shared__ int sDrawn, sStop, sResult, sIter, sNiters, sMaxGood;
+    __shared__ ransac::State sR;
     const int p = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
     const int off = a.offsets ? a.offsets[p] : p * a.maxPoints, cnt = a.counts[p];
     double *Fout = a.F + (size_t)p * 9;
     int *st = a.status + (size_t)p * 4;
+    uint8_t *mask = a.mask ? a.mask + off : nullptr;
     if (cnt < 0 || cnt > a.maxPoints) {  // out of range: nothing is read, no mask written
-        if (t < 9) Fout[t] = 0.0;
-        if (t == 0) { st[0] = -3; st[1] = 0; st[2] = 0; st[3] = 0; }
+        ransac::no_model<kFmatThreads, 9, 4>(Fout, st, -3, 0, 0, nullptr, 0);
         return;
     }
-    const int n = fmat_scan(a.select, off, cnt, sWave, [&](int i, int c) {
+    auto selected = [&](int i) { return !a.select || a.select[off + i] != 0; };
+    const int n = block_compact<kFmatThreads>(cnt, sWave, selected, [&](int i, int c) {
         if (c >= 0) sPts[c] = make_float4(a.p1[off + i].x, a.p1[off + i].y, a.p2[off + i].x, a.p2[off + i].y);
     });
-    if (t == 0) { sStop = 0; sResult = 0; sIter = 0; sNiters = a.maxIters; sMaxGood = 0; }
+    ransac::begin(sR, a.maxIters);
     if (n < 15) {  // n < 7: no model; 7 <= n < 15: OpenCV's LMeDS / 7-point branches (not built here)
-        if (t < 9) Fout[t] = 0.0;
-        if (t == 0) { st[0] = n < 7 ? 0 : -1; st[1] = 0; st[2] = 0; st[3] = n; }
-        if (a.mask) for (int i = t; i < cnt; i += kFmatThreads) a.mask[off + i] = 0;
+        ransac::no_model<kFmatThreads, 9, 4>(Fout, st, n < 7 ? 0 : -1, 0, n, mask, cnt);
         return;
     }
     __syncthreads();
+    auto error_of = [&](const double *F, int i) {
+        const float4 P = sPts[i];
+        return fm::point_error(F, P.x, P.y, P.z, P.w);
+    };
     uint64_t rng = ~0ull;  // cv::RNG rng((uint64)-1), wave 0's lanes hold identical copies
     for (;;) {
-        const int iter0 = sIter, limit = min(kFmatRound, sNiters - iter0);
-        // ---- draw the subsets of iterations iter0 .. iter0 + limit - 1 (getSubset, maxAttempts 10000)
+        const int limit = min(kFmatRound, sR.niters - sR.iter);
+        // ---- draw the subsets of iterations iter .. iter + limit - 1 (getSubset, maxAttempts 10000)
         if (wv == 0) {
             int drawn = 0, stop = 0;
             for (int slot = 0; slot < limit; slot++) {
                 int idx[7];
                 bool found = false, cap = false;
                 for (int attempt = 0; attempt < fm::kMaxAttempts && !found && !cap; attempt++) {
-#pragma unroll
-                    for (int i = 0; i < 7; i++) {
-                        for (uint32_t draws = 1;; draws++) {
-                            const int v = (int)(fm::rng_next(rng) % (uint32_t)n);
-                            bool dup = false;
-#pragma unroll
-                            for (int j = 0; j < i; j++) dup |= v == idx[j];
-                            idx[i] = v;
-                            if (!dup) break;
-                            if (draws >= fm::kRedrawCap) { cap = true; break; }
-                        }
-                        if (cap) break;
-                    }
+                    cap = !ransac::draw_distinct<7>(rng, n, idx);
                     if (cap) break;
                     bool col = false;  // FMEstimatorCallback::checkSubset: lanes 0..14 set 1, 15..29 set 2
                     if (lane < 30) {
@@ -125,10 +95,10 @@ __global__ __launch_bounds__(kFmatThreads) void k_fmat_ransac(const FmatArgs a)
                 }
                 drawn++;
             }
-            if (lane == 0) { sDrawn = drawn; sStop = stop; }
+            if (lane == 0) { sR.drawn = drawn; sR.stop = stop; }
         }
         __syncthreads();
-        const int drawn = sDrawn;
+        const int drawn = sR.drawn;
         // ---- run7Point, one lane per subset
         if (t < drawn) {
             float x0[7], y0[7], x1[7], y1[7];
@@ -145,64 +115,22 @@ __global__ __launch_bounds__(kFmatThreads) void k_fmat_ransac(const FmatArgs a)
                 for (int k = 0; k < 9; k++) sModel[3 * t + m][k] = F[9 * m + k];
         }
         __syncthreads();
-        // ---- scoring: model m = 3 * slot + root on wave m % kFmatWaves, points over the lanes
-        for (int m = wv; m < 3 * drawn; m += kFmatWaves) {
-            if (m % 3 >= sNModels[m / 3]) continue;  // wave-uniform
-            double F[9];
-#pragma unroll
-            for (int k = 0; k < 9; k++) F[k] = sModel[m][k];
-            int count = 0;
-            for (int i = lane; i < n; i += 64) {
-                const float4 P = sPts[i];
-                count += fm::point_error(F, P.x, P.y, P.z, P.w) <= a.thresh2 ? 1 : 0;
-            }
-            for (int d = 32; d > 0; d >>= 1) count += __shfl_xor(count, d, 64);
-            if (lane == 0) sCount[m] = count;
-        }
+        // ---- scoring: model m = 3 * slot + root
+        ransac::score_models<kFmatThreads>(sModel, 3 * drawn, n, a.thresh2, sCount, [&](int m) { return m % 3 < sNModels[m / 3]; }, error_of);
         __syncthreads();
-        // ---- the sequential loop of RANSACPointSetRegistrator::run over this round's iterations
-        if (t == 0) {
-            int iter = iter0, niters = sNiters, maxGood = sMaxGood, stop = 0;
-            for (int slot = 0;; slot++) {
-                if (iter >= niters) break;
-                if (slot == drawn) {  // the sampler stopped here (or the round is used up)
-                    if (sStop == 2) { sResult = -2; stop = 1; }
-                    else if (sStop == 1) { stop = 1; if (iter == 0) maxGood = 0; }
-                    break;
-                }
-                for (int m = 0; m < sNModels[slot]; m++) {
-                    const int good = sCount[3 * slot + m];
-                    if (good > max(maxGood, fm::kModelPoints - 1)) {
-                        for (int k = 0; k < 9; k++) sBest[k] = sModel[3 * slot + m][k];
-                        maxGood = good;
-                        niters = fm::update_num_iters(a.confidence, fm::dvd((double)(n - good), (double)n), niters);
-                    }
-                }
-                iter++;
-            }
-            sIter = iter; sNiters = niters; sMaxGood = maxGood;
-            if (iter >= niters) stop = 1;
-            sStop = stop ? 3 : 0;
-        }
+        if (t == 0) ransac::replay_round<9, 3, fm::kModelPoints>(sR, n, a.confidence, sModel, sNModels, sCount, sBest);
         __syncthreads();
-        if (sStop == 3) break;
+        if (sR.stop == 3) break;
     }
     // ---- result, F, mask of the best model
-    const int result = sResult == -2 ? -2 : (sMaxGood > 0 ? 1 : 0), maxGood = result == 1 ? sMaxGood : 0;
+    const int result = ransac::result_of(sR), maxGood = result == 1 ? sR.maxGood : 0;
     if (t < 9) Fout[t] = result == 1 ? sBest[t] : 0.0;
-    if (t == 0) { st[0] = result; st[1] = maxGood; st[2] = sIter; st[3] = n; }
-    if (a.mask) {
+    if (t == 0) { st[0] = result; st[1] = maxGood; st[2] = sR.iter; st[3] = n; }
+    if (mask) {
         double F[9];
 #pragma unroll
         for (int k = 0; k < 9; k++) F[k] = sBest[k];
-        fmat_scan(a.select, off, cnt, sWave, [&](int i, int c) {
-            uint8_t v = 0;
-            if (c >= 0 && result == 1) {
-                const float4 P = sPts[c];
-                v = fm::point_error(F, P.x, P.y, P.z, P.w) <= a.thresh2 ? 1 : 0;
-            }
-            a.mask[off + i] = v;
-        });
+        block_compact<kFmatThreads>(cnt, sWave, selected, [&](int i, int c) { mask[i] = c >= 0 && result == 1 && error_of(F, c) <= a.thresh2 ? 1 : 0; });
     }
 }
 
@@ -215,12 +143,7 @@ __global__ __launch_bounds__(256) void k_fmat_keep(const float2 *__restrict__ pr
     if (n < 0 || n > maxPoints || i >= n) return;
     uint8_t k = 0;
     if (status1[0] == 1 && state[i] != 0) {
-        const double px = pre[i].x, py = pre[i].y, qx = next[i].x, qy = next[i].y;
-        const double A = __dadd_rn(__dadd_rn(__dmul_rn(F[0], px), __dmul_rn(F[1], py)), F[2]);
-        const double B = __dadd_rn(__dadd_rn(__dmul_rn(F[3], px), __dmul_rn(F[4], py)), F[5]);
-        const double C = __dadd_rn(__dadd_rn(__dmul_rn(F[6], px), __dmul_rn(F[7], py)), F[8]);
-        const double num = fabs(__dadd_rn(__dadd_rn(__dmul_rn(A, qx), __dmul_rn(B, qy)), C));
-        k = __ddiv_rn(num, __dsqrt_rn(__dadd_rn(__dmul_rn(A, A), __dmul_rn(B, B)))) <= 0.5 ? 1 : 0;
+        k = epipolar_distance(F, pre[i].x, pre[i].y, next[i].x, next[i].y) <= 0.5 ? 1 : 0;
     }
     keep[i] = k;
 }
@@ -229,20 +152,13 @@ __global__ __launch_bounds__(256) void k_fmat_keep(const float2 *__restrict__ pr
 
 using namespace amos;
 
-struct amos_fmat {
-    int device = 0, maxPoints = 0, maxProblems = 0;
-    hipStream_t stream = nullptr;
-    bool ownStream = false;
+struct amos_fmat : StreamHandle {
+    int maxPoints = 0, maxProblems = 0;
     float2 *dP1 = nullptr, *dP2 = nullptr;
     int *dInt = nullptr;  // [0] zero offset, [1] count of the synchronous call, [2..5] its status
     double *dF = nullptr;
     uint8_t *dMask = nullptr;
 };
-
-static bool fmat_params_ok(double threshold, double confidence, int max_iters)
-{
-    return threshold > 0 && confidence > 0 && confidence < 1 && max_iters >= 1 && max_iters <= (1 << 20);
-}
 
 static int fmat_launch(amos_fmat *h, int n_problems, const float *d_p1, const float *d_p2, const int *d_offsets, const int *d_counts, const uint8_t *d_select,
                        double threshold, double confidence, int max_iters, double *d_F, int *d_status, uint8_t *d_mask)
@@ -268,14 +184,10 @@ int amos_fmat_create(int device, void *stream, int max_points, int max_problems,
         return AMOS_ERR_INVALID;
     }
     *out = nullptr;
-    AMOS_HIP_CHECK(hipSetDevice(device));
     amos_fmat *h = new amos_fmat();
-    h->device = device; h->maxPoints = max_points; h->maxProblems = max_problems;
-    if (stream) h->stream = (hipStream_t)stream;
-    else {
-        if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { set_error("hipStreamCreate failed"); delete h; return AMOS_ERR_DEVICE; }
-        h->ownStream = true;
-    }
+    h->maxPoints = max_points; h->maxProblems = max_problems;
+    const int rc = h->open(device, stream);
+    if (rc != AMOS_OK) { delete h; return rc; }
     hipError_t e = hipMalloc((void **)&h->dP1, sizeof(float2) * max_points);
     if (e == hipSuccess) e = hipMalloc((void **)&h->dP2, sizeof(float2) * max_points);
     if (e == hipSuccess) e = hipMalloc((void **)&h->dInt, sizeof(int) * 8);
@@ -291,10 +203,8 @@ int amos_fmat_create(int device, void *stream, int max_points, int max_problems,
 void amos_fmat_destroy(amos_fmat *h)
 {
     if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    h->close();
     for (void *q : {(void *)h->dP1, (void *)h->dP2, (void *)h->dInt, (void *)h->dF, (void *)h->dMask}) if (q) (void)hipFree(q);
-    if (h->ownStream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
 
@@ -304,7 +214,7 @@ int amos_fmat_ransac_device(amos_fmat *h, int n_problems, const float *d_p1_xy, 
                             const uint8_t *d_select, double threshold, double confidence, int max_iters, double *d_F, int32_t *d_status, uint8_t *d_mask)
 {
     if (!h || n_problems < 0 || n_problems > h->maxProblems || !d_p1_xy || !d_p2_xy || !d_counts || !d_F || !d_status ||
-        !fmat_params_ok(threshold, confidence, max_iters)) {
+        !ransac_params_ok(threshold, confidence, max_iters)) {
         set_error("amos_fmat_ransac_device: invalid argument");
         return AMOS_ERR_INVALID;
     }
@@ -332,7 +242,7 @@ int amos_fmat_scene_flow_pair_device(amos_fmat *h, const float *d_pre_xy, const 
 int amos_fmat_ransac(amos_fmat *h, int n, const float *p1_xy, const float *p2_xy, double threshold, double confidence, int max_iters, double *F,
                      uint8_t *mask, int32_t *status)
 {
-    if (!h || n < 0 || n > h->maxPoints || (n > 0 && (!p1_xy || !p2_xy)) || !F || !status || !fmat_params_ok(threshold, confidence, max_iters)) {
+    if (!h || n < 0 || n > h->maxPoints || (n > 0 && (!p1_xy || !p2_xy)) || !F || !status || !ransac_params_ok(threshold, confidence, max_iters)) {
         set_error("amos_fmat_ransac: invalid argument (n <= max_points)");
         return AMOS_ERR_INVALID;
     }

@@ -1,6 +1,7 @@
 // amos_pnp.hip -- cv::solvePnPRansac(pre_3d, cur_2d, K, 0, rvec, tvec, false, 500, 0.4, 0.98, inliers, SOLVEPNP_P3P) of
 // Tracking::GetSceneFlowObj (src/Tracking.cc:1006) on the device: the RANSAC over P3P samples and the EPnP refit on its inliers.
-// The arithmetic is amos_pnp_core.h (restated; parity with OpenCV unpinned).
+// The arithmetic is amos_pnp_core.h (restated; parity with OpenCV unpinned); the round's draw, scorer and sequential
+// replay are amos_ransac.h (shared with amos_fmat.hip), the compaction amos_block.h.
 //   k_pnp_ransac   ONE WORK-GROUP PER PROBLEM (a batch of problems is one launch).  The selected points go to LDS (20 B each), then
 //                  rounds of up to 64 iterations: lane 0 runs the serial RNG and draws the subsets (PnPRansacCallback has no
 //                  checkSubset, so every draw of 4 distinct indices is a subset); one lane per subset runs P3P; all waves score the up to
@@ -12,6 +13,7 @@
 //   k_pnp_points   Tracking.cc:955-990: the N-point lists of the reference (pre_3d, cur_2d), (0, 0, 0) -> (0, 0) where a depth is missing
 #include "amos_common.h"
 #include "amos_pnp_core.h"
+#include "amos_ransac.h"
 #include "amos_scene_flow.h"
 
 namespace amos {
@@ -35,30 +37,6 @@ struct PnpArgs {
     double *scratch;  // [problem][maxPoints][kPnpScratch]
 };
 
-// calls f(index i, compact index c or -1) for i < cnt, c counting the i with sel_of(i) in order (block-wide)
-template <typename Sel, typename Fn>
-__device__ __forceinline__ int block_scan(int cnt, int *sWave, Sel sel_of, Fn f)
-{
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    int total = 0;
-    for (int base = 0; base < cnt; base += kPnpThreads) {
-        const int i = base + t;
-        const bool sel = i < cnt && sel_of(i);
-        const unsigned long long b = __ballot(sel);
-        if (lane == 0) sWave[wv] = (int)__popcll(b);
-        __syncthreads();
-        int before = total, all = total;
-        for (int w = 0; w < kPnpWaves; w++) {
-            if (w < wv) before += sWave[w];
-            all += sWave[w];
-        }
-        if (i < cnt) f(i, sel ? before + (int)__popcll(b & ((1ull << lane) - 1ull)) : -1);
-        __syncthreads();
-        total = all;
-    }
-    return total;
-}
-
 __global__ __launch_bounds__(kPnpThreads) void k_pnp_ransac(const PnpArgs a)
 {
     __shared__ float4 sP[kPnpMaxPoints];  // (X, Y, Z, u) of the selected points
@@ -72,19 +50,20 @@ __global__ __launch_bounds__(kPnpThreads) void k_pnp_ransac(const PnpArgs a)
     __shared__ double sCcs[3][4][3], sSum[3][6], sAbt[3][9], sRt[3][12], sRep[3];
     __shared__ int sNeg[3];
     __shared__ int sWave[kPnpWaves];
-    __shared__ int sDrawn, sStop, sResult, sIter, sNiters, sMaxGood;
-    const int p = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    __shared__ ransac::State sR;
+    const int p = blockIdx.x, t = threadIdx.x;
     const int off = a.offsets ? a.offsets[p] : p * a.maxPoints, cnt = a.counts[p];
     double *Rout = a.Rt + (size_t)p * 12;
     int *st = a.status + (size_t)p * kPnpStatus;
+    uint8_t *mask = a.mask ? a.mask + off : nullptr;
     if (cnt < 0 || cnt > a.maxPoints) {  // out of range: nothing is read, no mask written
-        if (t < 12) Rout[t] = 0.0;
-        if (t == 0) { st[0] = -3; st[1] = 0; st[2] = 0; st[3] = 0; st[4] = 0; }
+        ransac::no_model<kPnpThreads, 12, kPnpStatus>(Rout, st, -3, 0, 0, nullptr, 0);
         return;
     }
     const float *obj = a.obj, *img = a.img;
     const uint8_t *select = a.select;
-    const int n = block_scan(cnt, sWave, [&](int i) { return !select || select[off + i] != 0; }, [&](int i, int c) {
+    auto selected = [&](int i) { return !select || select[off + i] != 0; };
+    const int n = block_compact<kPnpThreads>(cnt, sWave, selected, [&](int i, int c) {
         if (c >= 0) {
             const size_t g = (size_t)(off + i);
             sP[c] = make_float4(obj[3 * g], obj[3 * g + 1], obj[3 * g + 2], img[2 * g]);
@@ -93,12 +72,10 @@ __global__ __launch_bounds__(kPnpThreads) void k_pnp_ransac(const PnpArgs a)
     });
     const double fx = a.fx, fy = a.fy, cx = a.cx, cy = a.cy;
     if (n < pnp::kModelPoints) {  // OpenCV asserts: no model, too few points
-        if (t < 12) Rout[t] = 0.0;
-        if (t == 0) { st[0] = -1; st[1] = 0; st[2] = 0; st[3] = n; st[4] = 0; }
-        if (a.mask) for (int i = t; i < cnt; i += kPnpThreads) a.mask[off + i] = 0;
+        ransac::no_model<kPnpThreads, 12, kPnpStatus>(Rout, st, -1, 0, n, mask, cnt);
         return;
     }
-    if (t == 0) { sStop = 0; sResult = 0; sIter = 0; sNiters = a.maxIters; sMaxGood = 0; }
+    ransac::begin(sR, a.maxIters);
     if (n == pnp::kModelPoints) {  // solvePnPRansac's direct call: solvePnP(P3P) on the four points, all of them inliers
         if (t == 0) {
             float o[12], im[8];
@@ -109,42 +86,36 @@ __global__ __launch_bounds__(kPnpThreads) void k_pnp_ransac(const PnpArgs a)
             double M[12];
             const bool ok = pnp::p3p4(o, im, fx, fy, cx, cy, M);
             for (int k = 0; k < 12; k++) sBest[k] = ok ? M[k] : 0.0;
-            sResult = ok ? 1 : 0;
+            sR.result = ok ? 1 : 0;
         }
         __syncthreads();
-        const int ok = sResult;
+        const int ok = sR.result;
         if (t < 12) Rout[t] = sBest[t];
         if (t == 0) { st[0] = ok; st[1] = ok ? 4 : 0; st[2] = 0; st[3] = n; st[4] = 0; }
-        if (a.mask) block_scan(cnt, sWave, [&](int i) { return !select || select[off + i] != 0; }, [&](int i, int c) { a.mask[off + i] = c >= 0 && ok ? 1 : 0; });
+        if (mask) block_compact<kPnpThreads>(cnt, sWave, selected, [&](int i, int c) { mask[i] = c >= 0 && ok ? 1 : 0; });
         return;
     }
     __syncthreads();
+    auto error_of = [&](const double *M, int i) {
+        const float4 P = sP[i];
+        return pnp::point_error(M, P.x, P.y, P.z, P.w, sV[i], fx, fy, cx, cy);
+    };
     uint64_t rng = ~0ull;  // cv::RNG rng((uint64)-1), lane 0's copy
     for (;;) {
-        const int iter0 = sIter, limit = min(kPnpRound, sNiters - iter0);
-        // ---- draw the subsets of iterations iter0 .. iter0 + limit - 1 (getSubset: 4 distinct indices)
+        const int limit = min(kPnpRound, sR.niters - sR.iter);
+        // ---- draw the subsets of iterations iter .. iter + limit - 1 (getSubset: 4 distinct indices, no checkSubset)
         if (t == 0) {
             int drawn = 0, stop = 0;
-            for (int slot = 0; slot < limit && !stop; slot++) {
+            for (int slot = 0; slot < limit; slot++) {
                 int idx[4];
-                for (int i = 0; i < 4 && !stop; i++) {
-                    for (uint32_t draws = 1;; draws++) {
-                        const int v = (int)(fm::rng_next(rng) % (uint32_t)n);
-                        bool dup = false;
-                        for (int j = 0; j < i; j++) dup |= v == idx[j];
-                        idx[i] = v;
-                        if (!dup) break;
-                        if (draws >= fm::kRedrawCap) { stop = 2; break; }
-                    }
-                }
-                if (stop) break;
+                if (!ransac::draw_distinct<4>(rng, n, idx)) { stop = 2; break; }
                 for (int i = 0; i < 4; i++) sSub[slot][i] = idx[i];
                 drawn++;
             }
-            sDrawn = drawn; sStop = stop;
+            sR.drawn = drawn; sR.stop = stop;
         }
         __syncthreads();
-        const int drawn = sDrawn;
+        const int drawn = sR.drawn;
         // ---- P3P, one lane per subset
         if (t < drawn) {
             float o[12], im[8];
@@ -160,64 +131,24 @@ __global__ __launch_bounds__(kPnpThreads) void k_pnp_ransac(const PnpArgs a)
             for (int k = 0; k < 12; k++) sModel[t][k] = M[k];
         }
         __syncthreads();
-        // ---- scoring: model m on wave m % kPnpWaves, points over the lanes
-        for (int m = wv; m < drawn; m += kPnpWaves) {
-            if (!sOk[m]) continue;  // wave-uniform
-            double M[12];
-            for (int k = 0; k < 12; k++) M[k] = sModel[m][k];
-            int count = 0;
-            for (int i = lane; i < n; i += 64) {
-                const float4 P = sP[i];
-                count += pnp::point_error(M, P.x, P.y, P.z, P.w, sV[i], fx, fy, cx, cy) <= a.thresh2 ? 1 : 0;
-            }
-            for (int d = 32; d > 0; d >>= 1) count += __shfl_xor(count, d, 64);
-            if (lane == 0) sCount[m] = count;
-        }
+        // ---- scoring: one model per slot, sOk its count
+        ransac::score_models<kPnpThreads>(sModel, drawn, n, a.thresh2, sCount, [&](int m) { return sOk[m] != 0; }, error_of);
         __syncthreads();
-        // ---- the sequential loop of RANSACPointSetRegistrator::run over this round's iterations
-        if (t == 0) {
-            int iter = iter0, niters = sNiters, maxGood = sMaxGood, stop = 0;
-            for (int slot = 0;; slot++) {
-                if (iter >= niters) break;
-                if (slot == drawn) {
-                    if (sStop == 2) { sResult = -2; stop = 1; }
-                    break;
-                }
-                if (sOk[slot]) {
-                    const int good = sCount[slot];
-                    if (good > max(maxGood, pnp::kModelPoints - 1)) {
-                        for (int k = 0; k < 12; k++) sBest[k] = sModel[slot][k];
-                        maxGood = good;
-                        niters = pnp::update_num_iters(a.confidence, fm::dvd((double)(n - good), (double)n), niters);
-                    }
-                }
-                iter++;
-            }
-            sIter = iter; sNiters = niters; sMaxGood = maxGood;
-            if (iter >= niters) stop = 1;
-            sStop = stop ? 3 : 0;
-        }
+        if (t == 0) ransac::replay_round<12, 1, pnp::kModelPoints>(sR, n, a.confidence, sModel, sOk, sCount, sBest);
         __syncthreads();
-        if (sStop == 3) break;
+        if (sR.stop == 3) break;
     }
-    const int result = sResult == -2 ? -2 : (sMaxGood > 0 ? 1 : 0);
+    const int result = ransac::result_of(sR);
     if (result != 1) {
-        if (t < 12) Rout[t] = 0.0;
-        if (t == 0) { st[0] = result; st[1] = 0; st[2] = sIter; st[3] = n; st[4] = 0; }
-        if (a.mask) for (int i = t; i < cnt; i += kPnpThreads) a.mask[off + i] = 0;
+        ransac::no_model<kPnpThreads, 12, kPnpStatus>(Rout, st, result, sR.iter, n, mask, cnt);
         return;
     }
     // ---- the RANSAC mask, the inlier list in order
     double B[12];
     for (int k = 0; k < 12; k++) B[k] = sBest[k];
-    auto inlier = [&](int c) {
-        const float4 P = sP[c];
-        return pnp::point_error(B, P.x, P.y, P.z, P.w, sV[c], fx, fy, cx, cy) <= a.thresh2;
-    };
-    const int m = block_scan(n, sWave, inlier, [&](int i, int c) { if (c >= 0) sIdx[c] = (uint16_t)i; });
-    if (a.mask) {
-        block_scan(cnt, sWave, [&](int i) { return !select || select[off + i] != 0; }, [&](int i, int c) { a.mask[off + i] = c >= 0 && inlier(c) ? 1 : 0; });
-    }
+    auto inlier = [&](int c) { return error_of(B, c) <= a.thresh2; };
+    const int m = block_compact<kPnpThreads>(n, sWave, inlier, [&](int i, int c) { if (c >= 0) sIdx[c] = (uint16_t)i; });
+    if (mask) block_compact<kPnpThreads>(cnt, sWave, selected, [&](int i, int c) { mask[i] = c >= 0 && inlier(c) ? 1 : 0; });
     // ---- EPnP on the m inliers (m = maxGood >= 4)
     double *scr = a.scratch + (size_t)p * a.maxPoints * kPnpScratch;
     auto pw_of = [&](int j, double *pw) {
@@ -352,7 +283,7 @@ __global__ __launch_bounds__(kPnpThreads) void k_pnp_ransac(const PnpArgs a)
         bool ok = true;
         for (int k = 0; k < 12; k++) ok = ok && pnp::finite_(sRt[N][k]);
         for (int k = 0; k < 12; k++) Rout[k] = ok ? sRt[N][k] : sBest[k];
-        st[0] = 1; st[1] = sMaxGood; st[2] = sIter; st[3] = n; st[4] = ok ? 1 : -1;
+        st[0] = 1; st[1] = sR.maxGood; st[2] = sR.iter; st[3] = n; st[4] = ok ? 1 : -1;
     }
 }
 
@@ -366,10 +297,8 @@ __global__ __launch_bounds__(256) void k_pnp_points(const float2 *__restrict__ p
     const int i = blockIdx.x * 256 + threadIdx.x, n = *dN;
     if (n < 0 || n > maxPoints || i >= n) return;
     const float2 P = pre[i], Q = next[i];
-    const int x1 = (int)P.x, y1 = (int)P.y, x2 = (int)Q.x, y2 = (int)Q.y;
-    const bool in1 = P.x >= 0 && P.y >= 0 && x1 < width && y1 < height, in2 = Q.x >= 0 && Q.y >= 0 && x2 < width && y2 < height;
-    const float z1 = in1 ? depthLast[(size_t)y1 * lastStride + x1] : 0.f;
-    const float z2 = in2 ? depthCur[(size_t)y2 * curStride + x2] : 0.f;
+    float z1, z2;
+    scene_flow_depths(depthLast, lastStride, depthCur, curStride, width, height, P, Q, z1, z2);
     float o0 = 0.f, o1 = 0.f, o2 = 0.f, u = 0.f, v = 0.f;
     if (z1 > 0 && z2 > 0) {
         scene_flow_pre3d(sa, P.x, P.y, z1, o0, o1, o2);
@@ -384,25 +313,13 @@ __global__ __launch_bounds__(256) void k_pnp_points(const float2 *__restrict__ p
 
 using namespace amos;
 
-struct amos_pnp {
-    int device = 0, maxPoints = 0, maxProblems = 0;
-    hipStream_t stream = nullptr;
-    bool ownStream = false;
+struct amos_pnp : StreamHandle {
+    int maxPoints = 0, maxProblems = 0;
     float *dObj = nullptr, *dImg = nullptr;
     int *dInt = nullptr;  // [0] zero offset, [1] count of the synchronous call, [2..6] its status
     double *dRt = nullptr, *dScratch = nullptr;
     uint8_t *dMask = nullptr;
 };
-
-static bool pnp_params_ok(double reprojection_error, double confidence, int max_iters)
-{
-    return reprojection_error > 0 && confidence > 0 && confidence < 1 && max_iters >= 1 && max_iters <= (1 << 20);
-}
-
-static bool pnp_camera_ok(double fx, double fy, double cx, double cy)
-{
-    return fx > 0 && fy > 0 && cx - cx == 0 && cy - cy == 0 && fx - fx == 0 && fy - fy == 0;
-}
 
 static int pnp_launch(amos_pnp *h, int n_problems, const float *d_obj, const float *d_img, const int *d_offsets, const int *d_counts, const uint8_t *d_select,
                       double fx, double fy, double cx, double cy, double reprojection_error, double confidence, int max_iters, double *d_Rt, int *d_status,
@@ -431,14 +348,10 @@ int amos_pnp_create(int device, void *stream, int max_points, int max_problems, 
         return AMOS_ERR_INVALID;
     }
     *out = nullptr;
-    AMOS_HIP_CHECK(hipSetDevice(device));
     amos_pnp *h = new amos_pnp();
-    h->device = device; h->maxPoints = max_points; h->maxProblems = max_problems;
-    if (stream) h->stream = (hipStream_t)stream;
-    else {
-        if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { set_error("hipStreamCreate failed"); delete h; return AMOS_ERR_DEVICE; }
-        h->ownStream = true;
-    }
+    h->maxPoints = max_points; h->maxProblems = max_problems;
+    const int rc = h->open(device, stream);
+    if (rc != AMOS_OK) { delete h; return rc; }
     hipError_t e = hipMalloc((void **)&h->dObj, sizeof(float) * 3 * max_points);
     if (e == hipSuccess) e = hipMalloc((void **)&h->dImg, sizeof(float) * 2 * max_points);
     if (e == hipSuccess) e = hipMalloc((void **)&h->dInt, sizeof(int) * 8);
@@ -455,10 +368,8 @@ int amos_pnp_create(int device, void *stream, int max_points, int max_problems, 
 void amos_pnp_destroy(amos_pnp *h)
 {
     if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    h->close();
     for (void *q : {(void *)h->dObj, (void *)h->dImg, (void *)h->dInt, (void *)h->dRt, (void *)h->dScratch, (void *)h->dMask}) if (q) (void)hipFree(q);
-    if (h->ownStream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
 
@@ -469,7 +380,7 @@ int amos_pnp_ransac_device(amos_pnp *h, int n_problems, const float *d_object_xy
                            double *d_Rt, int32_t *d_status, uint8_t *d_mask)
 {
     if (!h || n_problems < 0 || n_problems > h->maxProblems || !d_object_xyz || !d_image_xy || !d_counts || !d_Rt || !d_status ||
-        !pnp_params_ok(reprojection_error, confidence, max_iters) || !pnp_camera_ok(fx, fy, cx, cy)) {
+        !ransac_params_ok(reprojection_error, confidence, max_iters) || !camera_ok(fx, fy, cx, cy)) {
         set_error("amos_pnp_ransac_device: invalid argument");
         return AMOS_ERR_INVALID;
     }
@@ -484,7 +395,7 @@ int amos_pnp_scene_flow_device(amos_pnp *h, const float *d_pre_xy, const float *
                                const amos_scene_flow_camera *cam, double fx, double fy, double *d_Rt, int32_t *d_status, uint8_t *d_mask)
 {
     if (!h || !d_pre_xy || !d_next_xy || !d_state || !d_n || !d_depth_last || !d_depth_cur || !cam || !d_Rt || !d_status || width < 1 || height < 1 ||
-        last_stride < (size_t)width || cur_stride < (size_t)width || !pnp_camera_ok(fx, fy, cam->cx, cam->cy)) {
+        last_stride < (size_t)width || cur_stride < (size_t)width || !camera_ok(fx, fy, cam->cx, cam->cy)) {
         set_error("amos_pnp_scene_flow_device: invalid argument");
         return AMOS_ERR_INVALID;
     }
@@ -500,8 +411,8 @@ int amos_pnp_scene_flow_device(amos_pnp *h, const float *d_pre_xy, const float *
 int amos_pnp_ransac(amos_pnp *h, int n, const float *object_xyz, const float *image_xy, double fx, double fy, double cx, double cy, double reprojection_error,
                     double confidence, int max_iters, double *Rt, uint8_t *mask, int32_t *status)
 {
-    if (!h || n < 0 || n > h->maxPoints || (n > 0 && (!object_xyz || !image_xy)) || !Rt || !status || !pnp_params_ok(reprojection_error, confidence, max_iters) ||
-        !pnp_camera_ok(fx, fy, cx, cy)) {
+    if (!h || n < 0 || n > h->maxPoints || (n > 0 && (!object_xyz || !image_xy)) || !Rt || !status || !ransac_params_ok(reprojection_error, confidence, max_iters) ||
+        !camera_ok(fx, fy, cx, cy)) {
         set_error("amos_pnp_ransac: invalid argument (n <= max_points)");
         return AMOS_ERR_INVALID;
     }

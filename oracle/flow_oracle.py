@@ -71,17 +71,19 @@ def fundamental_errors(F, p1, p2):
     F = np.asarray(F, np.float64).reshape(9)
     x1, y1 = p1[:, 0].astype(np.float64), p1[:, 1].astype(np.float64)
     x2, y2 = p2[:, 0].astype(np.float64), p2[:, 1].astype(np.float64)
-    a = (F[0] * x1 + F[1] * y1) + F[2]
-    b = (F[3] * x1 + F[4] * y1) + F[5]
-    c = (F[6] * x1 + F[7] * y1) + F[8]
-    s2 = 1.0 / (a * a + b * b)
-    d2 = (x2 * a + y2 * b) + c
-    a = (F[0] * x2 + F[3] * y2) + F[6]
-    b = (F[1] * x2 + F[4] * y2) + F[7]
-    c = (F[2] * x2 + F[5] * y2) + F[8]
-    s1 = 1.0 / (a * a + b * b)
-    d1 = (x1 * a + y1 * b) + c
-    return np.maximum((d1 * d1) * s1, (d2 * d2) * s2).astype(np.float32)
+    with np.errstate(all="ignore"):
+        a = (F[0] * x1 + F[1] * y1) + F[2]
+        b = (F[3] * x1 + F[4] * y1) + F[5]
+        c = (F[6] * x1 + F[7] * y1) + F[8]
+        s2 = 1.0 / (a * a + b * b)
+        d2 = (x2 * a + y2 * b) + c
+        a = (F[0] * x2 + F[3] * y2) + F[6]
+        b = (F[1] * x2 + F[4] * y2) + F[7]
+        c = (F[2] * x2 + F[5] * y2) + F[8]
+        s1 = 1.0 / (a * a + b * b)
+        d1 = (x1 * a + y1 * b) + c
+        e1, e2 = (d1 * d1) * s1, (d2 * d2) * s2
+        return np.where(e1 < e2, e2, e1).astype(np.float32)  # std::max(e1, e2) = e1 < e2 ? e2 : e1: a NaN e1 stays
 
 
 def pnp_errors(R, t, obj, img, fx, fy, cx, cy):

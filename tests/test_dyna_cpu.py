@@ -170,6 +170,9 @@ def test_dyna_entry_points_reject_bad_arguments(pkg):
     d = C.c_double
     assert L.amos_dyna_tail_device(None, C.c_int(0), buf, buf, buf, buf, buf, buf, buf, buf, buf, C.c_size_t(640), buf, C.c_size_t(640), C.c_int(640),
                                    C.c_int(480), C.byref(cam), d(500), d(500), C.byref(poses)) == -1
+    for fx, fy in ((float("inf"), 500.0), (500.0, float("inf")), (float("nan"), 500.0), (0.0, 500.0)):  # the PnP's camera rule: finite, positive
+        assert L.amos_dyna_tail_device(None, C.c_int(0), buf, buf, buf, buf, buf, buf, buf, buf, buf, C.c_size_t(640), buf, C.c_size_t(640), C.c_int(640),
+                                       C.c_int(480), C.byref(cam), d(fx), d(fy), C.byref(poses)) == -1
     assert L.amos_dyna_reset_frame_device(None, C.c_int(0)) == -1
     assert L.amos_dyna_decide_batch_device(None, C.c_int(1), buf, C.c_size_t(0), C.c_size_t(640), C.c_int(640), C.c_int(480), buf, C.c_size_t(0),
                                            C.c_int(100), C.c_int(15), buf, C.c_size_t(15)) == -1

@@ -84,6 +84,20 @@ def test_ransac_special_inputs():
     assert fr.find_fundamental_ransac(p1, p2, max_iters=5)[2][2] == 5
 
 
+def test_error_keeps_a_nan_first_term():
+    """std::max(e1, e2) = e1 < e2 ? e2 : e1: with F = [[0, 0, 1], [0, 0, 0], [0, 0, 0]] and x2 = 0, e2 = 0 and e1 = 0 * inf = NaN; the
+    error is NaN and the point is not an inlier (flow_oracle.fundamental_errors, the scorer kernel's check, follows the same rule)."""
+    import os
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle"))
+    import flow_oracle as fo
+    F = np.array([[0, 0, 1], [0, 0, 0], [0, 0, 0]], np.float64)
+    p1, p2 = np.array([[5, 7], [5, 7]], np.float32), np.array([[0, 2], [3, 2]], np.float32)
+    for e in (fr.errors(F, p1, p2), fo.fundamental_errors(F, p1, p2)):
+        assert e.dtype == np.float32 and np.isnan(e[0]) and np.isinf(e[1])
+        assert not (e <= np.float32(0.1 * 0.1)).any()
+
+
 def test_rng_is_opencvs_multiply_with_carry():
     r = fr.Rng()
     a = [r.next() for _ in range(3)]

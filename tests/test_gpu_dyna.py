@@ -102,6 +102,19 @@ def test_tail_rejects_a_count_out_of_range_and_resets(gpu_lib, dyna):
     assert r["status"] == dr.RESET and np.all(r["counts"] == 0)
 
 
+def test_tail_rejects_an_infinite_focal_length(gpu_lib, dyna):
+    """the PnP entry points' camera rule (finite, positive fx / fy) holds for the tail alone too; every buffer is real and n = 0"""
+    import torch
+    z = torch.zeros(640 * 480, dtype=torch.float32, device="cuda")
+    args = lambda fx, fy: (0, z.data_ptr(), z.data_ptr(), z.data_ptr(), z.data_ptr(), z.data_ptr(), z.data_ptr(), z.data_ptr(), z.data_ptr(),
+                           z.data_ptr(), 640, z.data_ptr(), 640, 640, 480, _camera(gpu_lib), fx, fy, gpu_lib.DynaPoses.of(np.eye(3, 4, dtype=np.float32)))
+    for fx, fy in ((float("inf"), dr.FY), (dr.FX, float("inf"))):
+        with pytest.raises(gpu_lib.AmosError):
+            dyna.tail_device(*args(fx, fy))
+    dyna.tail_device(*args(dr.FX, dr.FY))
+    assert np.all(dyna.fetch(0)["counts"] == 0)
+
+
 def _tails(gpu_lib, dyna, n_frames, n=400):
     """slot f: a tail on a scene of seed f (moving points), returns the fetched lists"""
     out = []

@@ -135,6 +135,21 @@ def test_ransac_hypothesis_scorers_vs_numpy(gpu_lib, synth):
     torch.cuda.synchronize()
     assert torch.equal(cnt, cnt2)
 
+    # std::max's rule on a NaN first term: F = [[0, 0, 1], [0, 0, 0], [0, 0, 0]] and x2 = 0 give e2 = 0 and e1 = 0 * inf = NaN; the error is
+    # NaN and the point no inlier (the second correspondence, x2 = 3, has e1 = inf and e2 = 9)
+    Fn = np.array([[0, 0, 1], [0, 0, 0], [0, 0, 0]], np.float64).reshape(1, 9)
+    q1, q2 = np.array([[5, 7], [5, 7]], np.float32), np.array([[0, 2], [3, 2]], np.float32)
+    d_Fn, d_q1, d_q2 = torch.from_numpy(Fn).cuda(), torch.from_numpy(q1).cuda(), torch.from_numpy(q2).cuda()
+    err_n = torch.zeros((1, 2), device="cuda")
+    cnt_n = torch.full((1,), -1, dtype=torch.int32, device="cuda")
+    msk_n = torch.full((1, 2), 7, dtype=torch.uint8, device="cuda")
+    gpu_lib.flow_fundamental_score(st, d_Fn.data_ptr(), 1, d_q1.data_ptr(), d_q2.data_ptr(), 2, 0.1, err_n.data_ptr(), cnt_n.data_ptr(), msk_n.data_ptr())
+    torch.cuda.synchronize()
+    want = fo.fundamental_errors(Fn[0], q1, q2)
+    assert np.isnan(want[0]) and np.isinf(want[1])
+    assert err_n[0].cpu().numpy().tobytes() == want.tobytes()
+    assert msk_n[0].cpu().numpy().tolist() == [0, 0] and int(cnt_n[0]) == 0
+
     # poses: the true one, perturbed ones, one that puts a point at depth exactly zero
     obj = X.astype(np.float32)
     obj[5] = [0.3, 0.2, 0.0]
