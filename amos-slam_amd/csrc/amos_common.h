@@ -52,8 +52,9 @@ inline hipError_t set_max_dynamic_lds(DeviceOnce &once, const void *kernel, int 
     return e;
 }
 
-// The stream-owning part of a scene-flow handle (corners, LK, fmat, pnp, dyna): the caller's stream, or a non-blocking one of the
-// handle's own.  open() makes the device current; close() does too (the frees that follow it need it), then drains the stream.
+// The stream-owning part of every handle of the library (orb, match, slic, mask_pre, corners, LK, fmat, pnp, dyna): the caller's stream,
+// or a non-blocking one of the handle's own.  open() makes the device current; close() does too (the frees that follow it need it), then
+// drains the stream.
 struct StreamHandle {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -64,7 +65,7 @@ struct StreamHandle {
         device = device_;
         if (stream_) stream = (hipStream_t)stream_;
         else {
-            if (hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) != hipSuccess) { set_error("hipStreamCreate failed"); return AMOS_ERR_DEVICE; }
+            AMOS_HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
             ownStream = true;
         }
         return AMOS_OK;

@@ -306,10 +306,8 @@ __global__ __launch_bounds__(256) void k_nms_column_max(const float4 *__restrict
 
 using namespace amos;
 
-struct amos_mask_pre {
-    int device = 0, width = 0, height = 0, maxBatch = 0;
-    hipStream_t stream = nullptr;
-    bool ownStream = false;
+struct amos_mask_pre : StreamHandle {
+    int width = 0, height = 0, maxBatch = 0;
     FixTap *dFixX = nullptr, *dFixY = nullptr;
     FltTap *dFltX = nullptr, *dFltY = nullptr;
     float *dLut = nullptr, *dMid = nullptr, *dBack = nullptr;
@@ -359,15 +357,10 @@ extern "C" {
 int amos_mask_pre_create(int device, void *stream, int width, int height, int max_batch, amos_mask_pre **out)
 {
     if (!out || width < 2 || height < 2 || max_batch < 1) { set_error("amos_mask_pre_create: invalid argument"); return AMOS_ERR_INVALID; }
-    AMOS_HIP_CHECK(hipSetDevice(device));
     amos_mask_pre *p = new amos_mask_pre();
-    p->device = device; p->width = width; p->height = height; p->maxBatch = max_batch;
-    if (stream) p->stream = (hipStream_t)stream;
-    else {
-        hipError_t e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
-        if (e != hipSuccess) { set_error("hipStreamCreate: %s", hipGetErrorString(e)); delete p; return AMOS_ERR_DEVICE; }
-        p->ownStream = true;
-    }
+    p->width = width; p->height = height; p->maxBatch = max_batch;
+    const int rc = p->open(device, stream);
+    if (rc != AMOS_OK) { delete p; return rc; }
     std::vector<int> s0, s1;
     std::vector<float> f;
     auto fix = [&](int srcN, int dstN, bool clamp, FixTap **dst, int **first) -> hipError_t {
@@ -416,11 +409,9 @@ int amos_mask_pre_create(int device, void *stream, int width, int height, int ma
 void amos_mask_pre_destroy(amos_mask_pre *p)
 {
     if (!p) return;
-    (void)hipSetDevice(p->device);
-    if (p->stream) (void)hipStreamSynchronize(p->stream);
+    p->close();
     void *ptrs[] = {p->dFixX, p->dFixY, p->dFltX, p->dFltY, p->dLut, p->dMid, p->dBack, p->dFirstX, p->dFirstY};
     for (void *q : ptrs) if (q) (void)hipFree(q);
-    if (p->ownStream && p->stream) (void)hipStreamDestroy(p->stream);
     delete p;
 }
 

@@ -589,10 +589,7 @@ __global__ __launch_bounds__(64 * kWaves * kQ) void k_bf_best2_mfma(const uint8_
 
 using namespace amos;
 
-struct amos_match {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool ownStream = false;
+struct amos_match : StreamHandle {
     // device scratch of the host-pointer entry points: the inputs of the call in flight (pointers into dArena), the grow-only result buffer
     uint8_t *dQ = nullptr, *dT = nullptr;
     int *dOff = nullptr, *dIdx = nullptr;
@@ -737,15 +734,9 @@ extern "C" {
 int amos_match_create(int device, void *stream, amos_match **out)
 {
     if (!out) { set_error("amos_match_create: invalid argument"); return AMOS_ERR_INVALID; }
-    AMOS_HIP_CHECK(hipSetDevice(device));
     amos_match *m = new amos_match();
-    m->device = device;
-    if (stream) m->stream = (hipStream_t)stream;
-    else {
-        hipError_t e = hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking);
-        if (e != hipSuccess) { set_error("hipStreamCreate: %s", hipGetErrorString(e)); delete m; return AMOS_ERR_DEVICE; }
-        m->ownStream = true;
-    }
+    const int rc = m->open(device, stream);
+    if (rc != AMOS_OK) { delete m; return rc; }
     *out = m;
     return AMOS_OK;
 }
@@ -753,12 +744,10 @@ int amos_match_create(int device, void *stream, amos_match **out)
 void amos_match_destroy(amos_match *m)
 {
     if (!m) return;
-    (void)hipSetDevice(m->device);
-    if (m->stream) (void)hipStreamSynchronize(m->stream);
+    m->close();
     void *ptrs[] = {m->dArena, m->dOut};  // (dQ / dT / dOff / dIdx point into the arena)
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (m->hStage) (void)hipHostFree(m->hStage);
-    if (m->ownStream && m->stream) (void)hipStreamDestroy(m->stream);
     delete m;
 }
 

@@ -46,11 +46,9 @@ constexpr int kTimingEvents = 9;
 
 using namespace amos;
 
-struct amos_orb {
+struct amos_orb : StreamHandle {
     amos_orb_params p{};
-    int maxW = 0, maxH = 0, maxB = 0, device = 0;
-    hipStream_t stream = nullptr;
-    bool ownStream = false;
+    int maxW = 0, maxH = 0, maxB = 0;
     // side stream: the blur only needs the pyramid, so it runs beside the latency-bound quad-tree
     hipStream_t streamB = nullptr;
     hipEvent_t evFork = nullptr, evJoin = nullptr, evBlur0 = nullptr, evBlur1 = nullptr;
@@ -569,25 +567,19 @@ int amos_orb_create(const amos_orb_params *params, int max_width, int max_height
         set_error("amos_orb_create: invalid argument");
         return AMOS_ERR_INVALID;
     }
-    AMOS_HIP_CHECK(hipSetDevice(device));
     amos_orb *h = new amos_orb();
     h->p = *params;
     h->maxW = max_width;
     h->maxH = max_height;
     h->maxB = max_batch;
-    h->device = device;
+    int rc = h->open(device, stream);
+    if (rc != AMOS_OK) { delete h; return rc; }
     build_tables(h);
     static const int kUmax[16] = {15, 15, 15, 15, 14, 14, 14, 13, 13, 12, 11, 10, 9, 8, 6, 3};
-    if (std::memcmp(kUmax, h->umax, sizeof(kUmax)) != 0) { set_error("umax table mismatch"); delete h; return AMOS_ERR_INVALID; }
-    int rc = compute_capacity(h);
-    if (rc != AMOS_OK) { delete h; return rc; }
+    if (std::memcmp(kUmax, h->umax, sizeof(kUmax)) != 0) { set_error("umax table mismatch"); amos_orb_destroy(h); return AMOS_ERR_INVALID; }
+    rc = compute_capacity(h);
+    if (rc != AMOS_OK) { amos_orb_destroy(h); return rc; }
     const Geom &c = h->capGeom;
-    if (stream) h->stream = (hipStream_t)stream;
-    else {
-        hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-        if (e != hipSuccess) { set_error("hipStreamCreate: %s", hipGetErrorString(e)); delete h; return AMOS_ERR_DEVICE; }
-        h->ownStream = true;
-    }
     if (hipStreamCreateWithFlags(&h->streamB, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&h->evFork, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&h->evJoin, hipEventDisableTiming) != hipSuccess || hipEventCreate(&h->evBlur0) != hipSuccess ||
@@ -675,8 +667,7 @@ int amos_orb_create(const amos_orb_params *params, int max_width, int max_height
 void amos_orb_destroy(amos_orb *h)
 {
     if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    h->close();
     void *ptrs[] = {h->dGeom, h->dCells, h->dTaps, h->dPyr, h->dBlur, h->dInput, h->dSlotCount, h->dSlots, h->dPts,
                     h->dNodeOf, h->dQuadOf, h->dCandCount, h->dLvCount, h->dOutCount, h->dLvKps, h->dOutKps, h->dOutDesc,
                     h->dRemoved, h->dScratchKps, h->dMask, h->dMaskTmp, h->dMaskClosed, h->dLabels, h->dCenterIds, h->dRm,
@@ -687,7 +678,6 @@ void amos_orb_destroy(amos_orb *h)
     for (hipEvent_t e : h->events) (void)hipEventDestroy(e);
     if (h->streamB) { (void)hipStreamSynchronize(h->streamB); (void)hipStreamDestroy(h->streamB); }
     for (hipEvent_t e : {h->evFork, h->evJoin, h->evBlur0, h->evBlur1}) if (e) (void)hipEventDestroy(e);
-    if (h->ownStream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
 

@@ -285,10 +285,8 @@ __global__ __launch_bounds__(256) void k_bgr2lab(const uint8_t *__restrict__ src
 
 using namespace amos;
 
-struct amos_slic {
-    int device = 0, maxW = 0, maxH = 0, maxB = 0;
-    hipStream_t stream = nullptr;
-    bool ownStream = false;
+struct amos_slic : StreamHandle {
+    int maxW = 0, maxH = 0, maxB = 0;
     unsigned long long *dDis = nullptr;
     int *dCk = nullptr;
     // host-call staging
@@ -317,15 +315,10 @@ int amos_slic_center_count(int width, int height, int len, int *nx, int *ny)
 int amos_slic_create(int device, void *stream, int max_width, int max_height, int max_batch, amos_slic **out)
 {
     if (!out || max_width < 3 || max_height < 3 || max_batch < 1) { set_error("amos_slic_create: invalid argument"); return AMOS_ERR_INVALID; }
-    AMOS_HIP_CHECK(hipSetDevice(device));
     amos_slic *s = new amos_slic();
-    s->device = device; s->maxW = max_width; s->maxH = max_height; s->maxB = max_batch;
-    if (stream) s->stream = (hipStream_t)stream;
-    else {
-        hipError_t e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);
-        if (e != hipSuccess) { set_error("hipStreamCreate: %s", hipGetErrorString(e)); delete s; return AMOS_ERR_DEVICE; }
-        s->ownStream = true;
-    }
+    s->maxW = max_width; s->maxH = max_height; s->maxB = max_batch;
+    const int rc = s->open(device, stream);
+    if (rc != AMOS_OK) { delete s; return rc; }
     const size_t px = (size_t)max_width * max_height, B = (size_t)max_batch;
     hipError_t e = hipMalloc((void **)&s->dDis, sizeof(unsigned long long) * px * B);
     if (e == hipSuccess) e = hipMalloc((void **)&s->dCk, sizeof(int) * px * B);
@@ -341,12 +334,9 @@ int amos_slic_create(int device, void *stream, int max_width, int max_height, in
 void amos_slic_destroy(amos_slic *s)
 {
     if (!s) return;
-    if (s->dLabTabs) (void)hipFree(s->dLabTabs);
-    (void)hipSetDevice(s->device);
-    if (s->stream) (void)hipStreamSynchronize(s->stream);
-    void *ptrs[] = {s->dDis, s->dCk, s->dLab, s->dDepth, s->dLabels, s->dCenters};
+    s->close();
+    void *ptrs[] = {s->dDis, s->dCk, s->dLab, s->dDepth, s->dLabels, s->dCenters, s->dLabTabs};
     for (void *p : ptrs) if (p) (void)hipFree(p);
-    if (s->ownStream && s->stream) (void)hipStreamDestroy(s->stream);
     delete s;
 }
 

@@ -79,7 +79,7 @@ class MaskEngine:
         # make the consumer (the network, on torch's stream) wait for them
         ev_in = torch.cuda.Event()
         ev_in.record(cur)
-        ext = torch.cuda.ExternalStream(pre.stream_ptr, device=self.device)
+        ext = torch.cuda.ExternalStream(pre.stream, device=self.device)
         ext.wait_event(ev_in)
         pre.run(frames.data_ptr(), b, out.data_ptr())
         ev_out = torch.cuda.Event()

@@ -66,6 +66,30 @@ def test_cabi_exports_every_declared_symbol(pkg):
     assert sorted(pkg.EXPORTS) == declared
 
 
+def test_prototype_table_matches_the_header(pkg):
+    """The binding's one table of prototypes against include/amos_frontend.h: for every declared function the number of argtypes is the
+    number of parameters, the restype is the declared return type, every pointer parameter is a void pointer and every scalar its own type."""
+    hdr = open(os.path.join(ROOT, "include", "amos_frontend.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    protos = re.findall(r"([A-Za-z_][\w \*]*?)\b(amos_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", hdr)
+    assert sorted(name for _, name, _ in protos) == sorted(set(re.findall(r"\b(amos_[a-z0-9_]+)\s*\(", hdr)))  # every declaration parsed
+    restypes = {"void": None, "void *": ctypes.c_void_p, "const char *": ctypes.c_char_p, "size_t": ctypes.c_size_t, "int": ctypes.c_int}
+    scalars = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t,
+               "long long": ctypes.c_longlong, "uint32_t": ctypes.c_uint32}
+    assert sorted(pkg.PROTOTYPES) == sorted(name for _, name, _ in protos)
+    for ret, name, params in protos:
+        params = [p for p in (q.strip() for q in params.split(",")) if p and p != "void"]
+        restype, argtypes = pkg.PROTOTYPES[name]
+        assert len(argtypes) == len(params), (name, len(argtypes), params)
+        assert restype is restypes[" ".join(ret.split())], (name, ret, restype)
+        for p, t in zip(params, argtypes):  # a pointer is a void pointer, a scalar its own type
+            want = ctypes.c_void_p if "*" in p or "[" in p else scalars[" ".join(p.replace("const ", "").split()[:-1])]
+            assert t is want, (name, p, t)
+    L = pkg.lib()  # applied once, to every function
+    for name, (restype, argtypes) in pkg.PROTOTYPES.items():
+        assert getattr(L, name).restype is restype and tuple(getattr(L, name).argtypes) == tuple(argtypes), name
+
+
 def test_keypoint_layout_matches_cv_keypoint(pkg):
     """amos_keypoint must be memcpy-compatible with cv::KeyPoint (7 x 4 bytes, pt first)."""
     assert pkg.KP_DTYPE.itemsize == 28
