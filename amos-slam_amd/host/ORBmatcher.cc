@@ -41,19 +41,18 @@ bool FeatureGrid::PosInGrid(const amos_keypoint &kp, int &posX, int &posY) const
     return true;
 }
 
-// Frame.cc:894-1003
-vector<size_t> FeatureGrid::GetFeaturesInArea(const float &x, const float &y, const float &r, const int minLevel, const int maxLevel) const
+// Frame.cc:894-1003, appending to vIndices
+void FeatureGrid::AppendFeaturesInArea(vector<int> &vIndices, const float &x, const float &y, const float &r, const int minLevel,
+                                       const int maxLevel) const
 {
-    vector<size_t> vIndices;
-    vIndices.reserve(mFrame.n);
     const int nMinCellX = max(0, (int)floor((x - mFrame.min_x - r) * mfGridElementWidthInv));
-    if (nMinCellX >= AMOS_FRAME_GRID_COLS) return vIndices;
+    if (nMinCellX >= AMOS_FRAME_GRID_COLS) return;
     const int nMaxCellX = min((int)AMOS_FRAME_GRID_COLS - 1, (int)ceil((x - mFrame.min_x + r) * mfGridElementWidthInv));
-    if (nMaxCellX < 0) return vIndices;
+    if (nMaxCellX < 0) return;
     const int nMinCellY = max(0, (int)floor((y - mFrame.min_y - r) * mfGridElementHeightInv));
-    if (nMinCellY >= AMOS_FRAME_GRID_ROWS) return vIndices;
+    if (nMinCellY >= AMOS_FRAME_GRID_ROWS) return;
     const int nMaxCellY = min((int)AMOS_FRAME_GRID_ROWS - 1, (int)ceil((y - mFrame.min_y + r) * mfGridElementHeightInv));
-    if (nMaxCellY < 0) return vIndices;
+    if (nMaxCellY < 0) return;
     const bool bCheckLevels = (minLevel > 0) || (maxLevel >= 0);
     for (int ix = nMinCellX; ix <= nMaxCellX; ix++) {
         for (int iy = nMinCellY; iy <= nMaxCellY; iy++) {
@@ -68,11 +67,17 @@ vector<size_t> FeatureGrid::GetFeaturesInArea(const float &x, const float &y, co
                 }
                 const float distx = kpUn.x - x;
                 const float disty = kpUn.y - y;
-                if (fabs(distx) < r && fabs(disty) < r) vIndices.push_back(vCell[j]);
+                if (fabs(distx) < r && fabs(disty) < r) vIndices.push_back((int)vCell[j]);
             }
         }
     }
-    return vIndices;
+}
+
+vector<size_t> FeatureGrid::GetFeaturesInArea(const float &x, const float &y, const float &r, const int minLevel, const int maxLevel) const
+{
+    vector<int> vIndices;
+    AppendFeaturesInArea(vIndices, x, y, r, minLevel, maxLevel);
+    return vector<size_t>(vIndices.begin(), vIndices.end());
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -159,22 +164,153 @@ void AMOS_VIEW_MATCHER::DescriptorDistances(const uint8_t *q, int nq, const uint
     Check(amos_match_distances(Handle(), q, nq, t, nt, out.data()), "amos_match_distances");
 }
 
-void AMOS_VIEW_MATCHER::ListDistances(const amos_frame_view &train, const uint8_t *queries, int nq, const std::vector<int> &off,
-                               const std::vector<int> &idx, std::vector<uint16_t> &dist)
-{
-    dist.resize(idx.size());
-    if (idx.empty()) return;
-    Check(amos_match_list_distances(Handle(), queries, nq, train.descriptors, train.n, off.data(), idx.data(), dist.data()),
-          "amos_match_list_distances");
-}
+// ---------------------------------------------------------------------------------------------
+// The pieces every search is built from: candidate lists (with the one GPU call and the scans over its result) and the
+// rotation histogram.  Each search below is then: candidates, scan, its own accept rule, prune.
 
-void AMOS_VIEW_MATCHER::ListDistances(const uint8_t *train, int nt, const uint8_t *queries, int nq, const std::vector<int> &off,
-                               const std::vector<int> &idx, std::vector<uint16_t> &dist)
+// The candidate lists of all queries of a search, in CSR form: query i's candidates are idx[off[i] .. off[i + 1]), dist[] their
+// distances.  A list is filled by Open(), then pushing onto idx (Open() and Distances() close the list before).
+struct AMOS_VIEW_MATCHER::CandidateLists {
+    vector<int> off, idx;
+    vector<uint8_t> qdesc;  // the queries' descriptors, 32 bytes each
+    vector<uint16_t> dist;
+
+    explicit CandidateLists(int nq = 0)
+    {
+        off.reserve(nq + 1);
+        off.push_back(0);
+        qdesc.reserve((size_t)nq * 32);
+    }
+    // next query; desc = nullptr when the caller hands Distances() a descriptor block of its own
+    void Open(const uint8_t *desc = nullptr)
+    {
+        off.back() = (int)idx.size();
+        off.push_back(off.back());
+        if (desc) qdesc.insert(qdesc.end(), desc, desc + 32);
+    }
+    bool Empty(int i) const { return off[i] == off[i + 1]; }
+
+    // all candidate distances in one GPU call
+    void Distances(AMOS_VIEW_MATCHER &m, const uint8_t *train, int nt, const uint8_t *queries = nullptr)
+    {
+        off.back() = (int)idx.size();
+        dist.resize(idx.size());
+        if (idx.empty()) return;
+        Check(amos_match_list_distances(m.Handle(), queries ? queries : qdesc.data(), (int)off.size() - 1, train, nt, off.data(), idx.data(),
+                                        dist.data()),
+              "amos_match_list_distances");
+    }
+
+    // Best candidate of query i among those skip(candidate, distance) lets through: the FIRST of the smallest distance below
+    // the value bestDist comes in with, or -1.
+    template <typename Skip>
+    int Best(int i, int &bestDist, Skip skip) const
+    {
+        int bestIdx = -1;
+        for (int k = off[i]; k < off[i + 1]; k++) {
+            const int d = dist[k];
+            if (skip(idx[k], d)) continue;
+            if (d < bestDist) {
+                bestDist = d;
+                bestIdx = idx[k];
+            }
+        }
+        return bestIdx;
+    }
+    int Best(int i, int &bestDist) const
+    {
+        return Best(i, bestDist, [](int, int) { return false; });
+    }
+    // ... and the second best distance (with its candidate, when asked for)
+    template <typename Skip>
+    int Best2(int i, int &bestDist, int &bestDist2, Skip skip, int *pBestIdx2 = nullptr) const
+    {
+        int bestIdx = -1, bestIdx2 = -1;
+        for (int k = off[i]; k < off[i + 1]; k++) {
+            const int d = dist[k];
+            if (skip(idx[k], d)) continue;
+            if (d < bestDist) {
+                bestDist2 = bestDist;
+                bestDist = d;
+                bestIdx2 = bestIdx;
+                bestIdx = idx[k];
+            } else if (d < bestDist2) {
+                bestDist2 = d;
+                bestIdx2 = idx[k];
+            }
+        }
+        if (pBestIdx2) *pBestIdx2 = bestIdx2;
+        return bestIdx;
+    }
+
+    // Node-by-node search between two feature vectors (ORBmatcher.cc:248-339, :673-760, :835-935): for every feature of side A
+    // that take1 accepts (q1 lists them), the features of side B in the same node, in the FeatureVector's order.  The two-iterator
+    // merge over the ascending node ids is the reference's (lower_bound on a std::map = first node id >= the other side's).
+    template <typename Take1>
+    void OpenSharedNodes(const amos_bow_view &A, const amos_bow_view &B, Take1 take1, vector<int> &q1)
+    {
+        int a = 0, b = 0;
+        while (a < A.n_nodes && b < B.n_nodes) {
+            if (A.node_ids[a] == B.node_ids[b]) {
+                for (int k = A.node_off[a]; k < A.node_off[a + 1]; k++) {
+                    const int idx1 = A.node_idx[k];
+                    if (!take1(idx1)) continue;
+                    q1.push_back(idx1);
+                    Open(A.descriptors + (size_t)idx1 * 32);
+                    idx.insert(idx.end(), B.node_idx + B.node_off[b], B.node_idx + B.node_off[b + 1]);
+                }
+                a++;
+                b++;
+            } else if (A.node_ids[a] < B.node_ids[b]) {
+                while (a < A.n_nodes && A.node_ids[a] < B.node_ids[b]) a++;
+            } else {
+                while (b < B.n_nodes && B.node_ids[b] < A.node_ids[a]) b++;
+            }
+        }
+    }
+};
+
+namespace
 {
-    dist.resize(idx.size());
-    if (idx.empty()) return;
-    Check(amos_match_list_distances(Handle(), queries, nq, train, nt, off.data(), idx.data(), dist.data()), "amos_match_list_distances");
-}
+// The orientation check the six oriented searches end with (e.g. ORBmatcher.cc:1693-1725): every accepted match votes with its
+// angle difference, and the matches outside the three fullest bins are taken back.
+struct RotationHistogram {
+    vector<int> bins[AMOS_VIEW_MATCHER::HISTO_LENGTH];
+
+    RotationHistogram()
+    {
+        for (vector<int> &bin : bins) bin.reserve(500);
+    }
+    // slot: the entry of the search's match table that Prune() clears if this vote loses
+    void Add(float angleQuery, float angleTrain, int slot)
+    {
+        const float factor = AMOS_VIEW_MATCHER::HISTO_LENGTH / 360.0f;
+        float rot = angleQuery - angleTrain;
+        if (rot < 0.0) rot += 360.0f;
+        int bin = round(rot * factor);
+        if (bin == AMOS_VIEW_MATCHER::HISTO_LENGTH) bin = 0;
+        bins[bin].push_back(slot);
+    }
+    // Returns the number of matches to subtract: one per VOTE, not per slot -- a slot that was overwritten during the search and
+    // voted twice counts twice, which is the reference's accounting.  onlyIfSet: leave out votes whose slot is clear already.
+    int Prune(vector<int> &table, int freeValue, bool onlyIfSet = false)
+    {
+        int ind1 = -1, ind2 = -1, ind3 = -1;
+        AMOS_VIEW_MATCHER::ComputeThreeMaxima(bins, AMOS_VIEW_MATCHER::HISTO_LENGTH, ind1, ind2, ind3);
+        int removed = 0;
+        for (int i = 0; i < AMOS_VIEW_MATCHER::HISTO_LENGTH; i++) {
+            if (i == ind1 || i == ind2 || i == ind3) continue;
+            for (size_t j = 0, jend = bins[i].size(); j < jend; j++) {
+                const int slot = bins[i][j];
+                if (onlyIfSet && table[slot] < 0) continue;
+                table[slot] = freeValue;
+                removed++;
+            }
+        }
+        return removed;
+    }
+};
+}  // namespace
 
 float AMOS_VIEW_MATCHER::RadiusByViewingCos(const float &viewCos)
 {
@@ -190,77 +326,44 @@ int AMOS_VIEW_MATCHER::SearchByProjection(const FeatureGrid &CurrentFrame, const
 {
     const amos_frame_view &F = CurrentFrame.Frame();
     const int nq = (int)vLastPoints.size();
-    // 1. candidates of every query, in GetFeaturesInArea order (:1627-1637)
-    vector<int> off(nq + 1, 0), idx;
+    CandidateLists c(nq);  // in GetFeaturesInArea order (:1627-1637)
     vector<float> radius(nq);
-    vector<uint8_t> qdesc((size_t)nq * 32);
     for (int i = 0; i < nq; i++) {
         const amos_proj_query &p = vLastPoints[i];
-        memcpy(&qdesc[(size_t)i * 32], p.desc, 32);
         const int nLastOctave = p.octave;
         radius[i] = th * mvScaleFactors[nLastOctave];
-        vector<size_t> vIndices2;
+        c.Open(p.desc);
         if (bForward)
-            vIndices2 = CurrentFrame.GetFeaturesInArea(p.u, p.v, radius[i], nLastOctave);
+            CurrentFrame.AppendFeaturesInArea(c.idx, p.u, p.v, radius[i], nLastOctave);
         else if (bBackward)
-            vIndices2 = CurrentFrame.GetFeaturesInArea(p.u, p.v, radius[i], 0, nLastOctave);
+            CurrentFrame.AppendFeaturesInArea(c.idx, p.u, p.v, radius[i], 0, nLastOctave);
         else
-            vIndices2 = CurrentFrame.GetFeaturesInArea(p.u, p.v, radius[i], nLastOctave - 1, nLastOctave + 1);
-        for (size_t k = 0; k < vIndices2.size(); k++) idx.push_back((int)vIndices2[k]);
-        off[i + 1] = (int)idx.size();
+            CurrentFrame.AppendFeaturesInArea(c.idx, p.u, p.v, radius[i], nLastOctave - 1, nLastOctave + 1);
     }
-    // 2. all candidate distances in one GPU call
-    vector<uint16_t> dist;
-    ListDistances(F, qdesc.data(), nq, off, idx, dist);
-    // 3. the reference's greedy loop over the precomputed distances
+    c.Distances(*this, F.descriptors, F.n);
     int nmatches = 0;
-    vector<int> rotHist[HISTO_LENGTH];
-    for (int i = 0; i < HISTO_LENGTH; i++) rotHist[i].reserve(500);
-    const float factor = HISTO_LENGTH / 360.0f;
+    RotationHistogram rotHist;
     for (int i = 0; i < nq; i++) {
-        if (off[i] == off[i + 1]) continue;
+        if (c.Empty(i)) continue;
         const amos_proj_query &p = vLastPoints[i];
         int bestDist = 256;
-        int bestIdx2 = -1;
-        for (int k = off[i]; k < off[i + 1]; k++) {
-            const int i2 = idx[k];
+        const int bestIdx2 = c.Best(i, bestDist, [&](int i2, int) {
             if (vnCurMatch[i2] >= 0)
-                if (vLastPoints[vnCurMatch[i2]].has_obs) continue;  // :1658-1660
-            if (F.u_right && F.u_right[i2] > 0) {                    // :1662-1669
+                if (vLastPoints[vnCurMatch[i2]].has_obs) return true;  // :1658-1660
+            if (F.u_right && F.u_right[i2] > 0) {                       // :1662-1669
                 const float ur = p.u - mbf * p.invz;
                 const float er = fabs(ur - F.u_right[i2]);
-                if (er > radius[i]) continue;
+                if (er > radius[i]) return true;
             }
-            const int d = dist[k];
-            if (d < bestDist) {
-                bestDist = d;
-                bestIdx2 = i2;
-            }
-        }
+            return false;
+        });
         if (bestDist <= TH_HIGH) {
-            vnCurMatch[bestIdx2] = i;
+            vnCurMatch[bestIdx2] = i;  // may overwrite an occupant without observations, whose vote stays in the histogram
             nmatches++;
-            if (mbCheckOrientation) {
-                float rot = p.angle - F.keys_un[bestIdx2].angle;
-                if (rot < 0.0) rot += 360.0f;
-                int bin = round(rot * factor);
-                if (bin == HISTO_LENGTH) bin = 0;
-                rotHist[bin].push_back(bestIdx2);
-            }
+            if (mbCheckOrientation) rotHist.Add(p.angle, F.keys_un[bestIdx2].angle, bestIdx2);
         }
     }
-    if (mbCheckOrientation) {
-        int ind1 = -1, ind2 = -1, ind3 = -1;
-        ComputeThreeMaxima(rotHist, HISTO_LENGTH, ind1, ind2, ind3);
-        for (int i = 0; i < HISTO_LENGTH; i++) {
-            if (i != ind1 && i != ind2 && i != ind3) {
-                for (size_t j = 0, jend = rotHist[i].size(); j < jend; j++) {
-                    vnCurMatch[rotHist[i][j]] = -1;
-                    nmatches--;
-                }
-            }
-        }
-    }
+    if (mbCheckOrientation) nmatches -= rotHist.Prune(vnCurMatch, -1);
     return nmatches;
 }
 
@@ -271,50 +374,37 @@ int AMOS_VIEW_MATCHER::SearchByProjection(const FeatureGrid &Fg, const vector<am
     const amos_frame_view &F = Fg.Frame();
     const int nq = (int)vpMapPoints.size();
     const bool bFactor = th != 1.0;
-    vector<int> off(nq + 1, 0), idx;
+    CandidateLists c(nq);
     vector<float> rr(nq);
-    vector<uint8_t> qdesc((size_t)nq * 32);
     for (int iMP = 0; iMP < nq; iMP++) {
         const amos_map_query &mp = vpMapPoints[iMP];
-        memcpy(&qdesc[(size_t)iMP * 32], mp.desc, 32);
         const int nPredictedLevel = mp.level;
         float r = RadiusByViewingCos(mp.view_cos);
         if (bFactor) r *= th;
         rr[iMP] = r;
-        const vector<size_t> vIndices =
-            Fg.GetFeaturesInArea(mp.proj_x, mp.proj_y, r * mvScaleFactors[nPredictedLevel], nPredictedLevel - 1, nPredictedLevel);
-        for (size_t k = 0; k < vIndices.size(); k++) idx.push_back((int)vIndices[k]);
-        off[iMP + 1] = (int)idx.size();
+        c.Open(mp.desc);
+        Fg.AppendFeaturesInArea(c.idx, mp.proj_x, mp.proj_y, r * mvScaleFactors[nPredictedLevel], nPredictedLevel - 1, nPredictedLevel);
     }
-    vector<uint16_t> dist;
-    ListDistances(F, qdesc.data(), nq, off, idx, dist);
+    c.Distances(*this, F.descriptors, F.n);
     int nmatches = 0;
     for (int iMP = 0; iMP < nq; iMP++) {
-        if (off[iMP] == off[iMP + 1]) continue;
+        if (c.Empty(iMP)) continue;
         const amos_map_query &mp = vpMapPoints[iMP];
         const int nPredictedLevel = mp.level;
         const float r = rr[iMP];
-        int bestDist = 256, bestLevel = -1, bestDist2 = 256, bestLevel2 = -1, bestIdx = -1;
-        for (int k = off[iMP]; k < off[iMP + 1]; k++) {
-            const int i = idx[k];
-            if (vbCurHasObs[i]) continue;  // :121-123
-            if (F.u_right && F.u_right[i] > 0) {
-                const float er = fabs(mp.proj_xr - F.u_right[i]);
-                if (er > r * mvScaleFactors[nPredictedLevel]) continue;
-            }
-            const int d = dist[k];
-            if (d < bestDist) {
-                bestDist2 = bestDist;
-                bestDist = d;
-                bestLevel2 = bestLevel;
-                bestLevel = F.keys_un[i].octave;
-                bestIdx = i;
-            } else if (d < bestDist2) {
-                bestLevel2 = F.keys_un[i].octave;
-                bestDist2 = d;
-            }
-        }
+        int bestDist = 256, bestDist2 = 256, bestIdx2 = -1;
+        const int bestIdx = c.Best2(iMP, bestDist, bestDist2,
+                                    [&](int i, int) {
+                                        if (vbCurHasObs[i]) return true;  // :121-123
+                                        if (F.u_right && F.u_right[i] > 0) {
+                                            const float er = fabs(mp.proj_xr - F.u_right[i]);
+                                            if (er > r * mvScaleFactors[nPredictedLevel]) return true;
+                                        }
+                                        return false;
+                                    },
+                                    &bestIdx2);
         if (bestDist <= TH_HIGH) {
+            const int bestLevel = F.keys_un[bestIdx].octave, bestLevel2 = bestIdx2 >= 0 ? F.keys_un[bestIdx2].octave : -1;
             if (bestLevel == bestLevel2 && bestDist > mfNNratio * bestDist2) continue;  // :163-167
             vnCurMatch[bestIdx] = iMP;
             vbCurHasObs[bestIdx] = mp.has_obs != 0;
@@ -325,179 +415,61 @@ int AMOS_VIEW_MATCHER::SearchByProjection(const FeatureGrid &Fg, const vector<am
 }
 
 // ORBmatcher.cc:1731-1863 (relocalisation): window nPredictedLevel-1 .. +1, ANY occupied feature is skipped,
-// best only, accepted at bestDist <= ORBdist, rotation histogram pruning unconditional.
+// best only, accepted at bestDist <= ORBdist.
 int AMOS_VIEW_MATCHER::SearchByProjection(const FeatureGrid &CurrentFrame, const vector<amos_kf_query> &vKFPoints, vector<int> &vnCurMatch,
                                    const vector<float> &mvScaleFactors, const float th, const int ORBdist)
 {
     const amos_frame_view &F = CurrentFrame.Frame();
     const int nq = (int)vKFPoints.size();
-    vector<int> off(nq + 1, 0), idx;
-    vector<uint8_t> qdesc((size_t)nq * 32);
+    CandidateLists c(nq);
     for (int i = 0; i < nq; i++) {
         const amos_kf_query &p = vKFPoints[i];
-        memcpy(&qdesc[(size_t)i * 32], p.desc, 32);
         const int nPredictedLevel = p.level;
         const float radius = th * mvScaleFactors[nPredictedLevel];
-        const vector<size_t> vIndices2 = CurrentFrame.GetFeaturesInArea(p.u, p.v, radius, nPredictedLevel - 1, nPredictedLevel + 1);
-        for (size_t k = 0; k < vIndices2.size(); k++) idx.push_back((int)vIndices2[k]);
-        off[i + 1] = (int)idx.size();
+        c.Open(p.desc);
+        CurrentFrame.AppendFeaturesInArea(c.idx, p.u, p.v, radius, nPredictedLevel - 1, nPredictedLevel + 1);
     }
-    vector<uint16_t> dist;
-    ListDistances(F, qdesc.data(), nq, off, idx, dist);
+    c.Distances(*this, F.descriptors, F.n);
     int nmatches = 0;
-    vector<int> rotHist[HISTO_LENGTH];
-    for (int i = 0; i < HISTO_LENGTH; i++) rotHist[i].reserve(500);
-    const float factor = HISTO_LENGTH / 360.0f;
+    RotationHistogram rotHist;
     for (int i = 0; i < nq; i++) {
-        if (off[i] == off[i + 1]) continue;  // :1802-1803
+        if (c.Empty(i)) continue;  // :1802-1803
         int bestDist = 256;
-        int bestIdx2 = -1;
-        for (int k = off[i]; k < off[i + 1]; k++) {
-            const int i2 = idx[k];
-            if (vnCurMatch[i2] != AMOS_MATCH_FREE) continue;  // :1816-1817
-            const int d = dist[k];
-            if (d < bestDist) {
-                bestDist = d;
-                bestIdx2 = i2;
-            }
-        }
+        const int bestIdx2 = c.Best(i, bestDist, [&](int i2, int) { return vnCurMatch[i2] != AMOS_MATCH_FREE; });  // :1816-1817
         if (bestDist <= ORBdist) {
             vnCurMatch[bestIdx2] = i;
             nmatches++;
-            if (mbCheckOrientation) {
-                float rot = vKFPoints[i].angle - F.keys_un[bestIdx2].angle;
-                if (rot < 0.0) rot += 360.0f;
-                int bin = round(rot * factor);
-                if (bin == HISTO_LENGTH) bin = 0;
-                rotHist[bin].push_back(bestIdx2);
-            }
+            if (mbCheckOrientation) rotHist.Add(vKFPoints[i].angle, F.keys_un[bestIdx2].angle, bestIdx2);
         }
     }
-    if (mbCheckOrientation) {
-        int ind1 = -1, ind2 = -1, ind3 = -1;
-        ComputeThreeMaxima(rotHist, HISTO_LENGTH, ind1, ind2, ind3);
-        for (int i = 0; i < HISTO_LENGTH; i++) {
-            if (i != ind1 && i != ind2 && i != ind3) {
-                for (size_t j = 0, jend = rotHist[i].size(); j < jend; j++) {
-                    vnCurMatch[rotHist[i][j]] = AMOS_MATCH_FREE;
-                    nmatches--;
-                }
-            }
-        }
-    }
+    if (mbCheckOrientation) nmatches -= rotHist.Prune(vnCurMatch, AMOS_MATCH_FREE);
     return nmatches;
 }
 
-// ORBmatcher.cc:230-382.  Candidates of a keyframe feature = the frame's features in the same vocabulary node,
-// in the FeatureVector's order; the two-iterator merge over the ascending node ids is the reference's
-// (lower_bound on a std::map = first node id >= the other side's).
+// ORBmatcher.cc:230-382.  Candidates of a keyframe feature = the frame's features in the same vocabulary node.
 int AMOS_VIEW_MATCHER::SearchByBoW(const amos_bow_view &KF, const amos_bow_view &F, vector<int> &vnMatchesF)
 {
     vnMatchesF.assign(F.n, -1);
-    // 1. candidate lists, in the order the reference visits the keyframe features
-    vector<int> qKF, off(1, 0), idx;
-    {
-        int a = 0, b = 0;
-        while (a < KF.n_nodes && b < F.n_nodes) {
-            if (KF.node_ids[a] == F.node_ids[b]) {
-                for (int k = KF.node_off[a]; k < KF.node_off[a + 1]; k++) {
-                    const int realIdxKF = KF.node_idx[k];
-                    if (KF.has_point && !KF.has_point[realIdxKF]) continue;  // !pMP || pMP->isBad()
-                    qKF.push_back(realIdxKF);
-                    for (int m = F.node_off[b]; m < F.node_off[b + 1]; m++) idx.push_back(F.node_idx[m]);
-                    off.push_back((int)idx.size());
-                }
-                a++;
-                b++;
-            } else if (KF.node_ids[a] < F.node_ids[b]) {
-                while (a < KF.n_nodes && KF.node_ids[a] < F.node_ids[b]) a++;  // lower_bound(Fit->first)
-            } else {
-                while (b < F.n_nodes && F.node_ids[b] < KF.node_ids[a]) b++;
-            }
-        }
-    }
-    const int nq = (int)qKF.size();
-    vector<uint8_t> qdesc((size_t)nq * 32);
-    for (int i = 0; i < nq; i++) memcpy(&qdesc[(size_t)i * 32], KF.descriptors + (size_t)qKF[i] * 32, 32);
-    // 2. all candidate distances in one GPU call
-    vector<uint16_t> dist;
-    ListDistances(F.descriptors, F.n, qdesc.data(), nq, off, idx, dist);
-    // 3. the reference's greedy loop
+    vector<int> qKF;
+    CandidateLists c;
+    c.OpenSharedNodes(KF, F, [&](int iKF) { return !KF.has_point || KF.has_point[iKF]; }, qKF);  // pMP && !pMP->isBad()
+    c.Distances(*this, F.descriptors, F.n);
     int nmatches = 0;
-    vector<int> rotHist[HISTO_LENGTH];
-    for (int i = 0; i < HISTO_LENGTH; i++) rotHist[i].reserve(500);
-    const float factor = HISTO_LENGTH / 360.0f;
-    for (int i = 0; i < nq; i++) {
+    RotationHistogram rotHist;
+    for (int i = 0, nq = (int)qKF.size(); i < nq; i++) {
         const int realIdxKF = qKF[i];
-        int bestDist1 = 256;
-        int bestIdxF = -1;
-        int bestDist2 = 256;
-        for (int k = off[i]; k < off[i + 1]; k++) {
-            const int realIdxF = idx[k];
-            if (vnMatchesF[realIdxF] >= 0) continue;  // :288-289
-            const int d = dist[k];
-            if (d < bestDist1) {
-                bestDist2 = bestDist1;
-                bestDist1 = d;
-                bestIdxF = realIdxF;
-            } else if (d < bestDist2) {
-                bestDist2 = d;
-            }
-        }
+        int bestDist1 = 256, bestDist2 = 256;
+        const int bestIdxF = c.Best2(i, bestDist1, bestDist2, [&](int realIdxF, int) { return vnMatchesF[realIdxF] >= 0; });  // :288-289
         if (bestDist1 <= TH_LOW) {
             if (static_cast<float>(bestDist1) < mfNNratio * static_cast<float>(bestDist2)) {
                 vnMatchesF[bestIdxF] = realIdxKF;
-                if (mbCheckOrientation) {
-                    float rot = KF.keys[realIdxKF].angle - F.keys[bestIdxF].angle;
-                    if (rot < 0.0) rot += 360.0f;
-                    int bin = round(rot * factor);
-                    if (bin == HISTO_LENGTH) bin = 0;
-                    rotHist[bin].push_back(bestIdxF);
-                }
+                if (mbCheckOrientation) rotHist.Add(KF.keys[realIdxKF].angle, F.keys[bestIdxF].angle, bestIdxF);
                 nmatches++;
             }
         }
     }
-    if (mbCheckOrientation) {
-        int ind1 = -1, ind2 = -1, ind3 = -1;
-        ComputeThreeMaxima(rotHist, HISTO_LENGTH, ind1, ind2, ind3);
-        for (int i = 0; i < HISTO_LENGTH; i++) {
-            if (i == ind1 || i == ind2 || i == ind3) continue;
-            for (size_t j = 0, jend = rotHist[i].size(); j < jend; j++) {
-                vnMatchesF[rotHist[i][j]] = -1;
-                nmatches--;
-            }
-        }
-    }
+    if (mbCheckOrientation) nmatches -= rotHist.Prune(vnMatchesF, -1);
     return nmatches;
-}
-
-// Candidate lists of a node-by-node search between two feature vectors (the merge of :673-760 / :835-935):
-// for every feature of side 1 that `take1` accepts, the features of side 2 in the same node, in list order.
-template <typename Take1>
-static void BowCandidates(const amos_bow_view &A, const amos_bow_view &B, Take1 take1, vector<int> &q1, vector<int> &off, vector<int> &idx)
-{
-    q1.clear();
-    idx.clear();
-    off.assign(1, 0);
-    int a = 0, b = 0;
-    while (a < A.n_nodes && b < B.n_nodes) {
-        if (A.node_ids[a] == B.node_ids[b]) {
-            for (int k = A.node_off[a]; k < A.node_off[a + 1]; k++) {
-                const int idx1 = A.node_idx[k];
-                if (!take1(idx1)) continue;
-                q1.push_back(idx1);
-                for (int m = B.node_off[b]; m < B.node_off[b + 1]; m++) idx.push_back(B.node_idx[m]);
-                off.push_back((int)idx.size());
-            }
-            a++;
-            b++;
-        } else if (A.node_ids[a] < B.node_ids[b]) {
-            while (a < A.n_nodes && A.node_ids[a] < B.node_ids[b]) a++;
-        } else {
-            while (b < B.n_nodes && B.node_ids[b] < A.node_ids[a]) b++;
-        }
-    }
 }
 
 // ORBmatcher.cc:656-808
@@ -506,60 +478,27 @@ int AMOS_VIEW_MATCHER::SearchByBoW(const amos_bow_view &KF1, const amos_bow_view
     if (!bBothKeyFrames) return SearchByBoW(KF1, KF2, vnMatches12);
     vnMatches12.assign(KF1.n, -1);
     vector<bool> vbMatched2(KF2.n, false);
-    vector<int> q1, off, idx;
-    BowCandidates(KF1, KF2, [&](int i1) { return !KF1.has_point || KF1.has_point[i1]; }, q1, off, idx);
-    const int nq = (int)q1.size();
-    vector<uint8_t> qdesc((size_t)nq * 32);
-    for (int i = 0; i < nq; i++) memcpy(&qdesc[(size_t)i * 32], KF1.descriptors + (size_t)q1[i] * 32, 32);
-    vector<uint16_t> dist;
-    ListDistances(KF2.descriptors, KF2.n, qdesc.data(), nq, off, idx, dist);
-    vector<int> rotHist[HISTO_LENGTH];
-    for (int i = 0; i < HISTO_LENGTH; i++) rotHist[i].reserve(500);
-    const float factor = HISTO_LENGTH / 360.0f;
+    vector<int> q1;
+    CandidateLists c;
+    c.OpenSharedNodes(KF1, KF2, [&](int i1) { return !KF1.has_point || KF1.has_point[i1]; }, q1);
+    c.Distances(*this, KF2.descriptors, KF2.n);
+    RotationHistogram rotHist;
     int nmatches = 0;
-    for (int i = 0; i < nq; i++) {
+    for (int i = 0, nq = (int)q1.size(); i < nq; i++) {
         const int idx1 = q1[i];
-        int bestDist1 = 256;
-        int bestIdx2 = -1;
-        int bestDist2 = 256;
-        for (int k = off[i]; k < off[i + 1]; k++) {
-            const int idx2 = idx[k];
-            if (vbMatched2[idx2] || (KF2.has_point && !KF2.has_point[idx2])) continue;  // :704-708
-            const int d = dist[k];
-            if (d < bestDist1) {
-                bestDist2 = bestDist1;
-                bestDist1 = d;
-                bestIdx2 = idx2;
-            } else if (d < bestDist2) {
-                bestDist2 = d;
-            }
-        }
+        int bestDist1 = 256, bestDist2 = 256;
+        const int bestIdx2 = c.Best2(i, bestDist1, bestDist2,
+                                     [&](int idx2, int) { return vbMatched2[idx2] || (KF2.has_point && !KF2.has_point[idx2]); });  // :704-708
         if (bestDist1 < TH_LOW) {  // strict here, <= in SearchByBoW(KF, F)
             if (static_cast<float>(bestDist1) < mfNNratio * static_cast<float>(bestDist2)) {
                 vnMatches12[idx1] = bestIdx2;
                 vbMatched2[bestIdx2] = true;
-                if (mbCheckOrientation) {
-                    float rot = KF1.keys[idx1].angle - KF2.keys[bestIdx2].angle;
-                    if (rot < 0.0) rot += 360.0f;
-                    int bin = round(rot * factor);
-                    if (bin == HISTO_LENGTH) bin = 0;
-                    rotHist[bin].push_back(idx1);
-                }
+                if (mbCheckOrientation) rotHist.Add(KF1.keys[idx1].angle, KF2.keys[bestIdx2].angle, idx1);
                 nmatches++;
             }
         }
     }
-    if (mbCheckOrientation) {
-        int ind1 = -1, ind2 = -1, ind3 = -1;
-        ComputeThreeMaxima(rotHist, HISTO_LENGTH, ind1, ind2, ind3);
-        for (int i = 0; i < HISTO_LENGTH; i++) {
-            if (i == ind1 || i == ind2 || i == ind3) continue;
-            for (size_t j = 0, jend = rotHist[i].size(); j < jend; j++) {
-                vnMatches12[rotHist[i][j]] = -1;
-                nmatches--;
-            }
-        }
-    }
+    if (mbCheckOrientation) nmatches -= rotHist.Prune(vnMatches12, -1);
     return nmatches;
 }
 
@@ -582,38 +521,34 @@ int AMOS_VIEW_MATCHER::SearchForTriangulation(const amos_bow_view &KF1, const am
                                        vector<pair<size_t, size_t> > &vMatchedPairs, const bool bOnlyStereo)
 {
     auto stereo = [](const amos_bow_view &v, int i) { return v.u_right ? v.u_right[i] >= 0 : false; };
-    vector<int> q1, off, idx;
-    BowCandidates(KF1, KF2,
-                  [&](int i1) {
-                      if (KF1.has_point && KF1.has_point[i1]) return false;  // pMP1 exists: nothing to triangulate (:846-849)
-                      if (bOnlyStereo && !stereo(KF1, i1)) return false;
-                      return true;
-                  },
-                  q1, off, idx);
-    const int nq = (int)q1.size();
-    vector<uint8_t> qdesc((size_t)nq * 32);
-    for (int i = 0; i < nq; i++) memcpy(&qdesc[(size_t)i * 32], KF1.descriptors + (size_t)q1[i] * 32, 32);
-    vector<uint16_t> dist;
-    ListDistances(KF2.descriptors, KF2.n, qdesc.data(), nq, off, idx, dist);
+    vector<int> q1;
+    CandidateLists c;
+    c.OpenSharedNodes(KF1, KF2,
+                      [&](int i1) {
+                          if (KF1.has_point && KF1.has_point[i1]) return false;  // pMP1 exists: nothing to triangulate (:846-849)
+                          if (bOnlyStereo && !stereo(KF1, i1)) return false;
+                          return true;
+                      },
+                      q1);
+    c.Distances(*this, KF2.descriptors, KF2.n);
     int nmatches = 0;
     vector<bool> vbMatched2(KF2.n, false);
     vector<int> vMatches12(KF1.n, -1);
-    vector<int> rotHist[HISTO_LENGTH];
-    for (int i = 0; i < HISTO_LENGTH; i++) rotHist[i].reserve(500);
-    const float factor = HISTO_LENGTH / 360.0f;
-    for (int i = 0; i < nq; i++) {
+    RotationHistogram rotHist;
+    for (int i = 0, nq = (int)q1.size(); i < nq; i++) {
         const int idx1 = q1[i];
         const bool bStereo1 = stereo(KF1, idx1);
         const amos_keypoint &kp1 = KF1.keys[idx1];
+        // Not an argmin: a later candidate of EQUAL distance that passes the geometric tests replaces an earlier one (d > bestDist skips).
         int bestDist = TH_LOW;
         int bestIdx2 = -1;
-        for (int k = off[i]; k < off[i + 1]; k++) {
-            const int idx2 = idx[k];
+        for (int k = c.off[i]; k < c.off[i + 1]; k++) {
+            const int idx2 = c.idx[k];
             if (vbMatched2[idx2] || (KF2.has_point && KF2.has_point[idx2])) continue;  // :866-869
             const bool bStereo2 = stereo(KF2, idx2);
             if (bOnlyStereo)
                 if (!bStereo2) continue;
-            const int d = dist[k];
+            const int d = c.dist[k];
             if (d > TH_LOW || d > bestDist) continue;
             const amos_keypoint &kp2 = KF2.keys[idx2];
             if (!bStereo1 && !bStereo2) {
@@ -627,30 +562,13 @@ int AMOS_VIEW_MATCHER::SearchForTriangulation(const amos_bow_view &KF1, const am
             }
         }
         if (bestIdx2 >= 0) {
-            const amos_keypoint &kp2 = KF2.keys[bestIdx2];
             vMatches12[idx1] = bestIdx2;
             vbMatched2[bestIdx2] = true;
             nmatches++;
-            if (mbCheckOrientation) {
-                float rot = kp1.angle - kp2.angle;
-                if (rot < 0.0) rot += 360.0f;
-                int bin = round(rot * factor);
-                if (bin == HISTO_LENGTH) bin = 0;
-                rotHist[bin].push_back(idx1);
-            }
+            if (mbCheckOrientation) rotHist.Add(kp1.angle, KF2.keys[bestIdx2].angle, idx1);
         }
     }
-    if (mbCheckOrientation) {
-        int ind1 = -1, ind2 = -1, ind3 = -1;
-        ComputeThreeMaxima(rotHist, HISTO_LENGTH, ind1, ind2, ind3);
-        for (int i = 0; i < HISTO_LENGTH; i++) {
-            if (i == ind1 || i == ind2 || i == ind3) continue;
-            for (size_t j = 0, jend = rotHist[i].size(); j < jend; j++) {
-                vMatches12[rotHist[i][j]] = -1;
-                nmatches--;
-            }
-        }
-    }
+    if (mbCheckOrientation) nmatches -= rotHist.Prune(vMatches12, -1);
     vMatchedPairs.clear();
     vMatchedPairs.reserve(nmatches);
     for (size_t i = 0, iend = vMatches12.size(); i < iend; i++) {
@@ -660,25 +578,24 @@ int AMOS_VIEW_MATCHER::SearchForTriangulation(const amos_bow_view &KF1, const am
     return nmatches;
 }
 
-// The candidate loop shared by Fuse (:1086-1127, :1252-1272), SearchByProjection(pKF, Scw, ...) (:466-494) and
-// SearchBySim3 (:1396-1420, :1476-1500): KeyFrame::GetFeaturesInArea(u, v, radius) has no level filter; the level
-// gate  kpLevel < nPredictedLevel-1 || kpLevel > nPredictedLevel  and Fuse's reprojection gate follow per candidate.
+// The candidates shared by Fuse (:1086-1127, :1252-1272), SearchByProjection(pKF, Scw, ...) (:466-494) and SearchBySim3
+// (:1396-1420, :1476-1500): KeyFrame::GetFeaturesInArea(u, v, th * scale) has no level filter; the level gate
+// kpLevel < nPredictedLevel-1 || kpLevel > nPredictedLevel  and, when mvInvLevelSigma2 is given, Fuse's chi2 gate on the
+// reprojection error follow per candidate.
 void AMOS_VIEW_MATCHER::WindowCandidates(const FeatureGrid &KF, const vector<amos_window_query> &q, const vector<float> &mvScaleFactors, const float th,
-                                  const vector<float> *mvInvLevelSigma2, vector<int> &off, vector<int> &idx, vector<uint16_t> &dist)
+                                  const vector<float> *mvInvLevelSigma2, CandidateLists &c)
 {
     const amos_frame_view &F = KF.Frame();
-    const int nq = (int)q.size();
-    off.assign(nq + 1, 0);
-    idx.clear();
-    vector<uint8_t> qdesc((size_t)nq * 32);
-    for (int i = 0; i < nq; i++) {
+    for (size_t i = 0; i < q.size(); i++) {
         const amos_window_query &p = q[i];
-        memcpy(&qdesc[(size_t)i * 32], p.desc, 32);
         const int nPredictedLevel = p.level;
         const float radius = th * mvScaleFactors[nPredictedLevel];
-        const vector<size_t> vIndices = KF.GetFeaturesInArea(p.u, p.v, radius);
-        for (size_t k = 0; k < vIndices.size(); k++) {
-            const size_t i2 = vIndices[k];
+        c.Open(p.desc);
+        const size_t first = c.idx.size();
+        KF.AppendFeaturesInArea(c.idx, p.u, p.v, radius);
+        size_t kept = first;  // the gates below compact the window's features in place
+        for (size_t k = first; k < c.idx.size(); k++) {
+            const int i2 = c.idx[k];
             const amos_keypoint &kp = F.keys_un[i2];
             const int kpLevel = kp.octave;
             if (kpLevel < nPredictedLevel - 1 || kpLevel > nPredictedLevel) continue;
@@ -696,83 +613,56 @@ void AMOS_VIEW_MATCHER::WindowCandidates(const FeatureGrid &KF, const vector<amo
                     if (e2 * (*mvInvLevelSigma2)[kpLevel] > 5.99) continue;
                 }
             }
-            idx.push_back((int)i2);
+            c.idx[kept++] = i2;
         }
-        off[i + 1] = (int)idx.size();
+        c.idx.resize(kept);
     }
-    ListDistances(F, qdesc.data(), nq, off, idx, dist);
+    c.Distances(*this, F.descriptors, F.n);
 }
 
-static int BestOfList(const vector<int> &off, const vector<int> &idx, const vector<uint16_t> &dist, int i, int &bestDist)
+// vnBestIdx[i] = the nearest window candidate of query i if its distance is <= maxDist, else -1; returns how many were found
+int AMOS_VIEW_MATCHER::BestInWindow(const FeatureGrid &KF, const vector<amos_window_query> &q, const vector<float> &mvScaleFactors, const float th,
+                             const vector<float> *mvInvLevelSigma2, const int maxDist, vector<int> &vnBestIdx)
 {
-    bestDist = 256;
-    int bestIdx = -1;
-    for (int k = off[i]; k < off[i + 1]; k++)
-        if (dist[k] < bestDist) {
-            bestDist = dist[k];
-            bestIdx = idx[k];
+    CandidateLists c((int)q.size());
+    WindowCandidates(KF, q, mvScaleFactors, th, mvInvLevelSigma2, c);
+    int nFound = 0;
+    vnBestIdx.assign(q.size(), -1);
+    for (int i = 0; i < (int)q.size(); i++) {
+        int bestDist = 256;
+        const int bestIdx = c.Best(i, bestDist);
+        if (bestDist <= maxDist) {
+            vnBestIdx[i] = bestIdx;
+            nFound++;
         }
-    return bestIdx;
+    }
+    return nFound;
 }
 
 // ORBmatcher.cc:1020-1177
 int AMOS_VIEW_MATCHER::Fuse(const FeatureGrid &KF, const vector<amos_window_query> &vpMapPoints, const vector<float> &mvScaleFactors,
                      const vector<float> &mvInvLevelSigma2, const float th, vector<int> &vnBestIdx)
 {
-    vector<int> off, idx;
-    vector<uint16_t> dist;
-    WindowCandidates(KF, vpMapPoints, mvScaleFactors, th, &mvInvLevelSigma2, off, idx, dist);
-    int nFused = 0;
-    vnBestIdx.assign(vpMapPoints.size(), -1);
-    for (int i = 0; i < (int)vpMapPoints.size(); i++) {
-        int bestDist;
-        const int bestIdx = BestOfList(off, idx, dist, i, bestDist);
-        if (bestDist <= TH_LOW) {
-            vnBestIdx[i] = bestIdx;
-            nFused++;
-        }
-    }
-    return nFused;
+    return BestInWindow(KF, vpMapPoints, mvScaleFactors, th, &mvInvLevelSigma2, TH_LOW, vnBestIdx);
 }
 
 // ORBmatcher.cc:1179-1312
 int AMOS_VIEW_MATCHER::Fuse(const FeatureGrid &KF, const vector<amos_window_query> &vpPoints, const vector<float> &mvScaleFactors, const float th,
                      vector<int> &vnBestIdx)
 {
-    vector<int> off, idx;
-    vector<uint16_t> dist;
-    WindowCandidates(KF, vpPoints, mvScaleFactors, th, nullptr, off, idx, dist);
-    int nFused = 0;
-    vnBestIdx.assign(vpPoints.size(), -1);
-    for (int i = 0; i < (int)vpPoints.size(); i++) {
-        int bestDist;
-        const int bestIdx = BestOfList(off, idx, dist, i, bestDist);
-        if (bestDist <= TH_LOW) {
-            vnBestIdx[i] = bestIdx;
-            nFused++;
-        }
-    }
-    return nFused;
+    return BestInWindow(KF, vpPoints, mvScaleFactors, th, nullptr, TH_LOW, vnBestIdx);
 }
 
 // ORBmatcher.cc:388-512
 int AMOS_VIEW_MATCHER::SearchByProjection(const FeatureGrid &KF, const vector<amos_window_query> &vpPoints, vector<int> &vnMatched,
                                    const vector<float> &mvScaleFactors, const int th)
 {
-    vector<int> off, idx;
-    vector<uint16_t> dist;
-    WindowCandidates(KF, vpPoints, mvScaleFactors, (float)th, nullptr, off, idx, dist);
+    CandidateLists c((int)vpPoints.size());
+    WindowCandidates(KF, vpPoints, mvScaleFactors, (float)th, nullptr, c);
     int nmatches = 0;
     for (int i = 0; i < (int)vpPoints.size(); i++) {
         int bestDist = 256;
-        int bestIdx = -1;
-        for (int k = off[i]; k < off[i + 1]; k++) {
-            if (vnMatched[idx[k]] != AMOS_MATCH_FREE) continue;  // :470-471
-            if (dist[k] < bestDist) {
-                bestDist = dist[k];
-                bestIdx = idx[k];
-            }
-        }
+        const int bestIdx = c.Best(i, bestDist, [&](int idx, int) { return vnMatched[idx] != AMOS_MATCH_FREE; });  // :470-471
         if (bestDist <= TH_LOW) {
             vnMatched[bestIdx] = i;
             nmatches++;
@@ -787,21 +677,13 @@ int AMOS_VIEW_MATCHER::SearchBySim3(const FeatureGrid &KF1, const FeatureGrid &K
                              vector<int> &vnMatches12, const float th)
 {
     const int N1 = KF1.Frame().n, N2 = KF2.Frame().n;
-    vector<int> vnMatch1(N1, -1), vnMatch2(N2, -1);
-    vector<int> off, idx;
-    vector<uint16_t> dist;
-    WindowCandidates(KF2, v1in2, mvScaleFactors2, th, nullptr, off, idx, dist);  // KF1's points searched in KF2
-    for (int i = 0; i < (int)v1in2.size(); i++) {
-        int bestDist;
-        const int bestIdx = BestOfList(off, idx, dist, i, bestDist);
-        if (bestDist <= TH_HIGH) vnMatch1[v1in2[i].src] = bestIdx;
-    }
-    WindowCandidates(KF1, v2in1, mvScaleFactors1, th, nullptr, off, idx, dist);  // KF2's points searched in KF1
-    for (int i = 0; i < (int)v2in1.size(); i++) {
-        int bestDist;
-        const int bestIdx = BestOfList(off, idx, dist, i, bestDist);
-        if (bestDist <= TH_HIGH) vnMatch2[v2in1[i].src] = bestIdx;
-    }
+    vector<int> vnMatch1(N1, -1), vnMatch2(N2, -1), vnBestIdx;
+    BestInWindow(KF2, v1in2, mvScaleFactors2, th, nullptr, TH_HIGH, vnBestIdx);  // KF1's points searched in KF2
+    for (size_t i = 0; i < v1in2.size(); i++)
+        if (vnBestIdx[i] >= 0) vnMatch1[v1in2[i].src] = vnBestIdx[i];
+    BestInWindow(KF1, v2in1, mvScaleFactors1, th, nullptr, TH_HIGH, vnBestIdx);  // KF2's points searched in KF1
+    for (size_t i = 0; i < v2in1.size(); i++)
+        if (vnBestIdx[i] >= 0) vnMatch2[v2in1[i].src] = vnBestIdx[i];
     vnMatches12.assign(N1, -1);
     int nFound = 0;
     for (int i1 = 0; i1 < N1; i1++) {  // :1540-1556: keep what both directions agree on
@@ -824,42 +706,25 @@ int AMOS_VIEW_MATCHER::SearchForInitialization(const amos_frame_view &F1, const 
     const amos_frame_view &F2 = F2g.Frame();
     int nmatches = 0;
     vnMatches12 = vector<int>(F1.n, -1);
-    vector<int> rotHist[HISTO_LENGTH];
-    for (int i = 0; i < HISTO_LENGTH; i++) rotHist[i].reserve(500);
-    const float factor = HISTO_LENGTH / 360.0f;
     vector<int> vMatchedDistance(F2.n, INT_MAX);
     vector<int> vnMatches21(F2.n, -1);
-    // candidates (level 0 features of F1 only, :540-552) and their distances
-    vector<int> off(F1.n + 1, 0), idx;
+    // every feature of F1 is a query, so F1.descriptors serves as the query block; only level 0 features get candidates (:540-552)
+    CandidateLists c;
     for (int i1 = 0; i1 < F1.n; i1++) {
         const int level1 = F1.keys_un[i1].octave;
-        if (level1 <= 0) {
-            vector<size_t> vIndices2 = F2g.GetFeaturesInArea(vbPrevMatched[i1].x, vbPrevMatched[i1].y, windowSize, level1, level1);
-            for (size_t k = 0; k < vIndices2.size(); k++) idx.push_back((int)vIndices2[k]);
-        }
-        off[i1 + 1] = (int)idx.size();
+        c.Open();
+        if (level1 <= 0) F2g.AppendFeaturesInArea(c.idx, vbPrevMatched[i1].x, vbPrevMatched[i1].y, windowSize, level1, level1);
     }
-    vector<uint16_t> dist;
-    ListDistances(F2, F1.descriptors, F1.n, off, idx, dist);
+    c.Distances(*this, F2.descriptors, F2.n, F1.descriptors);
+    RotationHistogram rotHist;
     for (int i1 = 0; i1 < F1.n; i1++) {
         if (F1.keys_un[i1].octave > 0) continue;
-        if (off[i1] == off[i1 + 1]) continue;
-        int bestDist = INT_MAX, bestDist2 = INT_MAX, bestIdx2 = -1;
-        for (int k = off[i1]; k < off[i1 + 1]; k++) {
-            const int i2 = idx[k];
-            const int d = dist[k];
-            if (vMatchedDistance[i2] <= d) continue;
-            if (d < bestDist) {
-                bestDist2 = bestDist;
-                bestDist = d;
-                bestIdx2 = i2;
-            } else if (d < bestDist2) {
-                bestDist2 = d;
-            }
-        }
+        if (c.Empty(i1)) continue;
+        int bestDist = INT_MAX, bestDist2 = INT_MAX;
+        const int bestIdx2 = c.Best2(i1, bestDist, bestDist2, [&](int i2, int d) { return vMatchedDistance[i2] <= d; });  // :554-555
         if (bestDist <= TH_LOW) {
             if (bestDist < (float)bestDist2 * mfNNratio) {
-                if (vnMatches21[bestIdx2] >= 0) {
+                if (vnMatches21[bestIdx2] >= 0) {  // displaces the earlier match of bestIdx2, whose vote stays in the histogram
                     vnMatches12[vnMatches21[bestIdx2]] = -1;
                     nmatches--;
                 }
@@ -867,30 +732,11 @@ int AMOS_VIEW_MATCHER::SearchForInitialization(const amos_frame_view &F1, const 
                 vnMatches21[bestIdx2] = i1;
                 vMatchedDistance[bestIdx2] = bestDist;
                 nmatches++;
-                if (mbCheckOrientation) {
-                    float rot = F1.keys_un[i1].angle - F2.keys_un[bestIdx2].angle;
-                    if (rot < 0.0) rot += 360.0f;
-                    int bin = round(rot * factor);
-                    if (bin == HISTO_LENGTH) bin = 0;
-                    rotHist[bin].push_back(i1);
-                }
+                if (mbCheckOrientation) rotHist.Add(F1.keys_un[i1].angle, F2.keys_un[bestIdx2].angle, i1);
             }
         }
     }
-    if (mbCheckOrientation) {
-        int ind1 = -1, ind2 = -1, ind3 = -1;
-        ComputeThreeMaxima(rotHist, HISTO_LENGTH, ind1, ind2, ind3);
-        for (int i = 0; i < HISTO_LENGTH; i++) {
-            if (i == ind1 || i == ind2 || i == ind3) continue;
-            for (size_t j = 0, jend = rotHist[i].size(); j < jend; j++) {
-                int idx1 = rotHist[i][j];
-                if (vnMatches12[idx1] >= 0) {
-                    vnMatches12[idx1] = -1;
-                    nmatches--;
-                }
-            }
-        }
-    }
+    if (mbCheckOrientation) nmatches -= rotHist.Prune(vnMatches12, -1, /*onlyIfSet=*/true);
     for (size_t i1 = 0, iend1 = vnMatches12.size(); i1 < iend1; i1++)
         if (vnMatches12[i1] >= 0) {
             vbPrevMatched[i1].x = F2.keys_un[vnMatches12[i1]].x;

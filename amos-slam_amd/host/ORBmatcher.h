@@ -2,11 +2,11 @@
 // constructor, DescriptorDistance and ComputeThreeMaxima (include/ORBmatcher.h:57-215), and the
 // gated searches of the tracking thread restated over plain frame views (include/amos_host_types.h).
 //
-// Structure of every search: the host enumerates each query's candidates exactly as the reference
-// does (Frame::GetFeaturesInArea order), ONE call computes all candidate distances on the GPU
-// (amos_match_list_distances), and the reference's sequential greedy loop -- "already matched"
-// skips, right-coordinate gate, best / second best, thresholds, rotation histogram -- then runs on
-// the host over those distances in the reference's order, so tie-breaks are identical.
+// Structure of every search: the host enumerates each query's candidates in the reference's order,
+// ONE call computes all candidate distances on the GPU (amos_match_list_distances), and the
+// reference's sequential greedy loop runs on the host over those distances, so tie-breaks are
+// identical.  ORBmatcher.cc writes the shared steps once (candidate lists with their best /
+// second-best scans, rotation histogram); a search spells out its skip and accept rules only.
 #ifndef ORBMATCHER_H
 #define ORBMATCHER_H
 
@@ -29,6 +29,9 @@ public:
     explicit FeatureGrid(const amos_frame_view &frame);
     std::vector<size_t> GetFeaturesInArea(const float &x, const float &y, const float &r, const int minLevel = -1,
                                           const int maxLevel = -1) const;
+    // the same indices in the same order, appended to vIndices
+    void AppendFeaturesInArea(std::vector<int> &vIndices, const float &x, const float &y, const float &r, const int minLevel = -1,
+                              const int maxLevel = -1) const;
     const amos_frame_view &Frame() const { return mFrame; }
 
 private:
@@ -54,8 +57,8 @@ public:
     AMOS_VIEW_MATCHER(const AMOS_VIEW_MATCHER &) = delete;
     AMOS_VIEW_MATCHER &operator=(const AMOS_VIEW_MATCHER &) = delete;
 
-    // ORBmatcher.cc:1913: one pair.  (Batches go through DescriptorDistances; a single pair still
-    // runs on the device so that there is one implementation of the distance.)
+    // ORBmatcher.cc:1913: one pair, eight popcounts on the host (callers use it inside host loops).
+    // Batches go through DescriptorDistances and the searches, on the device.
     static int DescriptorDistance(const cv::Mat &a, const cv::Mat &b);
     // all pairs: out[i * nt + j]
     void DescriptorDistances(const uint8_t *q, int nq, const uint8_t *t, int nt, std::vector<uint16_t> &out);
@@ -128,15 +131,14 @@ public:
 
 protected:
     float RadiusByViewingCos(const float &viewCos);
+    struct CandidateLists;  // ORBmatcher.cc
     // candidates of every query in pKF->GetFeaturesInArea(u, v, th * scale) order that pass the level gate (and the chi2
     // gate when mvInvLevelSigma2 is given), with their distances (one GPU call)
     void WindowCandidates(const FeatureGrid &KF, const std::vector<amos_window_query> &q, const std::vector<float> &mvScaleFactors,
-                          const float th, const std::vector<float> *mvInvLevelSigma2, std::vector<int> &off, std::vector<int> &idx,
-                          std::vector<uint16_t> &dist);
-    void ListDistances(const amos_frame_view &train, const uint8_t *queries, int nq, const std::vector<int> &off, const std::vector<int> &idx,
-                       std::vector<uint16_t> &dist);
-    void ListDistances(const uint8_t *train, int nt, const uint8_t *queries, int nq, const std::vector<int> &off, const std::vector<int> &idx,
-                       std::vector<uint16_t> &dist);
+                          const float th, const std::vector<float> *mvInvLevelSigma2, CandidateLists &c);
+    // the nearest of those per query, accepted at <= maxDist: both Fuse searches and each direction of SearchBySim3
+    int BestInWindow(const FeatureGrid &KF, const std::vector<amos_window_query> &q, const std::vector<float> &mvScaleFactors, const float th,
+                     const std::vector<float> *mvInvLevelSigma2, const int maxDist, std::vector<int> &vnBestIdx);
 
     // the device handle of this object: borrowed from the process-wide pool on first use (ORBmatcher.cc), returned by the destructor
     amos_match *Handle();

@@ -93,10 +93,19 @@ def test_features_in_area(hb, ob, synth):
             assert set(inside.tolist()) >= set(got.tolist())
 
 
-@pytest.mark.parametrize("forward,backward", [(0, 0), (1, 0), (0, 1)])
-def test_search_by_projection_frame(hb, ob, synth, forward, backward):
+def _pruning_is_live(with_ori, without_ori):
+    """The oracle's own two results (count first): the orientation check took at least one match back in this scene."""
+    assert without_ori[0] > with_ori[0] and not np.array_equal(with_ori[1], without_ori[1])
+
+
+@pytest.mark.parametrize("forward,backward,check_ori", [
+    pytest.param(0, 0, True, id="0-0"), pytest.param(1, 0, True, id="1-0"), pytest.param(0, 1, True, id="0-1"),
+    pytest.param(0, 0, False, id="0-0-no_ori"), pytest.param(1, 0, False, id="1-0-no_ori"), pytest.param(0, 1, False, id="0-1-no_ori")])
+def test_search_by_projection_frame(hb, ob, synth, forward, backward, check_ori):
     """ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) incl. the greedy
-    already-matched skip, right-coordinate gate and rotation histogram."""
+    already-matched skip, right-coordinate gate and rotation histogram.  With the histogram, th = 15 holds the
+    reference's double decrement: a feature whose occupant without observations was overwritten votes twice, and
+    the count drops once per pruned vote, i.e. by more than the number of features cleared."""
     k0, d0, k1, d1, sf = _two_frames(ob, synth)
     rng = np.random.default_rng(2)
     ur = np.where(rng.random(len(k1)) < 0.7, k1["x"] - rng.uniform(5, 40, len(k1)).astype(np.float32), np.float32(-1)).astype(np.float32)
@@ -109,13 +118,15 @@ def test_search_by_projection_frame(hb, ob, synth, forward, backward):
     q["has_obs"] = rng.random(len(k0)) < 0.6
     match0 = np.full(len(k1), -1, np.int32)
     for th in (7.0, 15.0):
-        rh, mh = hb.search_frame("host", view, q, match0, sf, 40.0, th, forward, backward)
-        ro, mo = hb.search_frame("oracle", view, q, match0, sf, 40.0, th, forward, backward)
+        rh, mh = hb.search_frame("host", view, q, match0, sf, 40.0, th, forward, backward, check_ori=check_ori)
+        ro, mo = hb.search_frame("oracle", view, q, match0, sf, 40.0, th, forward, backward, check_ori=check_ori)
         assert rh == ro and np.array_equal(mh, mo)
         assert rh > 50
-    rh, mh = hb.search_frame("host", view, q, match0, sf, 40.0, 15.0, forward, backward, check_ori=False)
-    ro, mo = hb.search_frame("oracle", view, q, match0, sf, 40.0, 15.0, forward, backward, check_ori=False)
-    assert rh == ro and np.array_equal(mh, mo)
+        if check_ori:
+            rn, mn = hb.search_frame("oracle", view, q, match0, sf, 40.0, th, forward, backward, check_ori=False)
+            _pruning_is_live((ro, mo), (rn, mn))
+    if check_ori:
+        assert rn - ro > int(((mn >= 0) & (mo < 0)).sum())
 
 
 def test_search_by_projection_points(hb, ob, synth):
@@ -150,6 +161,7 @@ def test_search_for_initialization(hb, ob, synth):
         rh, mh, ph = hb.search_init("host", v1, v2, prev, window)
         ro, mo, po = hb.search_init("oracle", v1, v2, prev, window)
         assert rh == ro and np.array_equal(mh, mo) and np.array_equal(ph, po)
+        _pruning_is_live((ro, mo), hb.search_init("oracle", v1, v2, prev, window, check_ori=False))
     assert rh > 30
     assert (mh[k0["octave"] > 0] == -1).all()  # only level-0 features take part
 
@@ -171,6 +183,7 @@ def test_search_by_projection_keyframe(hb, ob, synth):
         n_h, m_h = hb.search_kf("host", view, q, m0, sf, th, orb_dist)
         n_o, m_o = hb.search_kf("oracle", view, q, m0, sf, th, orb_dist)
         assert n_h == n_o and np.array_equal(m_h, m_o)
+        _pruning_is_live((n_o, m_o), hb.search_kf("oracle", view, q, m0, sf, th, orb_dist, check_ori=False))
     assert n_o > 50
 
 
@@ -197,6 +210,8 @@ def test_search_by_bow(hb, ob, synth):
         n_h, m_h = hb.search_bow("host", vkf, vf, ratio, ori)
         n_o, m_o = hb.search_bow("oracle", vkf, vf, ratio, ori)
         assert n_h == n_o and np.array_equal(m_h, m_o)
+        if ori:
+            _pruning_is_live((n_o, m_o), hb.search_bow("oracle", vkf, vf, ratio, False))
     assert n_o > 30
 
 
@@ -221,6 +236,8 @@ def test_search_by_bow_keyframes(hb, ob, synth):
         n_h, m_h = hb.search_bow_kf("host", v0, v1, ratio, ori)
         n_o, m_o = hb.search_bow_kf("oracle", v0, v1, ratio, ori)
         assert n_h == n_o and np.array_equal(m_h, m_o)
+        if ori:
+            _pruning_is_live((n_o, m_o), hb.search_bow_kf("oracle", v0, v1, ratio, False))
     assert n_o > 30
 
 
@@ -243,6 +260,7 @@ def test_search_for_triangulation(hb, ob, synth, only_stereo):
     n_o, p_o = hb.search_triangulation("oracle", v0, v1, f12, 320.0, 200.0, sf, sg, only_stereo)
     assert n_h == n_o and np.array_equal(p_h, p_o)
     assert n_o > 10
+    _pruning_is_live((n_o, p_o), hb.search_triangulation("oracle", v0, v1, f12, 320.0, 200.0, sf, sg, only_stereo, check_ori=False))
 
 
 def _win_queries(hb, k_src, d_src, rng, dx=-2.0, dy=-1.0):
