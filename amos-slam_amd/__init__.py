@@ -58,6 +58,9 @@ PROTOTYPES = {
     "amos_orb_describe_batch_device": (_i, (_v,)),
     "amos_orb_extract_batch_device_color": (_i, (_v, _v, _z, _z, _i, _i, _i, _i, _i)),
     "amos_frame_rgbd_glue_batch_device": (_i, (_v, _v, _i, _f, _z, _z, _f, _f, _f, _f, _f, _v, _v, _v, _v)),
+    "amos_frame_stereo_match": (_i, (_v, _v, _f, _f, _v, _v, _i)),
+    "amos_frame_stereo_match_batch_device": (_i, (_v, _v, _i, _f, _f, _v, _v, _v, _v)),
+    "amos_frame_stereo_match_arrays_device": (_i, (_v, _v, _i, _v, _v, _v, _i, _v, _v, _v, _i, _f, _f, _v, _v, _v, _v)),
     "amos_frame_undistort_batch_device": (_i, (_v, _f, _f, _f, _f, _v, _i, _v)),
     "amos_frame_image_bounds": (_i, (_i, _i, _f, _f, _f, _f, _v, _i, _v)),
     "amos_orb_batch_results_device": (_i, (_v, _v, _v, _v, _v)),
@@ -416,6 +419,29 @@ class OrbExtractor(_Handle):
         _check(self.L.amos_frame_rgbd_glue_batch_device(self.h, d_depth, int(depth_is_u16), depth_map_factor, depth_frame_stride, depth_row_stride, mbf, bounds[0],
                                                         bounds[1], bounds[2], bounds[3], d_kps_un, d_u_right, d_depth_out, d_grid_cell),
                "amos_frame_rgbd_glue_batch_device")
+
+    def stereo_match_batch_device(self, right, n_pairs, mbf, min_z, d_u_right, d_depth, d_sad=None, d_status=None):
+        """Frame::ComputeStereoMatches (Frame.cc:1179-1573) on the last batch results: pair p is frame p of self (left) and of `right`, or
+        -- right None / self -- frames 2p and 2p + 1 of this handle's batch.  float32 d_u_right / d_depth [n_pairs][capacity], -1 = no match;
+        int32 d_sad [n_pairs][capacity] and d_status [n_pairs] optional.  min_z is the reference's mb = mbf / fx.  Asynchronous on self's stream."""
+        r = self if right is None else right
+        _check(self.L.amos_frame_stereo_match_batch_device(self.h, r.h, n_pairs, mbf, min_z, d_u_right, d_depth, d_sad, d_status),
+               "amos_frame_stereo_match_batch_device")
+
+    def stereo_match(self, right, mbf, min_z, n):
+        """The synchronous host form: (u_right, depth) of the first n left keypoints of pair 0, one device-to-host transfer."""
+        r = self if right is None else right
+        ur, dep = np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.float32)
+        _check(self.L.amos_frame_stereo_match(self.h, r.h, mbf, min_z, _p(ur), _p(dep), n), "amos_frame_stereo_match")
+        return ur[:n], dep[:n]
+
+    def stereo_match_arrays_device(self, right, n_pairs, d_kps_l, d_desc_l, d_counts_l, capacity_l, d_kps_r, d_desc_r, d_counts_r, capacity_r, mbf, min_z,
+                                   d_u_right, d_depth, d_sad=None, d_status=None):
+        """The same with explicit [frames][capacity] keypoint / descriptor / count arrays; the handles give the pyramid planes and tables."""
+        r = self if right is None else right
+        _check(self.L.amos_frame_stereo_match_arrays_device(self.h, r.h, n_pairs, d_kps_l, d_desc_l, d_counts_l, capacity_l, d_kps_r, d_desc_r, d_counts_r,
+                                                            capacity_r, mbf, min_z, d_u_right, d_depth, d_sad, d_status),
+               "amos_frame_stereo_match_arrays_device")
 
     def undistort_batch_device(self, fx, fy, cx, cy, dist_coef, d_kps_un):
         """Frame::UndistortKeyPoints for every keypoint of the last batch (Frame.cc:1052-1118)."""

@@ -166,6 +166,28 @@ struct MaskPreStageA {
 
 struct amos_mask_pre;
 namespace amos {
+// ---- extractor handle, as the stereo matcher sees it (amos_stereo.hip): the resident planes, tables and last batch results
+struct OrbStereoView {
+    int device;
+    hipStream_t stream;
+    hipEvent_t event;              // the handle's own, for ordering against another handle's stream
+    amos_orb_params p;
+    int width, height, nFrames;    // frame size and frame count of the last detect / batch
+    bool detected, described;
+    const Geom *dGeom;
+    const uint8_t *dPyr;           // frame f at dPyr + f * frameBytes
+    unsigned long long frameBytes;
+    const amos_keypoint *dKps;     // amos_orb_batch_results_device
+    const uint8_t *dDesc;
+    const int *dCounts;
+    int capacity;
+    const float *scale, *invScale; // host tables, n_levels entries
+    int *dSadScratch;              // [max_batch][capacity]
+    float *dOutHostForm;           // [2][capacity]: uRight, depth of the host form
+    uint8_t *hStage;               // pinned, at least 2 * capacity floats
+};
+// AMOS_ERR_CAPACITY when sadScratchInts exceeds the handle's scratch
+int orb_stereo_view(amos_orb *h, size_t sadScratchInts, OrbStereoView *out);
 int mask_pre_stage_a(amos_mask_pre *p, MaskPreStageA *out);                              // tables and buffers of stage A
 int mask_pre_finish(amos_mask_pre *p, hipStream_t stream, int n_frames, float *d_out);  // stages B and C on `stream`
 const char *w24_variant_tag();  // amos_winograd24.hip: " NAME" per timing-experiment switch compiled in, "" for the product build

@@ -52,6 +52,7 @@ struct amos_orb : StreamHandle {
     // side stream: the blur only needs the pyramid, so it runs beside the latency-bound quad-tree
     hipStream_t streamB = nullptr;
     hipEvent_t evFork = nullptr, evJoin = nullptr, evBlur0 = nullptr, evBlur1 = nullptr;
+    hipEvent_t evStereo = nullptr;  // orders a stereo match (amos_stereo.hip) against the other handle's stream
     bool blurDone = false;  // the blurred planes of the current frame(s) exist
     size_t octLdsAttr = 0;  // dynamic LDS limit last set on k_octree
     // a1 tables
@@ -78,6 +79,8 @@ struct amos_orb : StreamHandle {
     int *dCandCount = nullptr, *dLvCount = nullptr, *dOutCount = nullptr;
     amos_keypoint *dLvKps = nullptr, *dOutKps = nullptr, *dRemoved = nullptr, *dScratchKps = nullptr;
     uint8_t *dOutDesc = nullptr;
+    int *dStereoSad = nullptr;  // [B][kpCap] accepted SADs of a stereo match whose caller passes no d_sad
+    float *dStereoOut = nullptr;  // [2][kpCap] uRight and depth of amos_frame_stereo_match (host form)
     uint8_t *dMask = nullptr, *dMaskTmp = nullptr, *dMaskClosed = nullptr;
     uint8_t *hStage = nullptr;  // pinned host staging for fetch_frame: count, one frame's keypoints and descriptors
     uint8_t *hPyrStage = nullptr;  // pinned host staging for one frame's pyramid (level images to host Mats), made on first use
@@ -483,6 +486,38 @@ static int dev_alloc(T **p, size_t count)
 }
 
 // ---------------------------------------------------------------------------------------------
+// what amos_stereo.hip sees of an extractor handle (amos_common.h)
+int amos::orb_stereo_view(amos_orb *h, size_t sadScratchInts, OrbStereoView *v)
+{
+    if (!h || !v) { set_error("orb_stereo_view: invalid argument"); return AMOS_ERR_INVALID; }
+    if (sadScratchInts > (size_t)h->maxB * h->capGeom.kpCap) {
+        set_error("stereo match without d_sad needs %zu ints of scratch, the handle holds %zu: pass d_sad", sadScratchInts, (size_t)h->maxB * h->capGeom.kpCap);
+        return AMOS_ERR_CAPACITY;
+    }
+    v->device = h->device;
+    v->stream = h->stream;
+    v->event = h->evStereo;
+    v->p = h->p;
+    v->width = h->curW;
+    v->height = h->curH;
+    v->nFrames = h->nFrames;
+    v->detected = h->detected;
+    v->described = h->described;
+    v->dGeom = h->dGeom;
+    v->dPyr = h->dPyr;
+    v->frameBytes = h->geom.frameBytes;
+    v->dKps = h->dOutKps;
+    v->dDesc = h->dOutDesc;
+    v->dCounts = h->dOutCount;
+    v->capacity = h->capGeom.kpCap;
+    v->scale = h->scale;
+    v->invScale = h->invScale;
+    v->dSadScratch = h->dStereoSad;
+    v->dOutHostForm = h->dStereoOut;
+    v->hStage = h->hStage;
+    return AMOS_OK;
+}
+
 extern "C" {
 
 const char *amos_last_error(void) { return g_error.c_str(); }
@@ -582,7 +617,8 @@ int amos_orb_create(const amos_orb_params *params, int max_width, int max_height
     const Geom &c = h->capGeom;
     if (hipStreamCreateWithFlags(&h->streamB, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&h->evFork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->evJoin, hipEventDisableTiming) != hipSuccess || hipEventCreate(&h->evBlur0) != hipSuccess ||
+        hipEventCreateWithFlags(&h->evJoin, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&h->evStereo, hipEventDisableTiming) != hipSuccess || hipEventCreate(&h->evBlur0) != hipSuccess ||
         hipEventCreate(&h->evBlur1) != hipSuccess) {
         set_error("side stream / event creation failed");
         amos_orb_destroy(h);
@@ -610,6 +646,8 @@ int amos_orb_create(const amos_orb_params *params, int max_width, int max_height
     ALLOC(h->dLvKps, B * c.kpLevelTotal);
     ALLOC(h->dOutKps, B * c.kpCap);
     ALLOC(h->dOutDesc, B * c.kpCap * 32);
+    ALLOC(h->dStereoSad, B * c.kpCap);
+    ALLOC(h->dStereoOut, (size_t)2 * c.kpCap);
     ALLOC(h->dRemoved, B * c.kpLevelTotal);
     ALLOC(h->dScratchKps, (size_t)c.ptsTotal);
     ALLOC(h->dMask, (size_t)h->maskPitch * max_height);
@@ -671,13 +709,13 @@ void amos_orb_destroy(amos_orb *h)
     void *ptrs[] = {h->dGeom, h->dCells, h->dTaps, h->dPyr, h->dBlur, h->dInput, h->dSlotCount, h->dSlots, h->dPts,
                     h->dNodeOf, h->dQuadOf, h->dCandCount, h->dLvCount, h->dOutCount, h->dLvKps, h->dOutKps, h->dOutDesc,
                     h->dRemoved, h->dScratchKps, h->dMask, h->dMaskTmp, h->dMaskClosed, h->dLabels, h->dCenterIds, h->dRm,
-                    h->dNRemoved, h->dErr};
+                    h->dNRemoved, h->dErr, h->dStereoSad, h->dStereoOut};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (h->hStage) (void)hipHostFree(h->hStage);
     if (h->hPyrStage) (void)hipHostFree(h->hPyrStage);
     for (hipEvent_t e : h->events) (void)hipEventDestroy(e);
     if (h->streamB) { (void)hipStreamSynchronize(h->streamB); (void)hipStreamDestroy(h->streamB); }
-    for (hipEvent_t e : {h->evFork, h->evJoin, h->evBlur0, h->evBlur1}) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {h->evFork, h->evJoin, h->evBlur0, h->evBlur1, h->evStereo}) if (e) (void)hipEventDestroy(e);
     delete h;
 }
 

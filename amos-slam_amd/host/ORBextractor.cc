@@ -38,7 +38,7 @@ int AmosPickDevice()
 
 ORBextractor::ORBextractor(int _nfeatures, float _scaleFactor, int _nlevels, int _iniThFAST, int _minThFAST)
     : nfeatures(_nfeatures), scaleFactor(_scaleFactor), nlevels(_nlevels), iniThFAST(_iniThFAST), minThFAST(_minThFAST), mpHandle(nullptr),
-      mnDevice(-1), mnHandleW(0), mnHandleH(0), mnPyramidMode(PYRAMID_AUTO), mbPyramidOnHost(false), mnLevelTotal(0), mbDeviceListsKnown(false)
+      mnDevice(-1), mnHandleW(0), mnHandleH(0), mnPyramidMode(PYRAMID_AUTO), mbPyramidOnHost(false), mnLevelTotal(0), mbDeviceListsKnown(false), mnLastCount(-1)
 {
     mvImagePyramid.resize(nlevels);
     mvPyramidStore.resize(nlevels);
@@ -112,6 +112,7 @@ void ORBextractor::DownloadPyramid()
 void ORBextractor::Detect(const cv::Mat &image)
 {
     EnsureHandle(image.cols, image.rows);
+    mnLastCount = -1;
     Check(amos_orb_detect(mpHandle, image.data, image.step, image.cols, image.rows), "amos_orb_detect");
     mvLevelOffset.resize(nlevels);
     mvLevelCap.resize(nlevels);
@@ -165,7 +166,9 @@ void ORBextractor::operator()(cv::InputArray _image, cv::InputArray _mask, std::
     mvStage.resize(cap);
     mvStageDesc.resize((size_t)cap * 32);
     int n = 0;
+    mnLastCount = -1;
     Check(amos_orb_extract(mpHandle, image.data, image.step, image.cols, image.rows, AsAmos(mvStage.data()), mvStageDesc.data(), cap, &n), "amos_orb_extract");
+    mnLastCount = n;
     mvLevelOffset.resize(nlevels);
     mvLevelCap.resize(nlevels);
     Check(amos_orb_level_layout(mpHandle, mvLevelOffset.data(), mvLevelCap.data(), &mnLevelTotal), "amos_orb_level_layout");
@@ -223,7 +226,9 @@ void ORBextractor::ProcessDesp(cv::InputArray _image, cv::InputArray _mask, std:
     mvStage.resize(cap);
     mvStageDesc.resize((size_t)cap * 32);
     int n = 0;
+    mnLastCount = -1;
     Check(amos_orb_describe(mpHandle, AsAmos(mvStage.data()), mvStageDesc.data(), cap, &n), "amos_orb_describe");
+    mnLastCount = n;
     if (n == 0) {
         _descriptors.release();
     } else {

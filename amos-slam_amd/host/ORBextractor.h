@@ -52,7 +52,8 @@ public:
 
     // ROIs into padded buffers, as in the reference; rows / cols / step are always those of the level.  The PIXELS live on the device:
     // by default (PYRAMID_AUTO) the 4-arg operator() -- the mono / stereo Frame constructors, whose ComputeStereoMatches reads
-    // mvImagePyramid pixels (Frame.cc:1401,1434) -- copies every level back, the 3-arg operator() of the RGB-D Amos flow, which
+    // mvImagePyramid pixels (Frame.cc:1401,1434; FrameStereo.h runs it on the device and needs none: PYRAMID_NEVER is then safe for
+    // stereo) -- copies every level back, the 3-arg operator() of the RGB-D Amos flow, which
     // only reads mvImagePyramid[0].rows (Frame.cc:1197), does not (1.16 MB per frame saved).  SetPyramidDownload(true / false) forces
     // either for both; DownloadPyramid() fills the Mats of the last extraction on demand.
     std::vector<cv::Mat> mvImagePyramid;
@@ -66,6 +67,8 @@ public:
     int GetDevice() const { return mnDevice; }
     // The device handle (batch API, streams): see include/amos_frontend.h.
     amos_orb *Handle() { return mpHandle; }
+    // Keypoints of the last 4-arg operator() / ProcessDesp, resident on the handle (FrameStereo.h matches them there); -1 before one.
+    int LastKeypointCount() const { return mnLastCount; }
 
 protected:
     void EnsureHandle(int width, int height);
@@ -99,6 +102,7 @@ protected:
     std::vector<int32_t> mvDeviceCounts;
     std::vector<cv::KeyPoint> mvDeviceLists;
     bool mbDeviceListsKnown;
+    int mnLastCount;
     std::vector<cv::KeyPoint> mvStage;  // marshalling scratch (level lists; keypoints of the final result)
     std::vector<uint8_t> mvStageDesc;
 };

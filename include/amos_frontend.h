@@ -221,6 +221,34 @@ int amos_frame_rgbd_glue_batch_device(amos_orb *h, const void *d_depth, int dept
                                       float min_x, float max_x, float min_y, float max_y,
                                       const amos_keypoint *d_kps_un, float *d_u_right, float *d_depth_out,
                                       int32_t *d_grid_cell);
+/* Frame::ComputeStereoMatches (Frame.cc:1179-1573) for n_pairs stereo pairs of resident extractions: the band search over the right
+ * keypoints (rows floor(yR - r) .. ceil(yR + r), r = 2 * scale[octaveR]; octave within +-1; uL - mbf / min_z <= uR <= uL) with its Hamming
+ * loop, the 11 x 11 SAD over 11 shifts on the level of the left keypoint, the parabola fit, depth = mbf / disparity and the rejection of
+ * every match whose SAD is not below 1.5f * 1.4f * median.  Integer Hamming and SAD, float32 in the source's order, nothing fused.
+ * Pairing: with two handles pair p is frame p of each; with left == right pair p is frames 2p (left) and 2p + 1 (right) of the one batch.
+ * The handles need the same amos_orb_params and frame size and live on one device.  mbf, min_z > 0; the reference's minZ is its mb,
+ * i.e. the caller passes min_z = mbf / fx.
+ * The first entry matches each handle's batch results (amos_orb_batch_results_device); the second takes the keypoints, descriptors
+ * (16-byte aligned, 32 bytes each) and counts explicitly -- laid out [frames][capacity] and indexed by the same frame numbers -- and uses
+ * the handles for their pyramid planes and tables only.
+ * Outputs, on the device: d_u_right, d_depth [n_pairs][capacity_l] (capacity_l = left's capacity in the first entry), -1 where there is no
+ * match; d_sad [n_pairs][capacity_l] (may be NULL): the best SAD of every match accepted BEFORE the median step, else -1; d_status
+ * [n_pairs] (may be NULL): 0, or bit 1 when a left keypoint's row is outside [0, height) or a keypoint's octave outside the pyramid (such
+ * a keypoint is skipped).  Window rows and columns are clamped into the padded plane (the reference does not check them).  A pair
+ * without an accepted match is left all -1 (the reference indexes an empty vector there).
+ * Asynchronous on left's stream; when the handles differ, left's stream waits for an event recorded on right's (and right's next work
+ * for the two launches): no host synchronisation.  AMOS_ERR_STATE before an extraction, AMOS_ERR_INVALID otherwise. */
+int amos_frame_stereo_match_batch_device(amos_orb *left, amos_orb *right, int n_pairs, float mbf, float min_z, float *d_u_right,
+                                         float *d_depth, int32_t *d_sad, int32_t *d_status);
+int amos_frame_stereo_match_arrays_device(amos_orb *left, amos_orb *right, int n_pairs, const amos_keypoint *d_kps_l,
+                                          const uint8_t *d_desc_l, const int32_t *d_counts_l, int capacity_l,
+                                          const amos_keypoint *d_kps_r, const uint8_t *d_desc_r, const int32_t *d_counts_r,
+                                          int capacity_r, float mbf, float min_z, float *d_u_right, float *d_depth, int32_t *d_sad,
+                                          int32_t *d_status);
+/* The host form for the C++ drop-in (amos-slam_amd/host/FrameStereo.h): pair 0 of the two handles' last extractions (left == right: frames
+ * 0 and 1 of the one batch), synchronous; u_right / depth are HOST arrays that receive the first n entries (n = number of left keypoints,
+ * at most left's capacity) in ONE device-to-host transfer of the two float arrays.  No pyramid plane leaves the device. */
+int amos_frame_stereo_match(amos_orb *left, amos_orb *right, float mbf, float min_z, float *u_right, float *depth, int n);
 /* Frame::UndistortKeyPoints (Frame.cc:1052-1118) for every keypoint of the last batch:
  * cv::undistortPoints(pts, pts, K, distCoef, Mat(), K) with OpenCV's default criteria (5 iterations, double
  * arithmetic), distCoef = (k1, k2, p1, p2[, k3]) as Tracking reads them from the YAML (n_dist = 4 or 5;
