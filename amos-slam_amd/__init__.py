@@ -81,6 +81,8 @@ PROTOTYPES = {
     "amos_match_bruteforce_best2_batch_device": (_i, (_v, _v, _z, _v, _v, _v, _i, _i, _i, _v)),
     "amos_frame_grid_build_batch_device": (_i, (_v, _v, _v, _i, _i, _v, _v)),
     "amos_match_window_best2_batch_device": (_i, (_v, _v, _v)),
+    "amos_match_local_points_batch_device": (_i, (_v, _v)),
+    "amos_match_local_points": (_i, (_v, _v, _v, _v, _i, _v, _i, _v, _v, _v, _i, _f, _f, _f, _f, _v, _v, _v, _v)),
     "amos_mask_pre_create": (_i, (_i, _v, _i, _i, _i, _v)),
     "amos_mask_pre_destroy": (None, (_v,)),
     "amos_mask_pre_stream": (_v, (_v,)),
@@ -802,6 +804,46 @@ class WindowSearch(C.Structure):
                 ("mbf", C.c_float), ("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float)]
 
 
+class MapPoint(C.Structure):
+    """amos_map_point (include/amos_frontend.h): 80 bytes; MAP_POINT_DTYPE is the same record for numpy."""
+    _fields_ = [("pos", C.c_float * 3), ("normal", C.c_float * 3), ("min_distance", C.c_float), ("max_distance", C.c_float),
+                ("flags", C.c_int32), ("desc", C.c_uint8 * 32), ("pad", C.c_uint8 * 12)]
+
+
+class LocalCamera(C.Structure):
+    """amos_local_camera: 92 bytes; LOCAL_CAMERA_DTYPE is the same record for numpy."""
+    _fields_ = [("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("Ow", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float),
+                ("cx", C.c_float), ("cy", C.c_float), ("mbf", C.c_float), ("view_cos_limit", C.c_float), ("th", C.c_float),
+                ("nn_ratio", C.c_float)]
+
+
+class LocalStats(C.Structure):
+    """amos_local_stats; LOCAL_STATS_DTYPE is the same record for numpy."""
+    _fields_ = [("n_in_view", C.c_int32), ("n_matches", C.c_int32), ("n_researched", C.c_int32), ("status", C.c_int32)]
+
+
+MAP_POINT_SKIP, MAP_POINT_HAS_OBS = 1, 2
+MAP_POINT_DTYPE = np.dtype([("pos", "<f4", (3,)), ("normal", "<f4", (3,)), ("min_distance", "<f4"), ("max_distance", "<f4"),
+                            ("flags", "<i4"), ("desc", "u1", (32,)), ("pad", "u1", (12,))])
+LOCAL_CAMERA_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("Ow", "<f4", (3,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"),
+                               ("cy", "<f4"), ("mbf", "<f4"), ("view_cos_limit", "<f4"), ("th", "<f4"), ("nn_ratio", "<f4")])
+LOCAL_STATS_DTYPE = np.dtype([("n_in_view", "<i4"), ("n_matches", "<i4"), ("n_researched", "<i4"), ("status", "<i4")])
+# amos_map_query (include/amos_host_types.h)
+MAP_QUERY_DTYPE = np.dtype([("proj_x", "<f4"), ("proj_y", "<f4"), ("proj_xr", "<f4"), ("view_cos", "<f4"), ("level", "<i4"),
+                            ("has_obs", "<i4"), ("desc", "u1", (32,))])
+assert (C.sizeof(MapPoint), C.sizeof(LocalCamera), C.sizeof(LocalStats)) == (MAP_POINT_DTYPE.itemsize, LOCAL_CAMERA_DTYPE.itemsize,
+                                                                            LOCAL_STATS_DTYPE.itemsize) == (80, 92, 16)
+
+
+class LocalSearch(C.Structure):
+    """amos_local_search (include/amos_frontend.h)."""
+    _fields_ = [("d_kps", C.c_void_p), ("d_desc", C.c_void_p), ("d_counts", C.c_void_p), ("d_cell_start", C.c_void_p), ("d_items", C.c_void_p),
+                ("d_u_right", C.c_void_p), ("d_points", C.c_void_p), ("point_off", C.c_void_p), ("cameras", C.c_void_p),
+                ("d_occupied", C.c_void_p), ("scale_factors", C.c_void_p), ("d_query", C.c_void_p), ("d_in_view", C.c_void_p),
+                ("d_match", C.c_void_p), ("d_stats", C.c_void_p), ("n_frames", C.c_int32), ("capacity", C.c_int32), ("n_levels", C.c_int32),
+                ("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float)]
+
+
 class OrbMatcher(_Handle):
     """The distance / best-two primitives every ORBmatcher::Search* inner loop reduces to
     (ORBmatcher.cc:1913-1933 and the candidate loops at :127-148, :278-304, :560-580, :1644-1690)."""
@@ -865,6 +907,38 @@ class OrbMatcher(_Handle):
         w = WindowSearch(d_kps, d_desc, d_counts, d_cell_start, d_items, d_query_uv, d_query_invz, d_u_right, d_pairs_q, d_pairs_t,
                          sf.ctypes.data, n_pairs, capacity, len(sf), mode, init_dist, th, mbf, *bounds)
         _check(self.L.amos_match_window_best2_batch_device(self.h, C.byref(w), d_out), "amos_match_window_best2_batch_device")
+
+    def local_points_batch_device(self, d_kps, d_desc, d_counts, d_cell_start, d_items, d_points, point_off, cameras, d_occupied, capacity,
+                                  scale_factors, d_query, d_in_view, d_match, d_stats, bounds=(0.0, 640.0, 0.0, 480.0), d_u_right=None):
+        """Step 2 of Tracking::SearchLocalPoints for resident frames: isInFrustum + PredictScale on every point, then
+        SearchByProjection(F, vpMapPoints, th) (Frame.cc:761-891, ORBmatcher.cc:70-175).  point_off: n_frames + 1 host ints; cameras: host
+        LOCAL_CAMERA_DTYPE records, one per frame.  Asynchronous on the matcher's stream."""
+        sf = np.ascontiguousarray(scale_factors, np.float32)
+        off = np.ascontiguousarray(point_off, np.int32)
+        cams = np.ascontiguousarray(cameras, LOCAL_CAMERA_DTYPE).reshape(-1)
+        if len(off) != len(cams) + 1:
+            raise ValueError("point_off holds one entry more than cameras")
+        s = LocalSearch(d_kps, d_desc, d_counts, d_cell_start, d_items, d_u_right, d_points, off.ctypes.data, cams.ctypes.data, d_occupied,
+                        sf.ctypes.data, d_query, d_in_view, d_match, d_stats, len(cams), capacity, len(sf), *bounds)
+        _check(self.L.amos_match_local_points_batch_device(self.h, C.byref(s)), "amos_match_local_points_batch_device")
+
+    def local_points(self, kps_un, desc, points, camera, occupied, scale_factors, bounds=(0.0, 640.0, 0.0, 480.0), u_right=None):
+        """The same for ONE frame from host arrays (amos_match_local_points): returns (query, in_view, match, stats)."""
+        kps_un = np.ascontiguousarray(kps_un, KP_DTYPE)
+        desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        points = np.ascontiguousarray(points, MAP_POINT_DTYPE)
+        cam = np.ascontiguousarray(camera, LOCAL_CAMERA_DTYPE).reshape(1)
+        occupied = np.ascontiguousarray(occupied, np.uint8)
+        sf = np.ascontiguousarray(scale_factors, np.float32)
+        ur = None if u_right is None else np.ascontiguousarray(u_right, np.float32)
+        n, m = len(kps_un), len(points)
+        if len(desc) != n or len(occupied) != n or (ur is not None and len(ur) != n):
+            raise ValueError("desc, occupied and u_right hold one entry per keypoint")
+        query, in_view = np.zeros(m, MAP_QUERY_DTYPE), np.zeros(m, np.uint8)
+        match, stats = np.full(n, -1, np.int32), np.zeros(1, LOCAL_STATS_DTYPE)
+        _check(self.L.amos_match_local_points(self.h, _p(kps_un), _p(desc), _p(ur), n, _p(points), m, _p(cam), _p(occupied), _p(sf), len(sf),
+                                              *bounds, _p(query), _p(in_view), _p(match), _p(stats)), "amos_match_local_points")
+        return query, in_view, match, stats[0]
 
     def sync(self):
         _check(self.L.amos_match_sync(self.h), "amos_match_sync")

@@ -6,59 +6,13 @@
 //     if(dist<bestDist){...} else if(dist<bestDist2){...}
 // loop does (first candidate wins; see DESIGN.md for the proof of equivalence).  No MFMA.
 #include "amos_common.h"
+#include "amos_match_core.h"
 
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
 
 namespace amos {
-
-struct Desc {
-    uint32_t w[8];
-};
-
-__device__ __forceinline__ int hamming256(const Desc &a, const Desc &b)
-{
-    int d = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) d += __popc(a.w[i] ^ b.w[i]);
-    return d;
-}
-
-__device__ __forceinline__ Desc load_desc(const uint8_t *p)
-{
-    Desc d;
-    const uint4 lo = reinterpret_cast<const uint4 *>(p)[0], hi = reinterpret_cast<const uint4 *>(p)[1];
-    d.w[0] = lo.x; d.w[1] = lo.y; d.w[2] = lo.z; d.w[3] = lo.w;
-    d.w[4] = hi.x; d.w[5] = hi.y; d.w[6] = hi.z; d.w[7] = hi.w;
-    return d;
-}
-
-// popcount(x) + acc in ONE instruction.  The compiler knows v_bcnt_u32_b32's accumulate operand but
-// re-associates an 8-term sum into 8 x v_bcnt(.., 0) + 3 x v_add3; the chained form is 8 instructions.
-__device__ __forceinline__ int bcnt_acc(uint32_t x, int acc)
-{
-    int r;
-    asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(acc));
-    return r;
-}
-
-// top-2 of unique keys
-template <typename K>
-__device__ __forceinline__ void top2_push(K &best, K &second, K key)
-{
-    const K hi = best > key ? best : key;
-    best = best < key ? best : key;
-    second = second < hi ? second : hi;
-}
-template <typename K>
-__device__ __forceinline__ void top2_merge(K &best, K &second, K ob, K os)
-{
-    const K hi = best > ob ? best : ob;
-    const K lo2 = second < os ? second : os;
-    best = best < ob ? best : ob;
-    second = hi < lo2 ? hi : lo2;
-}
 
 // ---- dense distances: out[i * nt + j].  grid = (ceil(nt/256), ceil(nq/16)), block = 256.
 __global__ __launch_bounds__(256) void k_dist_dense(const uint8_t *__restrict__ q, int nq, const uint8_t *__restrict__ t,
@@ -126,8 +80,6 @@ __global__ __launch_bounds__(256) void k_list_best2(const uint8_t *__restrict__ 
 // per-keypoint cell numbers (k_rgbd_glue) into CSR lists, ascending keypoint index inside a cell (the
 // reference push_back()s in index order).  Counting by LDS atomics, exclusive scan of the 3072
 // counts, unordered fill, then each thread insertion-sorts the (tiny) lists of its 12 cells.
-constexpr int kGridCells = AMOS_FRAME_GRID_COLS * AMOS_FRAME_GRID_ROWS;
-
 __global__ __launch_bounds__(256) void k_grid_build(const int *__restrict__ cell, const int *__restrict__ counts, int capacity,
                                                    int *__restrict__ cellStart, int *__restrict__ items)
 {
@@ -207,8 +159,6 @@ struct WindowArgs {
     int capacity, mode, initDist;
 };
 
-constexpr int kWindowLanes = 8;  // lanes per query: each takes every 8th grid column of the window
-
 __global__ __launch_bounds__(256) void k_window_best2(const WindowArgs a, amos_best2 *__restrict__ out)
 {
     const int t = blockIdx.x * 256 + threadIdx.x, pair = blockIdx.y;
@@ -228,16 +178,7 @@ __global__ __launch_bounds__(256) void k_window_best2(const WindowArgs a, amos_b
     const bool checkLevels = minLevel > 0 || maxLevel >= 0;
     const bool gateRight = a.uRight != nullptr && a.queryInvZ != nullptr;
     const float ur = gateRight ? __fsub_rn(u, __fmul_rn(a.mbf, a.queryInvZ[po])) : 0.f;
-    int x0 = (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(u, a.minX), r), a.wInv));
-    int x1 = (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(u, a.minX), r), a.wInv));
-    int y0 = (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(v, a.minY), r), a.hInv));
-    int y1 = (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(v, a.minY), r), a.hInv));
-    // Frame.cc:905-921: the reference returns early when a clamp range is empty; without this a query projected far
-    // outside the bounds would index cellStart with y0 >= ROWS
-    const bool empty = x0 >= AMOS_FRAME_GRID_COLS || x1 < 0 || y0 >= AMOS_FRAME_GRID_ROWS || y1 < 0;
-    x0 = max(x0, 0); y0 = max(y0, 0);
-    x1 = empty ? -1 : min(x1, AMOS_FRAME_GRID_COLS - 1); y1 = min(y1, AMOS_FRAME_GRID_ROWS - 1);
-    y0 = min(y0, AMOS_FRAME_GRID_ROWS - 1);
+    const CellRange c = cell_range(u, v, r, a.minX, a.minY, a.wInv, a.hInv);
     const int *cs = a.cellStart + (size_t)ft * (kGridCells + 1);
     const int *it = a.items + (size_t)ft * a.capacity;
     const amos_keypoint *tk = a.kps + (size_t)ft * a.capacity;
@@ -247,9 +188,9 @@ __global__ __launch_bounds__(256) void k_window_best2(const WindowArgs a, amos_b
     // strict-< updates keep the FIRST of equal distances: a min-reduction over keys (dist << 16 | CSR position)
     // gives the same best and second best whatever the evaluation order.
     unsigned best = 0xffffffffu, second = 0xffffffffu;
-    for (int ix = x0 + sub; ix <= x1; ix += kWindowLanes) {
-        // cells (ix, y0..y1) are consecutive in the CSR: one item range per column
-        const int b = cs[ix * AMOS_FRAME_GRID_ROWS + y0], e = y1 >= y0 ? cs[ix * AMOS_FRAME_GRID_ROWS + y1 + 1] : b;
+    for (int ix = c.x0 + sub; ix <= c.x1; ix += kWindowLanes) {
+        int b, e;  // cells (ix, y0..y1) are consecutive in the CSR: one item range per column
+        column_items(cs, c, ix, b, e);
         for (int j = b; j < e; j++) {
             const int idx = it[j];
             const amos_keypoint k = tk[idx];
@@ -589,21 +530,6 @@ __global__ __launch_bounds__(64 * kWaves * kQ) void k_bf_best2_mfma(const uint8_
 
 using namespace amos;
 
-struct amos_match : StreamHandle {
-    // device scratch of the host-pointer entry points: the inputs of the call in flight (pointers into dArena), the grow-only result buffer
-    uint8_t *dQ = nullptr, *dT = nullptr;
-    int *dOff = nullptr, *dIdx = nullptr;
-    void *dOut = nullptr;
-    size_t capOut = 0;
-    // pinned host staging of the host-buffer calls: the caller's (pageable) arrays are copied here and travel as true asynchronous DMA
-    // transfers; results land here behind the kernel and are copied out after the ONE synchronisation of the call (a hipMemcpyAsync on
-    // pageable memory is a blocking staged copy of its own: six of them were most of a 0.26 ms list-distance call)
-    uint8_t *hStage = nullptr;
-    uint8_t *dArena = nullptr;  // device mirror of the staging buffer's input part: the inputs of a call travel as ONE transfer (dQ / dT / dOff / dIdx point into it)
-    size_t capStage = 0, stageUsed = 0;
-    int bfKernel = 0;  // brute-force best-2: 0 = choose by size, 1 = xor + popcount kernel, 2 = i8 MFMA kernel
-};
-
 // the MFMA kernel works on 128-query x 32-train tiles: below a few tiles' worth of work the popcount kernel wins
 static bool use_mfma(const amos_match *m, int nq, int nt)
 {
@@ -634,72 +560,6 @@ static void launch_bf(amos_match *m, bool mfma, dim3 gridPop, dim3 gridMfma, con
         hipLaunchKernelGGL(k_bf_best2<kGate>, gridPop, dim3(256), 0, m->stream, dq, dt, stride, counts, pq, pt, nq, nt, capacity, initDist, out);
 }
 
-template <typename T>
-static int grow(T **p, size_t *cap, size_t need)
-{
-    if (need <= *cap) return AMOS_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    const size_t n = std::max<size_t>(need + need / 2, 256);
-    AMOS_HIP_CHECK(hipMalloc((void **)p, n * sizeof(T)));
-    *cap = n;
-    return AMOS_OK;
-}
-
-// every host-buffer call ends with a stream synchronisation, so the staging buffer is free at the start of the next one
-static int stage_begin(amos_match *m, size_t bytes)
-{
-    m->stageUsed = 0;
-    bytes += 1024;  // alignment slack of the pieces
-    if (bytes <= m->capStage) return AMOS_OK;
-    if (m->hStage || m->dArena) (void)hipStreamSynchronize(m->stream);  // (a call that failed half way may have left a transfer in flight)
-    if (m->hStage) (void)hipHostFree(m->hStage);
-    if (m->dArena) (void)hipFree(m->dArena);
-    m->hStage = m->dArena = nullptr;
-    m->capStage = 0;
-    const size_t n = std::max<size_t>(bytes + bytes / 2, 1 << 16);
-    if (hipHostMalloc((void **)&m->hStage, n, hipHostMallocDefault) != hipSuccess || hipMalloc((void **)&m->dArena, n) != hipSuccess) {
-        (void)hipGetLastError();
-        set_error("matcher staging of %zu bytes (pinned host + device) could not be allocated", n);
-        return AMOS_ERR_DEVICE;
-    }
-    m->capStage = n;
-    return AMOS_OK;
-}
-
-static size_t stage_take(amos_match *m, size_t bytes)
-{
-    const size_t o = m->stageUsed;
-    m->stageUsed += (bytes + 63) & ~(size_t)63;
-    return o;  // (stage_begin sized the buffers for the sum of the call's pieces)
-}
-
-// host array -> staging; returns where it will sit on the device once stage_flush has run
-template <typename T>
-static T *stage_input(amos_match *m, const void *src, size_t bytes)
-{
-    const size_t o = stage_take(m, bytes);
-    if (bytes) std::memcpy(m->hStage + o, src, bytes);
-    return reinterpret_cast<T *>(m->dArena + o);
-}
-
-static int stage_flush(amos_match *m)
-{
-    if (m->stageUsed) AMOS_HIP_CHECK(hipMemcpyAsync(m->dArena, m->hStage, m->stageUsed, hipMemcpyHostToDevice, m->stream));
-    return AMOS_OK;
-}
-
-// device -> staging (behind the inputs), one synchronisation, staging -> `out`
-static int stage_d2h_sync(amos_match *m, void *out, const void *src, size_t bytes)
-{
-    uint8_t *p = m->hStage + stage_take(m, bytes);
-    AMOS_HIP_CHECK(hipMemcpyAsync(p, src, bytes, hipMemcpyDeviceToHost, m->stream));
-    AMOS_HIP_CHECK(hipStreamSynchronize(m->stream));
-    std::memcpy(out, p, bytes);
-    return AMOS_OK;
-}
-
 static int upload_sets(amos_match *m, const uint8_t *q, int nq, const uint8_t *t, int nt)
 {
     m->dQ = stage_input<uint8_t>(m, q, (size_t)nq * 32);
@@ -721,14 +581,6 @@ static int upload_lists(amos_match *m, int nq, int nt, const int32_t *cand_off, 
     return AMOS_OK;
 }
 
-static int grow_out(amos_match *m, size_t bytes)
-{
-    uint8_t *p = (uint8_t *)m->dOut;
-    int rc = grow(&p, &m->capOut, bytes);
-    m->dOut = p;
-    return rc;
-}
-
 extern "C" {
 
 int amos_match_create(int device, void *stream, amos_match **out)
@@ -745,9 +597,11 @@ void amos_match_destroy(amos_match *m)
 {
     if (!m) return;
     m->close();
-    void *ptrs[] = {m->dArena, m->dOut};  // (dQ / dT / dOff / dIdx point into the arena)
+    void *ptrs[] = {m->dArena, m->dOut, m->dLocal};  // (dQ / dT / dOff / dIdx point into the arena)
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (m->hStage) (void)hipHostFree(m->hStage);
+    if (m->hLocal) (void)hipHostFree(m->hLocal);
+    if (m->localCopied) (void)hipEventDestroy(m->localCopied);
     delete m;
 }
 

@@ -356,6 +356,87 @@ typedef struct amos_window_search {
 } amos_window_search;
 int amos_match_window_best2_batch_device(amos_match *m, const amos_window_search *w, amos_best2 *d_out);
 
+/* ---------------------------------------------------------------- local map search ---------- */
+
+/* Step 2 of Tracking::SearchLocalPoints (Tracking.cc:2352-2389) for a batch of resident frames: Frame::isInFrustum (Frame.cc:761-891)
+ * with MapPoint::PredictScale (MapPoint.cc:571-586) on every local map point, then ORBmatcher::SearchByProjection(Frame&, const
+ * vector<MapPoint*>&, th) (ORBmatcher.cc:70-175) over the points in view, greedy loop included: three launches, nothing returns to the host.
+ *
+ * Arithmetic (PARITY UNPINNED, like the other OpenCV-derived stages): float32, every operation rounded, nothing fused, except
+ *   Pc = Rcw * P + tcw       one gemm per row: ((R0 P0 + R1 P1) + R2 P2) + t in double, one rounding to float; PcZ < 0 is out of view
+ *   invz = 1.0f / PcZ;  u = ((fx * PcX) * invz) + cx;  v alike;  projXR = u - mbf * invz
+ *   a u or v that is not finite is out of view and sets bit 0 (value 1) of the frame's status (the reference goes on to convert it
+ *   to int, which is undefined);
+ *   u < min_x || u > max_x || v < min_y || v > max_y is out of view
+ *   PO = P - Ow;  dist = (float) sqrt(((double) PO0^2 + (double) PO1^2) + (double) PO2^2)            (cv::norm on CV_32F)
+ *   dist < 0.8f * min_distance || dist > 1.2f * max_distance is out of view
+ *   viewCos = (float) ((((double) PO0 Pn0 + (double) PO1 Pn1) + (double) PO2 Pn2) / (double) dist)  (Mat::dot returns double)
+ *   viewCos < view_cos_limit is out of view
+ *   level = number of m in [0, n_levels) with max_distance / dist > scale_factors[m], at most n_levels - 1 (a NaN ratio gives 0): this
+ *   is ceil(logf(ratio) / mfLogScaleFactor) clamped, without a library logarithm; the two differ only for a ratio within rounding of
+ *   a table entry.
+ * Search: radius r * scale_factors[level], r = ((double) viewCos > 0.998 ? 2.5f : 4.0f), times th when th != 1; levels level - 1 .. level;
+ * features with d_occupied set or already matched by a point with observations are skipped; a feature with uRight > 0 is rejected when
+ * |projXR - uRight| > radius; first candidate wins ties; accepted when bestDist <= AMOS_TH_HIGH and not (the two best are on one level and
+ * (float) bestDist > nn_ratio * (float) bestDist2).  A later point may overwrite the match of a point without observations. */
+typedef struct amos_map_point {        /* one MapPoint as isInFrustum / PredictScale / the search read it: 80 bytes */
+    float pos[3];                      /* GetWorldPos() */
+    float normal[3];                   /* GetNormal() */
+    float min_distance, max_distance;  /* mfMinDistance, mfMaxDistance (raw: the 0.8f / 1.2f factors are applied on the device) */
+    int32_t flags;                     /* bit 0: skip (isBad() or mnLastFrameSeen == frame id), bit 1: Observations() > 0 */
+    uint8_t desc[32];                  /* GetDescriptor() */
+    uint8_t pad[12];                   /* to a multiple of 16 bytes */
+} amos_map_point;
+#define AMOS_MAP_POINT_SKIP 1
+#define AMOS_MAP_POINT_HAS_OBS 2
+
+typedef struct amos_local_camera {     /* per frame: 92 bytes */
+    float Rcw[9], tcw[3], Ow[3];       /* Frame::mRcw (row-major), mtcw, mOw */
+    float fx, fy, cx, cy, mbf;
+    float view_cos_limit;              /* 0.5 in Tracking.cc:2365 */
+    float th, nn_ratio;                /* 1 / 3 / 5 and 0.8 in Tracking.cc:2378-2389 */
+} amos_local_camera;
+
+typedef struct amos_local_stats {
+    int32_t n_in_view;                 /* points that passed isInFrustum */
+    int32_t n_matches;                 /* the search's return value */
+    int32_t n_researched;              /* points in view whose window was searched again because a best-two feature had been taken */
+    int32_t status;                    /* a bit mask: 0, or bit 0 (value 1) set: a projection of the frame was not finite */
+} amos_local_stats;
+
+struct amos_map_query;                 /* include/amos_host_types.h: mTrackProjX/Y/XR, mTrackViewCos, mnTrackScaleLevel, has_obs, descriptor */
+
+typedef struct amos_local_search {
+    const amos_keypoint *d_kps;        /* [frames][capacity]: the caller's undistorted keypoints (mvKeysUn) */
+    const uint8_t *d_desc;             /* [frames][capacity][32] */
+    const int32_t *d_counts;           /* [frames] */
+    const int32_t *d_cell_start;       /* [frames][64*48+1]       (amos_frame_grid_build_batch_device) */
+    const int32_t *d_items;            /* [frames][capacity] */
+    const float *d_u_right;            /* [frames][capacity] or NULL (monocular) */
+    const amos_map_point *d_points;    /* frame f owns points [point_off[f], point_off[f + 1]) */
+    const int32_t *point_off;          /* host, n_frames + 1 entries, ascending from >= 0 */
+    const amos_local_camera *cameras;  /* host, n_frames entries */
+    const uint8_t *d_occupied;         /* [frames][capacity]: 1 where F.mvpMapPoints[idx] is set and has Observations() > 0 on entry */
+    const float *scale_factors;        /* host, n_levels entries (mvScaleFactors) */
+    struct amos_map_query *d_query;    /* out, one per point: every tested point is written, the values hold where it is in view */
+    uint8_t *d_in_view;                /* out, one per point: mbTrackInView */
+    int32_t *d_match;                  /* out, [frames][capacity]: index of the matched point inside the frame's own list, or -1 */
+    amos_local_stats *d_stats;         /* out, [frames] */
+    int32_t n_frames, capacity, n_levels;
+    float min_x, max_x, min_y, max_y;  /* Frame::mnMinX .. mnMaxY */
+} amos_local_search;
+/* Asynchronous on the matcher's stream (the two host arrays and the table are consumed before the call returns).  capacity <= 65536: the CSR
+ * position is packed in 16 bits of the reduction key.  AMOS_ERR_INVALID for a NULL argument, a capacity or n_levels out of range, a
+ * point_off that descends or empty image bounds. */
+int amos_match_local_points_batch_device(amos_match *m, const amos_local_search *s);
+/* The host form for a C++ drop-in: ONE frame of n features (mvKeysUn, mDescriptors, mvuRight or
+ * NULL) and n_points map points, host arrays in and out, synchronous: one upload (the grid cells of Frame::PosInGrid are computed on the
+ * way), AssignFeaturesToGrid and the three launches on the device, one download.  occupied [n]; query, in_view [n_points]; match [n]. */
+int amos_match_local_points(amos_match *m, const amos_keypoint *kps_un, const uint8_t *desc, const float *u_right, int n,
+                            const amos_map_point *points, int n_points, const amos_local_camera *camera, const uint8_t *occupied,
+                            const float *scale_factors, int n_levels, float min_x, float max_x, float min_y, float max_y,
+                            struct amos_map_query *query, uint8_t *in_view, int32_t *match, amos_local_stats *stats);
+
 /* ---------------------------------------------------------------- mask pre-processing (8f-4) - */
 
 /* The pre-processing chain of the mask pass on the device, from the raw BGR frame to the network input:
