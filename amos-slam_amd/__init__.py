@@ -83,6 +83,8 @@ PROTOTYPES = {
     "amos_match_window_best2_batch_device": (_i, (_v, _v, _v)),
     "amos_match_local_points_batch_device": (_i, (_v, _v)),
     "amos_match_local_points": (_i, (_v, _v, _v, _v, _i, _v, _i, _v, _v, _v, _i, _f, _f, _f, _f, _v, _v, _v, _v)),
+    "amos_match_motion_model_batch_device": (_i, (_v, _v)),
+    "amos_match_motion_model": (_i, (_v, _v, _v, _v, _i, _v, _i, _v, _v, _i, _f, _f, _f, _f, _v, _v, _v, _v)),
     "amos_mask_pre_create": (_i, (_i, _v, _i, _i, _i, _v)),
     "amos_mask_pre_destroy": (None, (_v,)),
     "amos_mask_pre_stream": (_v, (_v,)),
@@ -844,6 +846,50 @@ class LocalSearch(C.Structure):
                 ("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float)]
 
 
+class LastPoint(C.Structure):
+    """amos_last_point (include/amos_frontend.h): 64 bytes; LAST_POINT_DTYPE is the same record for numpy."""
+    _fields_ = [("pos", C.c_float * 3), ("angle", C.c_float), ("octave", C.c_int32), ("flags", C.c_int32), ("desc", C.c_uint8 * 32),
+                ("pad", C.c_uint8 * 8)]
+
+
+class MotionCamera(C.Structure):
+    """amos_motion_camera: 140 bytes; MOTION_CAMERA_DTYPE is the same record for numpy."""
+    _fields_ = [("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("Rlw", C.c_float * 9), ("tlw", C.c_float * 3), ("fx", C.c_float),
+                ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("mbf", C.c_float), ("mb", C.c_float), ("th", C.c_float),
+                ("th_retry", C.c_float), ("retry_below", C.c_int32), ("mono", C.c_int32), ("check_orientation", C.c_int32)]
+
+
+class MotionStats(C.Structure):
+    """amos_motion_stats: 32 bytes; MOTION_STATS_DTYPE is the same record for numpy."""
+    _fields_ = [("n_projected", C.c_int32), ("n_matches", C.c_int32), ("n_first", C.c_int32), ("pass_", C.c_int32),
+                ("n_researched", C.c_int32), ("flags", C.c_int32), ("status", C.c_int32), ("pad", C.c_int32)]
+
+
+LAST_POINT_SKIP, LAST_POINT_HAS_OBS = 1, 2
+MOTION_FORWARD, MOTION_BACKWARD = 1, 2  # amos_motion_stats.flags
+LAST_POINT_DTYPE = np.dtype([("pos", "<f4", (3,)), ("angle", "<f4"), ("octave", "<i4"), ("flags", "<i4"), ("desc", "u1", (32,)),
+                             ("pad", "u1", (8,))])
+MOTION_CAMERA_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("Rlw", "<f4", (9,)), ("tlw", "<f4", (3,)), ("fx", "<f4"),
+                                ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"), ("mbf", "<f4"), ("mb", "<f4"), ("th", "<f4"),
+                                ("th_retry", "<f4"), ("retry_below", "<i4"), ("mono", "<i4"), ("check_orientation", "<i4")])
+MOTION_STATS_DTYPE = np.dtype([("n_projected", "<i4"), ("n_matches", "<i4"), ("n_first", "<i4"), ("pass", "<i4"), ("n_researched", "<i4"),
+                               ("flags", "<i4"), ("status", "<i4"), ("pad", "<i4")])
+# amos_proj_query (include/amos_host_types.h)
+PROJ_QUERY_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("invz", "<f4"), ("octave", "<i4"), ("angle", "<f4"), ("has_obs", "<i4"),
+                             ("desc", "u1", (32,))])
+assert (C.sizeof(LastPoint), C.sizeof(MotionCamera), C.sizeof(MotionStats)) == (LAST_POINT_DTYPE.itemsize, MOTION_CAMERA_DTYPE.itemsize,
+                                                                                MOTION_STATS_DTYPE.itemsize) == (64, 140, 32)
+
+
+class MotionSearch(C.Structure):
+    """amos_motion_search (include/amos_frontend.h)."""
+    _fields_ = [("d_kps", C.c_void_p), ("d_desc", C.c_void_p), ("d_counts", C.c_void_p), ("d_cell_start", C.c_void_p), ("d_items", C.c_void_p),
+                ("d_u_right", C.c_void_p), ("d_points", C.c_void_p), ("point_off", C.c_void_p), ("cameras", C.c_void_p),
+                ("scale_factors", C.c_void_p), ("d_query", C.c_void_p), ("d_projected", C.c_void_p), ("d_match", C.c_void_p),
+                ("d_stats", C.c_void_p), ("n_frames", C.c_int32), ("capacity", C.c_int32), ("n_levels", C.c_int32), ("min_x", C.c_float),
+                ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float)]
+
+
 class OrbMatcher(_Handle):
     """The distance / best-two primitives every ORBmatcher::Search* inner loop reduces to
     (ORBmatcher.cc:1913-1933 and the candidate loops at :127-148, :278-304, :560-580, :1644-1690)."""
@@ -939,6 +985,38 @@ class OrbMatcher(_Handle):
         _check(self.L.amos_match_local_points(self.h, _p(kps_un), _p(desc), _p(ur), n, _p(points), m, _p(cam), _p(occupied), _p(sf), len(sf),
                                               *bounds, _p(query), _p(in_view), _p(match), _p(stats)), "amos_match_local_points")
         return query, in_view, match, stats[0]
+
+    def motion_model_batch_device(self, d_kps, d_desc, d_counts, d_cell_start, d_items, d_points, point_off, cameras, capacity, scale_factors,
+                                  d_query, d_projected, d_match, d_stats, bounds=(0.0, 640.0, 0.0, 480.0), d_u_right=None):
+        """Tracking::TrackWithMotionModel's search for resident frames: the projection of the last frame's points, SearchByProjection(
+        CurrentFrame, LastFrame, th, bMono) with its rotation histogram, and the second search with th_retry (Tracking.cc:1925-1945,
+        ORBmatcher.cc:1569-1728).  point_off: n_frames + 1 host ints; cameras: host MOTION_CAMERA_DTYPE records, one per frame.
+        Asynchronous on the matcher's stream."""
+        sf = np.ascontiguousarray(scale_factors, np.float32)
+        off = np.ascontiguousarray(point_off, np.int32)
+        cams = np.ascontiguousarray(cameras, MOTION_CAMERA_DTYPE).reshape(-1)
+        if len(off) != len(cams) + 1:
+            raise ValueError("point_off holds one entry more than cameras")
+        s = MotionSearch(d_kps, d_desc, d_counts, d_cell_start, d_items, d_u_right, d_points, off.ctypes.data, cams.ctypes.data,
+                         sf.ctypes.data, d_query, d_projected, d_match, d_stats, len(cams), capacity, len(sf), *bounds)
+        _check(self.L.amos_match_motion_model_batch_device(self.h, C.byref(s)), "amos_match_motion_model_batch_device")
+
+    def motion_model(self, kps_un, desc, points, camera, scale_factors, bounds=(0.0, 640.0, 0.0, 480.0), u_right=None):
+        """The same for ONE frame from host arrays (amos_match_motion_model): returns (query, projected, match, stats)."""
+        kps_un = np.ascontiguousarray(kps_un, KP_DTYPE)
+        desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        points = np.ascontiguousarray(points, LAST_POINT_DTYPE)
+        cam = np.ascontiguousarray(camera, MOTION_CAMERA_DTYPE).reshape(1)
+        sf = np.ascontiguousarray(scale_factors, np.float32)
+        ur = None if u_right is None else np.ascontiguousarray(u_right, np.float32)
+        n, m = len(kps_un), len(points)
+        if len(desc) != n or (ur is not None and len(ur) != n):
+            raise ValueError("desc and u_right hold one entry per keypoint")
+        query, projected = np.zeros(m, PROJ_QUERY_DTYPE), np.zeros(m, np.uint8)
+        match, stats = np.full(n, -1, np.int32), np.zeros(1, MOTION_STATS_DTYPE)
+        _check(self.L.amos_match_motion_model(self.h, _p(kps_un), _p(desc), _p(ur), n, _p(points), m, _p(cam), _p(sf), len(sf), *bounds,
+                                              _p(query), _p(projected), _p(match), _p(stats)), "amos_match_motion_model")
+        return query, projected, match, stats[0]
 
     def sync(self):
         _check(self.L.amos_match_sync(self.h), "amos_match_sync")

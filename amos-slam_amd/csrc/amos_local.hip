@@ -238,44 +238,10 @@ __global__ __launch_bounds__(64) void k_local_accept(const LocalArgs a)
                 nResearched++;
                 const LocalQuery q = load_local_query(a, fr.cam, base + k);
                 const CellRange c = cell_range(q.u, q.v, q.r, a.minX, a.minY, a.wInv, a.hInv);
-                unsigned best = 0xffffffffu, second = 0xffffffffu;
-                // the window's columns (at most 64: the grid has 64) hold one item range each; lane l fetches the range of column x0 + l,
-                // an inclusive scan numbers the items of all columns 0 .. total - 1, and the lanes stride over THAT range: item t lies in
-                // the last column whose first number is <= t (a binary search over the lanes' exclusive sums)
-                const int ncols = c.x1 - c.x0 + 1;
-                int b = 0, e = 0;
-                if (lane < ncols) column_items(cs, c, c.x0 + lane, b, e);
-                const int cnt = e - b;
-                int inc = cnt;
-#pragma unroll
-                for (int off = 1; off < 64; off <<= 1) {
-                    const int v = __shfl_up(inc, off, 64);
-                    if (lane >= off) inc += v;
-                }
-                const int total = __builtin_amdgcn_readlane(inc, 63), exc = inc - cnt;
-                for (int t0 = 0; t0 < total; t0 += 64) {
-                    const int t = t0 + lane;
-                    int col = 0;
-#pragma unroll
-                    for (int step = 32; step > 0; step >>= 1) {  // col + step <= 63
-                        const int ev = __shfl(exc, col + step, 64);
-                        if (ev <= t) col += step;
-                    }
-                    const int cb = __shfl(b, col, 64), ce = __shfl(exc, col, 64);
-                    if (t < total) {
-                        const int j = cb + (t - ce);
-                        const int idx = it[j];
-                        unsigned key;
-                        if (((taken[idx >> 5] >> (idx & 31)) & 1u) == 0 && local_candidate(q, tk, td, tr, idx, j, key)) top2_push(best, second, key);
-                    }
-                }
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) {
-                    const unsigned ob = __shfl_xor(best, off, 64), os = __shfl_xor(second, off, 64);
-                    top2_merge(best, second, ob, os);
-                }
-                best = __builtin_amdgcn_readfirstlane(best);
-                second = __builtin_amdgcn_readfirstlane(second);
+                unsigned best, second;
+                wave_window_best2(cs, it, c, lane, [&](int idx, int j, unsigned &key) {
+                    return ((taken[idx >> 5] >> (idx & 31)) & 1u) == 0 && local_candidate(q, tk, td, tr, idx, j, key);
+                }, best, second);
                 bi = best == 0xffffffffu ? -1 : it[best & 0xffffu];
                 bd = best == 0xffffffffu ? 256 : (int)(best >> 16);
                 si = second == 0xffffffffu ? -1 : it[second & 0xffffu];

@@ -1,6 +1,6 @@
-// amos_match_core.h -- what the matcher's source files share (amos_match.hip, amos_local.hip): the 256-bit descriptor with its load and
-// popcount, the best / second-best key reduction, the cell-range arithmetic of Frame::GetFeaturesInArea (Frame.cc:913-939), and the
-// matcher handle with its staging helpers.
+// amos_match_core.h -- what the matcher's source files share (amos_match.hip, amos_local.hip, amos_motion.hip): the 256-bit descriptor with
+// its load and popcount, the best / second-best key reduction, the cell-range arithmetic of Frame::GetFeaturesInArea (Frame.cc:913-939), the
+// wave-wide search of one window, and the matcher handle with its staging helpers.
 #pragma once
 #include "amos_common.h"
 
@@ -94,6 +94,51 @@ __device__ __forceinline__ void column_items(const int *cs, const CellRange &c, 
     e = c.y1 >= c.y0 ? cs[ix * AMOS_FRAME_GRID_ROWS + c.y1 + 1] : b;
 }
 
+// The best two candidates of a window for a whole wave (the greedy loops of amos_local.hip and amos_motion.hip search a window again with
+// it when the prepass record no longer holds).  All 64 lanes call it converged.  The window's columns (at most 64: the grid has 64) hold
+// one item range each; lane l fetches the range of column x0 + l, an inclusive scan numbers the items of all columns 0 .. total - 1, and
+// the lanes stride over THAT range: item t lies in the last column whose first number is <= t (a binary search over the lanes' exclusive
+// sums).  cand(idx, j, key) says whether feature idx at CSR position j is a candidate and gives its key dist << 16 | j; best / second
+// come back wave-uniform, 0xffffffff for none.
+template <class Cand>
+__device__ __forceinline__ void wave_window_best2(const int *cs, const int *it, const CellRange &c, int lane, Cand cand, unsigned &best, unsigned &second)
+{
+    best = second = 0xffffffffu;
+    const int ncols = c.x1 - c.x0 + 1;
+    int b = 0, e = 0;
+    if (lane < ncols) column_items(cs, c, c.x0 + lane, b, e);
+    const int cnt = e - b;
+    int inc = cnt;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int v = __shfl_up(inc, off, 64);
+        if (lane >= off) inc += v;
+    }
+    const int total = __builtin_amdgcn_readlane(inc, 63), exc = inc - cnt;
+    for (int t0 = 0; t0 < total; t0 += 64) {
+        const int t = t0 + lane;
+        int col = 0;
+#pragma unroll
+        for (int step = 32; step > 0; step >>= 1) {  // col + step <= 63
+            const int ev = __shfl(exc, col + step, 64);
+            if (ev <= t) col += step;
+        }
+        const int cb = __shfl(b, col, 64), ce = __shfl(exc, col, 64);
+        if (t < total) {
+            const int j = cb + (t - ce);
+            unsigned key;
+            if (cand(it[j], j, key)) top2_push(best, second, key);
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned ob = __shfl_xor(best, off, 64), os = __shfl_xor(second, off, 64);
+        top2_merge(best, second, ob, os);
+    }
+    best = __builtin_amdgcn_readfirstlane(best);
+    second = __builtin_amdgcn_readfirstlane(second);
+}
+
 }  // namespace amos
 
 struct amos_match : amos::StreamHandle {
@@ -109,7 +154,8 @@ struct amos_match : amos::StreamHandle {
     uint8_t *dArena = nullptr;  // device mirror of the staging buffer's input part: the inputs of a call travel as ONE transfer (dQ / dT / dOff / dIdx point into it)
     size_t capStage = 0, stageUsed = 0;
     int bfKernel = 0;  // brute-force best-2: 0 = choose by size, 1 = xor + popcount kernel, 2 = i8 MFMA kernel
-    // the local-map search's own scratch (amos_local.hip): per-frame parameters, best-two records and point flags of the call in flight
+    // scratch of the local-map and motion-model searches (amos_local.hip, amos_motion.hip; calls are ordered on the stream): per-frame
+    // parameters, best-two records and point flags of the call in flight
     uint8_t *dLocal = nullptr;
     size_t capLocal = 0;
     uint8_t *hLocal = nullptr;          // pinned: the per-frame parameters on their way to dLocal

@@ -14,8 +14,11 @@
 namespace ORB_SLAM2
 {
 
-// The call itself on a matcher handle that the calling thread owns (created on first use on amos_current_device(), or on AMOS_DEVICE).
-// Returns the number of matches, or -1 with the text in amos_last_error().
+// The matcher handle that the calling thread owns (created on first use on amos_current_device(), or on AMOS_DEVICE; NULL with the text in
+// amos_last_error() when that fails): the tracking thread's searches (this one, FrameMotionModel.h) share it.
+amos_match *ThreadMatcherHandle();
+
+// The call itself on the calling thread's handle.  Returns the number of matches, or -1 with the text in amos_last_error().
 int SearchLocalPointsArrays(const amos_keypoint *keysUn, const uint8_t *descriptors, const float *uRight, int N, const amos_map_point *points,
                             int nPoints, const amos_local_camera &camera, const uint8_t *occupied, const float *scaleFactors, int nLevels,
                             float minX, float maxX, float minY, float maxY, amos_map_query *query, uint8_t *inView, int32_t *match,

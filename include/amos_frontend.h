@@ -437,6 +437,94 @@ int amos_match_local_points(amos_match *m, const amos_keypoint *kps_un, const ui
                             const float *scale_factors, int n_levels, float min_x, float max_x, float min_y, float max_y,
                             struct amos_map_query *query, uint8_t *in_view, int32_t *match, amos_local_stats *stats);
 
+/* ---------------------------------------------------------------- motion-model search ------- */
+
+/* Tracking::TrackWithMotionModel's search (Tracking.cc:1925-1945) for a batch of resident frames: the fill of mvpMapPoints with NULL,
+ * ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) (ORBmatcher.cc:1569-1728) -- projection, window search, greedy loop,
+ * rotation histogram with ComputeThreeMaxima -- and the second search with th_retry when the first returned fewer than retry_below
+ * matches.  Three launches (projection, window search, acceptance) plus two for the second search; nothing returns to the host.
+ *
+ * Arithmetic (PARITY UNPINNED, like the other OpenCV-derived stages): float32, every operation rounded, nothing fused, except
+ *   x3Dc = Rcw * P + tcw     one gemm per row: ((R0 P0 + R1 P1) + R2 P2) + t in double, one rounding to float
+ *   invzc = (float) (1.0 / (double) zc);  invzc < 0 is skipped
+ *   u = ((fx * xc) * invzc) + cx;  v alike
+ *   a u or v that is not finite is skipped and sets bit 0 (value 1) of the frame's status (the reference goes on to convert it to int);
+ *   an octave outside [0, n_levels) is skipped and sets bit 1 (value 2) (the reference indexes mvScaleFactors with it)
+ *   u < min_x || u > max_x || v < min_y || v > max_y is skipped
+ *   twc = -Rcw^T tcw;  tlc = Rlw twc + tlw, one gemm each (host);  bForward = tlc.z > mb && !mono;  bBackward = -tlc.z > mb && !mono
+ * Search: radius th * scale_factors[octave]; levels >= octave when bForward, else 0 .. octave when bBackward, else octave - 1 .. octave + 1
+ * (GetFeaturesInArea's bCheckLevels rule, Frame.cc:894-1003); a feature with uRight > 0 is rejected when |(u - mbf * invzc) - uRight| >
+ * radius; a feature matched by a point with observations is skipped; the first candidate wins ties; accepted when bestDist <=
+ * AMOS_TH_HIGH (no ratio test).  A later point may overwrite the match of a point without observations.
+ * Rotation consistency (check_orientation): rot = angleLast - angleCur, + 360.0f when rot < 0; bin = (int) roundf(rot * (30 / 360.0f)),
+ * 30 becomes 0.  The histogram holds one entry per ACCEPTED POINT (:1683-1698), so a feature that was overwritten is in it once per
+ * accepting point; every entry of a bin that is not one of ComputeThreeMaxima's three (strict comparisons, max2 < 0.1f * max1 drops the
+ * second and third, max3 < 0.1f * max1 the third) sets its feature to -1 and lowers n_matches, unconditionally (:1714-1724).
+ * Second search: when retry_below > 0 and the first search's n_matches (after the pruning) is below it, d_match is reset and the search
+ * runs again from the empty frame with th_retry; its result stands whatever it is. */
+typedef struct amos_last_point {       /* LastFrame feature i as the search reads it: 64 bytes */
+    float pos[3];                      /* LastFrame.mvpMapPoints[i]->GetWorldPos() */
+    float angle;                       /* LastFrame.mvKeysUn[i].angle */
+    int32_t octave;                    /* LastFrame.mvKeys[i].octave */
+    int32_t flags;                     /* bit 0: skip (no map point, or mvbOutlier[i]); bit 1: Observations() > 0 */
+    uint8_t desc[32];                  /* pMP->GetDescriptor() (the map point's, not the feature's) */
+    uint8_t pad[8];
+} amos_last_point;
+#define AMOS_LAST_POINT_SKIP 1
+#define AMOS_LAST_POINT_HAS_OBS 2
+
+typedef struct amos_motion_camera {    /* per frame: 140 bytes */
+    float Rcw[9], tcw[3];              /* CurrentFrame.mTcw (after SetPose(mVelocity * mLastFrame.mTcw)), rotation row-major */
+    float Rlw[9], tlw[3];              /* LastFrame.mTcw */
+    float fx, fy, cx, cy, mbf, mb;
+    float th, th_retry;                /* 15 / 30 (7 / 14 for stereo), Tracking.cc:1929-1944 */
+    int32_t retry_below;               /* 20; 0 = never search again */
+    int32_t mono, check_orientation;   /* bMono; mbCheckOrientation (true in Tracking.cc:1910) */
+} amos_motion_camera;
+
+typedef struct amos_motion_stats {     /* 32 bytes */
+    int32_t n_projected;               /* points that reached GetFeaturesInArea */
+    int32_t n_matches;                 /* the return value of the search whose result stands (may count a feature twice, see above) */
+    int32_t n_first;                   /* the return value of the first search */
+    int32_t pass;                      /* 1 or 2: which radius produced d_match */
+    int32_t n_researched;              /* of the pass that stands: points whose window was searched again because both of its best two were taken */
+    int32_t flags;                     /* bit 0 bForward, bit 1 bBackward */
+    int32_t status;                    /* bit 0: a projection was not finite; bit 1: an octave outside the table */
+    int32_t pad;
+} amos_motion_stats;
+
+struct amos_proj_query;                /* include/amos_host_types.h: u, v, invz, octave, angle, has_obs, descriptor */
+
+typedef struct amos_motion_search {
+    const amos_keypoint *d_kps;        /* [frames][capacity]: the current frames' undistorted keypoints (mvKeysUn) */
+    const uint8_t *d_desc;             /* [frames][capacity][32] */
+    const int32_t *d_counts;           /* [frames] */
+    const int32_t *d_cell_start;       /* [frames][64*48+1]       (amos_frame_grid_build_batch_device) */
+    const int32_t *d_items;            /* [frames][capacity] */
+    const float *d_u_right;            /* [frames][capacity] or NULL (monocular) */
+    const amos_last_point *d_points;   /* frame f owns points [point_off[f], point_off[f + 1]) */
+    const int32_t *point_off;          /* host, n_frames + 1 entries, ascending from >= 0 */
+    const amos_motion_camera *cameras; /* host, n_frames entries */
+    const float *scale_factors;        /* host, n_levels entries (mvScaleFactors) */
+    struct amos_proj_query *d_query;   /* out, one per point: every point is written, u / v / invz hold where it is projected */
+    uint8_t *d_projected;              /* out, one per point: 1 where the point reached GetFeaturesInArea */
+    int32_t *d_match;                  /* out, [frames][capacity]: index of the matched point inside the frame's own list, or -1 (reset by the call) */
+    amos_motion_stats *d_stats;        /* out, [frames] */
+    int32_t n_frames, capacity, n_levels;
+    float min_x, max_x, min_y, max_y;  /* Frame::mnMinX .. mnMaxY */
+} amos_motion_search;
+/* Asynchronous on the matcher's stream (the two host arrays and the table are consumed before the call returns).  capacity <= 65536.
+ * AMOS_ERR_INVALID, before the device is touched, for a NULL handle or argument, a capacity or n_levels out of range, a point_off that
+ * descends or empty image bounds.  Five launches; three when every retry_below is 0. */
+int amos_match_motion_model_batch_device(amos_match *m, const amos_motion_search *s);
+/* The host form for a C++ drop-in (amos-slam_amd/host/FrameMotionModel.h): ONE current frame of n features (mvKeysUn, mDescriptors, mvuRight
+ * or NULL) and n_points last-frame features, host arrays in and out, synchronous: one upload (the grid cells of Frame::PosInGrid are
+ * computed on the way), AssignFeaturesToGrid and the launches on the device, one download.  query, projected [n_points]; match [n]. */
+int amos_match_motion_model(amos_match *m, const amos_keypoint *kps_un, const uint8_t *desc, const float *u_right, int n,
+                            const amos_last_point *points, int n_points, const amos_motion_camera *camera, const float *scale_factors,
+                            int n_levels, float min_x, float max_x, float min_y, float max_y, struct amos_proj_query *query,
+                            uint8_t *projected, int32_t *match, amos_motion_stats *stats);
+
 /* ---------------------------------------------------------------- mask pre-processing (8f-4) - */
 
 /* The pre-processing chain of the mask pass on the device, from the raw BGR frame to the network input:
