@@ -204,12 +204,13 @@ class MaskEngine:
 
     @torch.no_grad()
     def eval_bgr_batch(self, frames_u8, chunk=16):
-        """frames_u8: [B, H, W, 3] uint8 on the engine's device.  Returns [B, H, W] uint8 masks (zeros where
-        the network finds nothing, which is what the reference's caller ends up using, Tracking.cc:305).
-        The network runs on `chunk` frames at a time; pre- and post-processing are per frame."""
+        """frames_u8: [B, H, W, 3] uint8 on the engine's device, any H x W.  Returns [B, 480, 640] uint8 masks, the size
+        eval_bgr returns whatever the frame's (zeros where the network finds nothing, which is what the reference's
+        caller ends up using, Tracking.cc:305).  The network runs on `chunk` frames at a time; pre- and post-processing
+        are per frame."""
         frames = torch.as_tensor(frames_u8, dtype=torch.uint8, device=self.device)
-        B, H, W = frames.shape[:3]
-        out = torch.zeros((B, H, W), dtype=torch.uint8, device=self.device)
+        B = frames.shape[0]
+        out = torch.zeros((B, 480, 640), dtype=torch.uint8, device=self.device)
         for b0 in range(0, B, chunk):
             part = frames[b0:b0 + chunk]
             if self.device.type == "cuda" and self.use_hip_pre:
