@@ -6,7 +6,7 @@
 //     if(dist<bestDist){...} else if(dist<bestDist2){...}
 // loop does (first candidate wins; see DESIGN.md for the proof of equivalence).  No MFMA.
 #include "amos_common.h"
-#include "amos_match_core.h"
+#include "amos_projection_search.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -138,85 +138,36 @@ __global__ __launch_bounds__(256) void k_grid_build(const int *__restrict__ cell
 
 // ---- Frame::GetFeaturesInArea (Frame.cc:894-1003) + the best / second-best loop of
 // ORBmatcher::SearchByProjection(F, LastF) (ORBmatcher.cc:1645-1690) for a batch of (query frame,
-// train frame) pairs, everything resident.  One thread per query keypoint: window of radius
-// th * scaleFactor[octave] around its (projected) position, cells x-major then y, items in insertion
-// order, level gate by mode (0: octave-1..octave+1, 1 forward: >= octave, 2 backward: <= octave),
-// optional right-coordinate gate; first candidate wins ties (strict <).  The greedy "already matched"
-// skip of the reference stays with the caller: the unrestricted best is also the
-// restricted best whenever it is free.
-struct WindowArgs {
-    const amos_keypoint *kps;   // [frames][capacity]
-    const uint8_t *desc;        // [frames][capacity][32]
-    const int *counts;
-    const int *cellStart;       // [frames][3073]
-    const int *items;           // [frames][capacity]
-    const float *queryUv;       // [pairs][capacity][2] or null: the query keypoint's own position
-    const float *queryInvZ;     // [pairs][capacity] or null
-    const float *uRight;        // [frames][capacity] or null
+// train frame) pairs, everything resident: window of radius th * scaleFactor[octave] around the query keypoint's
+// (projected) position, level gate by mode (0: octave-1..octave+1, 1 forward: >= octave, 2 backward: <= octave).  The
+// greedy "already matched" skip of the reference stays with the caller: the unrestricted best is
+// also the restricted best whenever it is free.
+struct WindowArgs : ProjArgs {  // kps, desc, counts: of the query frames too; uRight is null unless queryInvZ is there
+    const float *queryUv;    // [pairs][capacity][2] or null: the query keypoint's own position
+    const float *queryInvZ;  // [pairs][capacity] or null
     const int *pairsQ, *pairsT;
-    float scale[AMOS_MAX_LEVELS];
-    float th, mbf, minX, minY, wInv, hInv;
-    int capacity, mode, initDist;
+    float th, mbf;
+    int mode, initDist;
 };
 
 __global__ __launch_bounds__(256) void k_window_best2(const WindowArgs a, amos_best2 *__restrict__ out)
 {
     const int t = blockIdx.x * 256 + threadIdx.x, pair = blockIdx.y;
-    const int i = t / kWindowLanes, sub = t % kWindowLanes;
-    const int fq = a.pairsQ[pair], ft = a.pairsT[pair];
-    const int nq = min(a.counts[fq], a.capacity);
-    const bool active = i < nq;
-    const int iq = active ? i : 0;  // idle lanes shadow query 0 so that the group shuffles stay convergent
-    const amos_keypoint qk = a.kps[(size_t)fq * a.capacity + iq];
-    const Desc qd = load_desc(a.desc + ((size_t)fq * a.capacity + iq) * 32);
-    const size_t po = (size_t)pair * a.capacity + iq;
-    const float u = a.queryUv ? a.queryUv[2 * po] : qk.x, v = a.queryUv ? a.queryUv[2 * po + 1] : qk.y;
-    const int oct = qk.octave;
-    const float r = __fmul_rn(a.th, a.scale[oct]);
-    const int minLevel = a.mode == 1 ? oct : a.mode == 2 ? 0 : oct - 1;
-    const int maxLevel = a.mode == 1 ? -1 : a.mode == 2 ? oct : oct + 1;
-    const bool checkLevels = minLevel > 0 || maxLevel >= 0;
-    const bool gateRight = a.uRight != nullptr && a.queryInvZ != nullptr;
-    const float ur = gateRight ? __fsub_rn(u, __fmul_rn(a.mbf, a.queryInvZ[po])) : 0.f;
-    const CellRange c = cell_range(u, v, r, a.minX, a.minY, a.wInv, a.hInv);
-    const int *cs = a.cellStart + (size_t)ft * (kGridCells + 1);
-    const int *it = a.items + (size_t)ft * a.capacity;
-    const amos_keypoint *tk = a.kps + (size_t)ft * a.capacity;
-    const uint8_t *td = a.desc + (size_t)ft * a.capacity * 32;
-    const float *tr = gateRight ? a.uRight + (size_t)ft * a.capacity : nullptr;
-    // The reference walks the cells x-major, then y, then insertion order = ascending CSR position, and its
-    // strict-< updates keep the FIRST of equal distances: a min-reduction over keys (dist << 16 | CSR position)
-    // gives the same best and second best whatever the evaluation order.
-    unsigned best = 0xffffffffu, second = 0xffffffffu;
-    for (int ix = c.x0 + sub; ix <= c.x1; ix += kWindowLanes) {
-        int b, e;  // cells (ix, y0..y1) are consecutive in the CSR: one item range per column
-        column_items(cs, c, ix, b, e);
-        for (int j = b; j < e; j++) {
-            const int idx = it[j];
-            const amos_keypoint k = tk[idx];
-            if (checkLevels && (k.octave < minLevel || (maxLevel >= 0 && k.octave > maxLevel))) continue;
-            if (!(fabsf(__fsub_rn(k.x, u)) < r && fabsf(__fsub_rn(k.y, v)) < r)) continue;
-            if (gateRight) {
-                const float tt = tr[idx];
-                if (tt > 0 && fabsf(__fsub_rn(ur, tt)) > r) continue;
-            }
-            const int d = hamming256(qd, load_desc(td + (size_t)idx * 32));
-            if (d < a.initDist) top2_push(best, second, ((unsigned)d << 16) | (unsigned)j);
-        }
+    const int i = t / kWindowLanes;
+    const int fq = a.pairsQ[pair];
+    const bool active = i < min(a.counts[fq], a.capacity);
+    const size_t po = (size_t)pair * a.capacity + i;
+    WindowQuery q;
+    if (active) {
+        const amos_keypoint qk = a.kps[(size_t)fq * a.capacity + i];
+        q.d = load_desc(a.desc + ((size_t)fq * a.capacity + i) * 32);
+        q.u = a.queryUv ? a.queryUv[2 * po] : qk.x;
+        q.v = a.queryUv ? a.queryUv[2 * po + 1] : qk.y;
+        q.ur = a.uRight ? __fsub_rn(q.u, __fmul_rn(a.mbf, a.queryInvZ[po])) : 0.f;
+        q.r = __fmul_rn(a.th, a.scale[qk.octave]);
+        level_window(q, qk.octave, a.mode == 1, a.mode == 2);
     }
-#pragma unroll
-    for (int off = kWindowLanes / 2; off > 0; off >>= 1) {
-        const unsigned ob = __shfl_xor(best, off, kWindowLanes), os = __shfl_xor(second, off, kWindowLanes);
-        top2_merge(best, second, ob, os);
-    }
-    if (active && sub == 0) {
-        amos_best2 res;
-        res.best_idx = best == 0xffffffffu ? -1 : it[best & 0xffffu];
-        res.best_dist = best == 0xffffffffu ? a.initDist : (int)(best >> 16);
-        res.second_idx = second == 0xffffffffu ? -1 : it[second & 0xffffu];
-        res.second_dist = second == 0xffffffffu ? a.initDist : (int)(second >> 16);
-        out[po] = res;
-    }
+    lanes_window_best2(a, frame_view(a, a.pairsT[pair]), q, active, t % kWindowLanes, a.initDist, [](int) { return true; }, active ? out + po : nullptr);
 }
 
 // ---- brute-force best / second best over ALL train descriptors, for a batch of (query set,
@@ -760,13 +711,10 @@ int amos_match_window_best2_batch_device(amos_match *m, const amos_window_search
     }
     AMOS_HIP_CHECK(hipSetDevice(m->device));
     WindowArgs a;
-    a.kps = w->d_kps; a.desc = w->d_desc; a.counts = w->d_counts; a.cellStart = w->d_cell_start; a.items = w->d_items;
-    a.queryUv = w->d_query_uv; a.queryInvZ = w->d_query_invz; a.uRight = w->d_u_right; a.pairsQ = w->d_pairs_q; a.pairsT = w->d_pairs_t;
-    for (int l = 0; l < AMOS_MAX_LEVELS; l++) a.scale[l] = l < w->n_levels ? w->scale_factors[l] : 0.f;
-    a.th = w->th; a.mbf = w->mbf; a.minX = w->min_x; a.minY = w->min_y;
-    a.wInv = static_cast<float>(AMOS_FRAME_GRID_COLS) / static_cast<float>(w->max_x - w->min_x);  // Frame.cc:302-303
-    a.hInv = static_cast<float>(AMOS_FRAME_GRID_ROWS) / static_cast<float>(w->max_y - w->min_y);
-    a.capacity = w->capacity; a.mode = w->mode; a.initDist = w->init_dist;
+    fill_proj_args(a, *w);
+    if (!w->d_query_invz) a.uRight = nullptr;
+    a.queryUv = w->d_query_uv; a.queryInvZ = w->d_query_invz; a.pairsQ = w->d_pairs_q; a.pairsT = w->d_pairs_t;
+    a.th = w->th; a.mbf = w->mbf; a.mode = w->mode; a.initDist = w->init_dist;
     hipLaunchKernelGGL(k_window_best2, dim3((w->capacity * kWindowLanes + 255) / 256, w->n_pairs), dim3(256), 0, m->stream, a, d_out);
     AMOS_HIP_CHECK(hipGetLastError());
     return AMOS_OK;

@@ -1,0 +1,241 @@
+// amos_projection_search.h -- what the projection-window searches share (k_window_best2 of amos_match.hip, the local-map search of
+// amos_local.hip, the motion-model search of amos_motion.hip): Frame::GetFeaturesInArea (Frame.cc:894-1003) plus the best / second-best
+// Hamming loop over a frame's cell CSR, on the device, and the argument filling, validation and staging of their entries on the host.
+// A search itself keeps how it finds its query, its extra filter and its accept rules.
+#pragma once
+#include "amos_match_core.h"
+
+#include <climits>
+#include <cmath>
+#include <vector>
+
+namespace amos {
+
+constexpr int kInitDist = 256;  // bestDist / bestDist2 on entry of the reference's loops (ORBmatcher.cc:125-126, :1645-1646)
+
+// what every search reads of its frames
+struct ProjArgs {
+    const amos_keypoint *kps;               // [frames][capacity]
+    const uint8_t *desc;                    // [frames][capacity][32]
+    const int *counts, *cellStart, *items;  // [frames], [frames][3073], [frames][capacity]
+    const float *uRight;                    // [frames][capacity] or null: no right gate
+    float scale[AMOS_MAX_LEVELS];
+    float minX, maxX, minY, maxY, wInv, hInv;
+    int capacity, nLevels;
+};
+
+// one frame of those arrays
+struct FrameView { const int *cs, *it; const amos_keypoint *tk; const uint8_t *td; const float *tr; };
+__device__ __forceinline__ FrameView frame_view(const ProjArgs &a, int f)
+{
+    const size_t o = (size_t)f * a.capacity;
+    return FrameView{a.cellStart + (size_t)f * (kGridCells + 1), a.items + o, a.kps + o, a.desc + o * 32, a.uRight ? a.uRight + o : nullptr};
+}
+
+// what a search reads of one query
+struct WindowQuery {
+    float u, v, ur, r;  // r: the window's radius
+    int lo, hi;         // the level window, inclusive
+    Desc d;
+};
+
+// GetFeaturesInArea(u, v, r, minLevel, maxLevel) checks levels when minLevel > 0 || maxLevel >= 0 (Frame.cc:945).  Its three uses around
+// an octave as inclusive windows: (octave, -1) forward, (0, octave) backward, (octave - 1, octave + 1) otherwise.
+__device__ __forceinline__ void level_window(WindowQuery &q, int octave, bool forward, bool backward)
+{
+    if (forward) { q.lo = octave > 0 ? octave : INT_MIN; q.hi = INT_MAX; }
+    else if (backward) { q.lo = 0; q.hi = octave; }
+    else { q.lo = octave - 1; q.hi = octave + 1; }
+}
+
+// one candidate of a window (CSR position j): its key dist << 16 | j, or none when a gate rejects it: the level window, the box, the right
+// gate (ORBmatcher.cc:132-137, :1662-1669) and the loops' strict dist < initDist.  Occupancy and bitmap filters are the caller's.
+__device__ __forceinline__ bool window_candidate(const WindowQuery &q, const FrameView &fv, int idx, int j, int initDist, unsigned &key)
+{
+    const amos_keypoint k = fv.tk[idx];
+    if (k.octave < q.lo || k.octave > q.hi) return false;
+    if (!(fabsf(__fsub_rn(k.x, q.u)) < q.r && fabsf(__fsub_rn(k.y, q.v)) < q.r)) return false;
+    if (fv.tr) {
+        const float tt = fv.tr[idx];
+        if (tt > 0 && fabsf(__fsub_rn(q.ur, tt)) > q.r) return false;
+    }
+    const int d = hamming256(q.d, load_desc(fv.td + (size_t)idx * 32));
+    key = ((unsigned)d << 16) | (unsigned)j;
+    return d < initDist;  // (the last gate is no early return: the push behind it stays a select)
+}
+
+// keys dist << 16 | CSR position -> the record
+__device__ __forceinline__ amos_best2 best2_from_keys(unsigned best, unsigned second, const int *it, int noneDist)
+{
+    amos_best2 r;
+    r.best_idx = best == 0xffffffffu ? -1 : it[best & 0xffffu];
+    r.best_dist = best == 0xffffffffu ? noneDist : (int)(best >> 16);
+    r.second_idx = second == 0xffffffffu ? -1 : it[second & 0xffffu];
+    r.second_dist = second == 0xffffffffu ? noneDist : (int)(second >> 16);
+    return r;
+}
+
+// The prepass of a search: kWindowLanes lanes per query, lane `sub` of them walks every kWindowLanes-th grid column of the window.  The
+// reference walks the cells x-major, then y, then insertion order = ascending CSR position, and its strict-< updates keep the FIRST of
+// equal distances: a min-reduction over keys (dist << 16 | CSR position) gives the same best two whatever the evaluation order.  All lanes
+// of a group call it; q is read only where `active`, the group's first lane writes *out (if not null); keep(idx) is the search's own filter.
+template <class Keep>
+__device__ __forceinline__ void lanes_window_best2(const ProjArgs &a, const FrameView &fv, const WindowQuery &q, bool active, int sub, int initDist,
+                                                   Keep keep, amos_best2 *out)
+{
+    CellRange c;
+    c.x0 = 0; c.x1 = -1; c.y0 = c.y1 = 0;  // idle lanes walk no column and keep the group shuffles convergent
+    if (active) c = cell_range(q.u, q.v, q.r, a.minX, a.minY, a.wInv, a.hInv);
+    unsigned best = 0xffffffffu, second = 0xffffffffu;
+    for (int ix = c.x0 + sub; ix <= c.x1; ix += kWindowLanes) {
+        int b, e;  // cells (ix, y0..y1) are consecutive in the CSR: one item range per column
+        column_items(fv.cs, c, ix, b, e);
+        for (int j = b; j < e; j++) {
+            const int idx = fv.it[j];
+            unsigned key;
+            if (keep(idx) && window_candidate(q, fv, idx, j, initDist, key)) top2_push(best, second, key);
+        }
+    }
+#pragma unroll
+    for (int off = kWindowLanes / 2; off > 0; off >>= 1) {
+        const unsigned ob = __shfl_xor(best, off, kWindowLanes), os = __shfl_xor(second, off, kWindowLanes);
+        top2_merge(best, second, ob, os);
+    }
+    if (out && sub == 0) *out = best2_from_keys(best, second, fv.it, initDist);
+}
+
+constexpr int kTakenWords = 65536 / 32;  // the features a greedy loop has taken, one bit each, in LDS (capacity <= 65536)
+struct TakenBitmap {
+    uint32_t w[kTakenWords];
+    __device__ __forceinline__ bool test(int i) const { return (w[i >> 5] >> (i & 31)) & 1u; }
+    // feature i, or feature j >= 0, is taken: both words are read before either is looked at, one LDS round trip in a sequential loop
+    __device__ __forceinline__ bool either(int i, int j) const { const uint32_t a = w[i >> 5], b = w[max(j, 0) >> 5]; return ((a >> (i & 31)) | (j >= 0 ? b >> (j & 31) : 0u)) & 1u; }
+    __device__ __forceinline__ void set(int i) { w[i >> 5] |= 1u << (i & 31); }
+};
+
+// the whole wave searches a query's window again, against the bitmap; the record comes back wave-uniform
+__device__ __forceinline__ amos_best2 wave_research(const ProjArgs &a, const FrameView &fv, const WindowQuery &q, const TakenBitmap &taken, int lane)
+{
+    const CellRange c = cell_range(q.u, q.v, q.r, a.minX, a.minY, a.wInv, a.hInv);
+    unsigned best, second;
+    wave_window_best2(fv.cs, fv.it, c, lane, [&](int idx, int j, unsigned &key) {
+        return !taken.test(idx) && window_candidate(q, fv, idx, j, kInitDist, key);
+    }, best, second);
+    return best2_from_keys(best, second, fv.it, kInitDist);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- host
+
+inline size_t align64(size_t n) { return (n + 63) & ~(size_t)63; }
+
+// S: amos_window_search, amos_local_search or amos_motion_search
+template <class S>
+inline void fill_proj_args(ProjArgs &a, const S &s)
+{
+    a.kps = s.d_kps; a.desc = s.d_desc; a.counts = s.d_counts; a.cellStart = s.d_cell_start; a.items = s.d_items; a.uRight = s.d_u_right;
+    for (int l = 0; l < AMOS_MAX_LEVELS; l++) a.scale[l] = l < s.n_levels ? s.scale_factors[l] : 0.f;
+    a.minX = s.min_x; a.maxX = s.max_x; a.minY = s.min_y; a.maxY = s.max_y;
+    a.wInv = static_cast<float>(AMOS_FRAME_GRID_COLS) / static_cast<float>(s.max_x - s.min_x);  // Frame.cc:302-303
+    a.hInv = static_cast<float>(AMOS_FRAME_GRID_ROWS) / static_cast<float>(s.max_y - s.min_y);
+    a.capacity = s.capacity; a.nLevels = s.n_levels;
+}
+
+// what the batch entries of the point searches check alike (own: the entry's own pointers are there) -> the most points of a frame, of all
+template <class S>
+inline int check_point_search(const char *name, const amos_match *m, const S *s, bool own, int *maxPoints, size_t *total)
+{
+    if (!m || !s || !own || !s->d_kps || !s->d_desc || !s->d_counts || !s->d_cell_start || !s->d_items || !s->d_points || !s->point_off ||
+        !s->cameras || !s->scale_factors || !s->d_query || !s->d_match || !s->d_stats || s->n_frames < 1 || s->capacity < 1 ||
+        s->capacity > 65536 || s->n_levels < 1 || s->n_levels > AMOS_MAX_LEVELS || !(s->max_x > s->min_x) || !(s->max_y > s->min_y)) {
+        set_error("%s: invalid argument", name);
+        return AMOS_ERR_INVALID;
+    }
+    *maxPoints = 0;
+    if (s->point_off[0] < 0) { set_error("%s: point_off[0] < 0", name); return AMOS_ERR_INVALID; }
+    for (int f = 0; f < s->n_frames; f++) {
+        if (s->point_off[f + 1] < s->point_off[f]) { set_error("%s: point_off descends at %d", name, f); return AMOS_ERR_INVALID; }
+        *maxPoints = std::max(*maxPoints, s->point_off[f + 1] - s->point_off[f]);
+    }
+    *total = (size_t)s->point_off[s->n_frames];
+    return AMOS_OK;
+}
+
+// The per-frame parameters of a call to the front of dLocal, through the handle's own pinned buffer: the previous call's copy out of it
+// has to be over before it is written again (an event, not a stream synchronisation: the kernels behind that copy are not waited for).
+inline int upload_frames(amos_match *m, const void *frames, size_t bytes)
+{
+    if (!m->localCopied) AMOS_HIP_CHECK(hipEventCreateWithFlags(&m->localCopied, hipEventDisableTiming));
+    else AMOS_HIP_CHECK(hipEventSynchronize(m->localCopied));
+    if (bytes > m->capHLocal) {
+        if (m->hLocal) (void)hipHostFree(m->hLocal);
+        m->hLocal = nullptr;
+        m->capHLocal = 0;
+        const size_t n = std::max<size_t>(2 * bytes, 4096);
+        AMOS_HIP_CHECK(hipHostMalloc((void **)&m->hLocal, n, hipHostMallocDefault));
+        m->capHLocal = n;
+    }
+    std::memcpy(m->hLocal, frames, bytes);
+    AMOS_HIP_CHECK(hipMemcpyAsync(m->dLocal, m->hLocal, bytes, hipMemcpyHostToDevice, m->stream));
+    AMOS_HIP_CHECK(hipEventRecord(m->localCopied, m->stream));
+    return AMOS_OK;
+}
+
+// The one-frame host forms of the point searches (S: amos_local_search, amos_motion_search): ONE frame of n features and n_points points,
+// host arrays in and out.  Lays out the result buffer (query records, one byte per point, match, stats: the download; then the grid),
+// computes Frame::PosInGrid, stages the frame's arrays and fills the fields of S that both kinds have; own(s, d_flag, zeros) stages the entry's
+// own inputs (ownBytes of them) and fills its own fields; then one upload, AssignFeaturesToGrid, the batch form, one download, the copy-out.
+template <class S, class Own>
+inline int one_frame_search(amos_match *m, int (*batch)(amos_match *, const S *), const amos_keypoint *kps_un, const uint8_t *desc,
+                            const float *u_right, int n, int n_points, size_t ownBytes, const float *scale_factors, int n_levels, float min_x,
+                            float max_x, float min_y, float max_y, void *query, uint8_t *flag, int32_t *match, void *stats, Own own)
+{
+    S s;
+    const size_t querySize = sizeof(*s.d_query), statsSize = sizeof(*s.d_stats);
+    AMOS_HIP_CHECK(hipSetDevice(m->device));
+    const int cap = std::max(n, 1);
+    const size_t np = (size_t)n_points, np1 = std::max<size_t>(np, 1);
+    const size_t oFlag = align64(querySize * np1), oMatch = oFlag + align64(np1), oStats = oMatch + align64(sizeof(int32_t) * (size_t)cap),
+                 oEnd = oStats + align64(statsSize), oItems = oEnd + align64(sizeof(int32_t) * (kGridCells + 1)),
+                 oAll = oItems + align64(sizeof(int32_t) * (size_t)cap);
+    int rc = stage_begin(m, (size_t)cap * (sizeof(amos_keypoint) + 32 + 4 + 4) + 64 + ownBytes + oEnd);
+    if (rc != AMOS_OK) return rc;
+    rc = grow_out(m, oAll);
+    if (rc != AMOS_OK) return rc;
+    // Frame::PosInGrid (Frame.cc:1007-1030)
+    const float wInv = static_cast<float>(AMOS_FRAME_GRID_COLS) / static_cast<float>(max_x - min_x);
+    const float hInv = static_cast<float>(AMOS_FRAME_GRID_ROWS) / static_cast<float>(max_y - min_y);
+    std::vector<int32_t> cell((size_t)cap, -1);
+    for (int i = 0; i < n; i++) {
+        const int px = (int)roundf((kps_un[i].x - min_x) * wInv), py = (int)roundf((kps_un[i].y - min_y) * hInv);
+        if (px >= 0 && px < AMOS_FRAME_GRID_COLS && py >= 0 && py < AMOS_FRAME_GRID_ROWS) cell[i] = px * AMOS_FRAME_GRID_ROWS + py;
+    }
+    const std::vector<uint8_t> zeros(std::max<size_t>((size_t)cap * 32, 256), 0);  // a frame without features or points still hands valid arrays down
+    const int32_t count = n, off[2] = {0, n_points};
+    uint8_t *out = (uint8_t *)m->dOut;
+    s.d_kps = stage_input<amos_keypoint>(m, n ? (const void *)kps_un : zeros.data(), sizeof(amos_keypoint) * (size_t)cap);
+    s.d_desc = stage_input<uint8_t>(m, n ? desc : zeros.data(), (size_t)cap * 32);
+    s.d_u_right = u_right && n ? stage_input<float>(m, u_right, sizeof(float) * (size_t)cap) : nullptr;
+    const int32_t *dCell = stage_input<int32_t>(m, cell.data(), sizeof(int32_t) * (size_t)cap);
+    s.d_counts = stage_input<int32_t>(m, &count, sizeof(count));
+    s.d_cell_start = (int32_t *)(out + oEnd); s.d_items = (int32_t *)(out + oItems);
+    s.point_off = off; s.scale_factors = scale_factors;
+    s.d_query = (decltype(s.d_query))out; s.d_match = (int32_t *)(out + oMatch); s.d_stats = (decltype(s.d_stats))(out + oStats);
+    s.n_frames = 1; s.capacity = cap; s.n_levels = n_levels;
+    s.min_x = min_x; s.max_x = max_x; s.min_y = min_y; s.max_y = max_y;
+    own(s, out + oFlag, zeros.data());
+    int32_t *dStart = (int32_t *)(out + oEnd), *dItems = (int32_t *)(out + oItems);
+    if ((rc = stage_flush(m)) != AMOS_OK || (rc = amos_frame_grid_build_batch_device(m, dCell, s.d_counts, 1, cap, dStart, dItems)) != AMOS_OK ||
+        (rc = batch(m, &s)) != AMOS_OK) return rc;
+    const uint8_t *h = m->hStage + stage_take(m, oEnd);
+    AMOS_HIP_CHECK(hipMemcpyAsync((void *)h, out, oEnd, hipMemcpyDeviceToHost, m->stream));
+    AMOS_HIP_CHECK(hipStreamSynchronize(m->stream));
+    if (np) {
+        std::memcpy(query, h, querySize * np);
+        std::memcpy(flag, h + oFlag, np);
+    }
+    if (n) std::memcpy(match, h + oMatch, sizeof(int32_t) * (size_t)n);
+    std::memcpy(stats, h + oStats, statsSize);
+    return AMOS_OK;
+}
+
+}  // namespace amos

@@ -79,18 +79,61 @@ def frustum(points, cam, scale_factors, bounds):
     return q, in_view, status, reason
 
 
+def search_python(view, kps, desc, u_right, queries, occupied, scale_factors, th, nn_ratio):
+    """The greedy loop of ORBmatcher.cc:77-172 in plain Python; only the window (Frame::GetFeaturesInArea) is the oracle's.  Beside the
+    live loop it keeps each point's ENTRY record: the best two of its window against the frame as it stands on entry (`occupied`).
+    -> (nmatches, match [len(kps)] = query index or -1, n_researched: the points that have a candidate on entry and whose entry best or
+    entry second best is taken when their turn comes, as include/amos_frontend.h states it)."""
+    sf = np.asarray(scale_factors, f32)
+    bits = np.unpackbits(np.ascontiguousarray(desc, np.uint8).reshape(-1, 32), axis=1)
+    taken = np.asarray(occupied, np.uint8) != 0
+    entry_free = ~taken
+    match = np.full(len(kps), -1, np.int32)
+    nmatches = n_researched = 0
+
+    def best_two(cand, dist, free):  # strict <, from 256: the first of equal distances wins, a distance of 256 never does
+        order = [k for k in np.argsort(dist, kind="stable") if free[cand[k]] and dist[k] < 256][:2]
+        return [(int(cand[k]), int(dist[k])) for k in order]
+    for i, p in enumerate(queries):
+        level = int(p["level"])
+        r = f32(2.5) if float(p["view_cos"]) > 0.998 else f32(4.0)
+        if f32(th) != f32(1.0):
+            r = f32(r * f32(th))
+        r = f32(r * sf[level])
+        cand = hb.oracle_features_in_area(view, float(p["proj_x"]), float(p["proj_y"]), float(r), level - 1, level)
+        if u_right is not None:
+            ur = np.asarray(u_right, f32)[cand]
+            cand = cand[~((ur > 0) & (np.abs(f32(p["proj_xr"]) - ur) > r))]
+        dist = (bits[cand] != np.unpackbits(p["desc"])).sum(1)
+        entry, now = best_two(cand, dist, entry_free), best_two(cand, dist, ~taken)
+        n_researched += bool(entry) and any(taken[c] for c, _ in entry)
+        if not now or now[0][1] > 100:
+            continue
+        (best, bd), (second, sd) = now[0], now[1] if len(now) > 1 else (-1, 256)
+        if second >= 0 and kps["octave"][best] == kps["octave"][second] and f32(bd) > f32(nn_ratio) * f32(sd):
+            continue
+        match[best] = i
+        taken[best] = p["has_obs"] != 0
+        nmatches += 1
+    return nmatches, match, int(n_researched)
+
+
 def search_local_points(kps, desc, u_right, points, cam, occupied, scale_factors, bounds):
-    """-> dict(query, in_view, match [len(kps)] = index into `points` or -1, n_in_view, n_matches, status)."""
+    """-> dict(query, in_view, match [len(kps)] = index into `points` or -1, n_in_view, n_matches, n_researched, status): the oracle's
+    search, and n_researched from the Python loop once that loop has reproduced the oracle's matches."""
     q, in_view, status, reason = frustum(points, cam, scale_factors, bounds)
     idx = np.nonzero(in_view)[0]
     match = np.full(len(kps), -1, np.int32)
-    n_matches = 0
+    n_matches = n_researched = 0
     if len(idx) and len(kps):
         view, keep = hb.frame_view(kps, desc, u_right, tuple(float(b) for b in bounds))
         n_matches, m, _ = hb.search_points("oracle", view, q[idx], match, np.asarray(occupied, np.uint8), scale_factors, float(cam["th"]),
                                            float(cam["nn_ratio"]))
+        n_py, m_py, n_researched = search_python(view, kps, desc, u_right, q[idx], occupied, scale_factors, cam["th"], cam["nn_ratio"])
+        assert n_py == n_matches and np.array_equal(m_py, m)
         match = np.where(m >= 0, idx[np.maximum(m, 0)], -1).astype(np.int32)
-    return dict(query=q, in_view=in_view, reason=reason, match=match, n_in_view=int(in_view.sum()), n_matches=int(n_matches), status=status)
+    return dict(query=q, in_view=in_view, reason=reason, match=match, n_in_view=int(in_view.sum()), n_matches=int(n_matches),
+                n_researched=n_researched, status=status)
 
 
 # ---------------------------------------------------------------------------------------------------------------- scenes

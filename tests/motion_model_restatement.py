@@ -117,8 +117,9 @@ def rotation_bin(angle_last, angle_cur):
 
 def search_python(kps, desc, u_right, queries, scale_factors, mbf, th, forward, backward, check_ori, bounds):
     """The greedy loop of ORBmatcher.cc:1595-1702 and the pruning of :1706-1726 in plain Python, from the empty frame; only the window
-    (Frame::GetFeaturesInArea) is the oracle's.  -> (nmatches, match [len(kps)] = query index or -1, windows in which both the best and the
-    second best feature were taken when their point came up)."""
+    (Frame::GetFeaturesInArea) is the oracle's.  -> (nmatches, match [len(kps)] = query index or -1, n_researched: the points whose entry
+    best and entry second best -- the best two of their window in the empty frame, a distance of 256 never being one -- are both taken
+    when their turn comes, as include/amos_frontend.h states it)."""
     queries = np.ascontiguousarray(queries, hb.PROJ_QUERY)
     view, keep = hb.frame_view(kps, desc, u_right, tuple(float(b) for b in bounds))
     sf = np.asarray(scale_factors, f32)
@@ -140,6 +141,8 @@ def search_python(kps, desc, u_right, queries, scale_factors, mbf, th, forward, 
                 if abs(f32(ur - f32(u_right[i2]))) > radius:
                     continue
             d = int(np.abs(bits[i2] - pbits).sum())
+            if d >= 256:  # strict < from 256: never a best or a second best
+                continue
             everything.append((d, i2))
             if not taken[i2]:
                 free.append((d, i2))
@@ -199,6 +202,19 @@ def search_motion_model(kps, desc, u_right, points, cam, scale_factors, bounds, 
     match = np.where(m >= 0, idx[np.maximum(m, 0)] if len(idx) else -1, -1).astype(np.int32)
     return dict(query=q, projected=projected, match=match, n_projected=int(projected.sum()), n_matches=r["n_matches"], n_first=r["n_first"],
                 flags=flags, status=status, **{"pass": r["pass"]})
+
+
+def researched(kps, desc, u_right, cam, scale_factors, bounds, result):
+    """n_researched of a search_motion_model result: search_python's count for the pass that stands, once it has reproduced that pass."""
+    idx = np.nonzero(result["projected"])[0]
+    if len(idx) == 0 or len(kps) == 0:
+        return 0
+    flags = result["flags"]
+    n, m, both_taken = search_python(kps, desc, u_right, result["query"][idx], scale_factors, float(cam["mbf"]),
+                                     float(cam["th_retry"] if result["pass"] == 2 else cam["th"]), flags & FORWARD, flags & BACKWARD,
+                                     int(cam["check_orientation"]), bounds)
+    assert n == result["n_matches"] and np.array_equal(np.where(m >= 0, idx[np.maximum(m, 0)], -1), result["match"])
+    return both_taken
 
 
 # ---------------------------------------------------------------------------------------------------------------- scenes

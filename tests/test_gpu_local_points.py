@@ -1,5 +1,5 @@
 """amos_match_local_points_batch_device / amos_match_local_points on the GPU against the numpy restatement + CPU oracle
-(tests/local_points_restatement.py), bit for bit: every field of d_query where in view, d_in_view, d_match, n_in_view, n_matches."""
+(tests/local_points_restatement.py), bit for bit: every field of d_query where in view, d_in_view, d_match and every stat."""
 import numpy as np
 import pytest
 
@@ -90,7 +90,7 @@ def check(pkg, frames, points, cams, occupied, sf, bounds, with_ur):
         want.append(w)
         a, b = off[f], off[f + 1]
         print(f"frame {f}: {b - a} points, in view {w['n_in_view']} / {stats['n_in_view'][f]}, matches {w['n_matches']} / {stats['n_matches'][f]}, "
-              f"researched {stats['n_researched'][f]}")
+              f"researched {w['n_researched']} / {stats['n_researched'][f]}")
         assert np.array_equal(in_view[a:b], w["in_view"]), f
         iv = w["in_view"] == 1
         for name in ("proj_x", "proj_y", "proj_xr", "view_cos", "level", "has_obs", "desc"):
@@ -98,6 +98,7 @@ def check(pkg, frames, points, cams, occupied, sf, bounds, with_ur):
         assert np.array_equal(match[f, :len(k)], w["match"]), f
         assert (match[f, len(k):] == -1).all()
         assert (stats["n_in_view"][f], stats["n_matches"][f], stats["status"][f]) == (w["n_in_view"], w["n_matches"], w["status"]), f
+        assert stats["n_researched"][f] == w["n_researched"], f
     return stats, want
 
 
@@ -199,6 +200,23 @@ def test_hand_cases(gpu_lib):
     stats, want = check(gpu_lib, frames, points, cams, no_occupancy(frames), lr.HAND_SCALE, lr.HAND_BOUNDS, False)
     for f, (name, (_, _, in_view, status, levels, matches)) in enumerate(cases.items()):
         assert list(want[f]["in_view"]) == in_view and stats["status"][f] == status, name
+
+
+def test_a_complement_is_no_second_best(gpu_lib):
+    """One point in view, two level-0 features inside its window: one 40 bits from the point's descriptor, one its bitwise complement, at
+    distance 256.  Both loops of the reference start at 256 with strict <, so the complement is never the second best, bestLevel2 stays -1
+    and the ratio test does not apply: the match stands although 40 > 0.1 * 256."""
+    kps = np.zeros(2, gpu_lib.KP_DTYPE)
+    kps["x"], kps["y"], kps["size"], kps["octave"] = [321.0, 319.0], [240.0, 240.0], 31.0, 0
+    point = np.zeros(1, lr.MAP_POINT)
+    point["pos"], point["normal"], point["max_distance"], point["flags"] = [0, 0, 2.0], [0, 0, 1.0], 1.9, lr.HAS_OBS
+    point["desc"] = np.random.default_rng(40).integers(0, 256, 32, dtype=np.uint8)
+    desc = np.stack([point["desc"][0], ~point["desc"][0]])
+    desc[0, :5] ^= 0xFF  # 40 bits
+    cam = lr.camera(np.eye(3, dtype=np.float32), np.zeros(3, np.float32), 512.0, 512.0, 320.0, 240.0, nn_ratio=0.1)
+    frames = [(kps, desc, np.full(2, -1, np.float32))]
+    stats, want = check(gpu_lib, frames, [point], [cam], no_occupancy(frames), lr.HAND_SCALE, lr.HAND_BOUNDS, False)
+    assert list(want[0]["in_view"]) == [1] and list(want[0]["match"]) == [0, -1] and stats["n_matches"][0] == 1
 
 
 @pytest.mark.parametrize("with_ur", [True, False])

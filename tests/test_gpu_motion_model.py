@@ -1,6 +1,6 @@
 """amos_match_motion_model_batch_device / amos_match_motion_model on the GPU against the numpy restatement + CPU oracle
 (tests/motion_model_restatement.py), bit for bit: every field of d_query where projected, d_projected, d_match with its padding, and every
-stat except n_researched."""
+stat."""
 import numpy as np
 import pytest
 
@@ -111,6 +111,7 @@ def check(pkg, frames, points, cams, sf, bounds, with_ur):
         assert (match[f, len(k):] == -1).all()
         assert tuple(int(stats[name][f]) for name in STAT_FIELDS) == tuple(int(w[name]) for name in STAT_FIELDS), f
         assert stats["pad"][f] == 0 and stats["n_researched"][f] >= 0
+        assert stats["n_researched"][f] == mr.researched(k, d, r if with_ur else None, cams[f], sf, bounds, w), f
     return stats, want
 
 
@@ -236,3 +237,50 @@ def test_batch_of_one_equals_the_frame_inside_a_batch_of_two(gpu_lib, scenes):
         n = len(sc["frames"][f][0])
         assert np.array_equal(p1, p2[a:b]) and q1[p1 == 1].tobytes() == q2[a:b][p1 == 1].tobytes()
         assert np.array_equal(m1[0, :n], m2[f, :n]) and tuple(s1[0]) == tuple(s2[f])
+
+
+@pytest.mark.parametrize("with_ur", [True, False])
+@pytest.mark.parametrize("motion", ["sideways", "forward", "backward"])
+def test_the_window_search_rebuilds_the_match(gpu_lib, scenes, motion, with_ur):
+    """Across the search families: with no observations and no orientation check nothing is ever taken, so d_match is a pure function of the
+    prepass.  amos_match_window_best2_batch_device on the same projections, its query frame built from the points (keypoint i carries point
+    i's octave and descriptor), gives the records, and the last point in list order whose best is feature i within TH_HIGH is d_match[i]."""
+    import torch
+    sc = scenes["small"]
+    (k, d, r), sf, bounds = sc["frames"][0], sc["sf"], sc["bounds"]
+    cam = cameras_of(sc, motion, th=7.0, check_orientation=0)[0]
+    points = scene_points(sc, (300, 0), seed=11)[0]
+    points["flags"] &= ~mr.HAS_OBS
+    query, projected, match, stats, _ = run_device(gpu_lib, [(k, d, r)], [points], [cam], sf, bounds, with_ur)
+    assert stats["n_researched"][0] == 0 and stats["flags"][0] == mr.MOTION_FLAGS[motion] and stats["n_matches"][0] > 30
+    n, m = len(k), len(points)
+    cap = max(n, m) + 5
+    kps, desc = np.zeros((2, cap), gpu_lib.KP_DTYPE), np.zeros((2, cap, 32), np.uint8)  # frame 0: the current frame, frame 1: the points
+    ur, cell = np.full((2, cap), -1, np.float32), np.full((2, cap), -1, np.int32)
+    kps[0, :n], desc[0, :n], ur[0, :n], cell[0, :n] = k, d, r, lr.grid_cells(k, bounds)
+    kps["octave"][1, :m], desc[1, :m] = points["octave"], points["desc"]
+    uv, invz = np.zeros((1, cap, 2), np.float32), np.zeros((1, cap), np.float32)
+    uv[0, :m, 0], uv[0, :m, 1], invz[0, :m] = query["u"], query["v"], query["invz"]
+
+    def up(a):
+        return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).cuda()
+    d_kps, d_desc, d_ur, d_cell, d_uv, d_invz = (up(a) for a in (kps, desc, ur, cell, uv, invz))
+    d_counts, d_pq, d_pt = up(np.array([n, m], np.int32)), up(np.array([1], np.int32)), up(np.array([0], np.int32))
+    d_start = torch.zeros((2, 64 * 48 + 1), dtype=torch.int32, device="cuda")
+    d_items = torch.full((2, cap), -1, dtype=torch.int32, device="cuda")
+    d_out = torch.zeros((cap, 4), dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    mt = gpu_lib.OrbMatcher()
+    mt.grid_build_batch_device(d_cell.data_ptr(), d_counts.data_ptr(), 2, cap, d_start.data_ptr(), d_items.data_ptr())
+    mt.window_best2_batch_device(d_kps.data_ptr(), d_desc.data_ptr(), d_counts.data_ptr(), d_start.data_ptr(), d_items.data_ptr(), d_pq.data_ptr(),
+                                 d_pt.data_ptr(), 1, cap, sf, float(cam["th"]), d_out.data_ptr(), mode={0: 0, mr.FORWARD: 1, mr.BACKWARD: 2}[int(stats["flags"][0])],
+                                 bounds=bounds, d_query_uv=d_uv.data_ptr(), d_query_invz=d_invz.data_ptr(),
+                                 d_u_right=d_ur.data_ptr() if with_ur else None, mbf=float(cam["mbf"]))
+    mt.sync()
+    best2 = d_out.cpu().numpy()[:m]  # best_idx, best_dist, second_idx, second_dist
+    mt.close()
+    rebuilt = np.full(n, -1, np.int32)
+    for i in np.nonzero(projected)[0]:
+        if best2[i, 0] >= 0 and best2[i, 1] <= mr.TH_HIGH:
+            rebuilt[best2[i, 0]] = i
+    assert np.array_equal(rebuilt, match[0, :n])
