@@ -128,6 +128,9 @@ PROTOTYPES = {
     "amos_mask_post_workspace_bytes": (_z, (_i, _i, _i, _i, _i, _i)),
     "amos_mask_person_masks_device": (_i, (_v, _v, _v, _v, _v, _v, _i, _i, _i, _i, _i, _i, _i, _i, _v, _z, _v, _v)),
     "amos_mask_person_masks_scores_device": (_i, (_v, _v, _v, _v, _v, _v, _i, _i, _i, _i, _i, _i, _i, _i, _v, _z, _v, _v)),
+    "amos_mask_coef_at_priors_device": (_i, (_v, _v, _v, _v, _v, _v, _i, _i, _v, _v, _v, _i, _i, _i, _i, _v)),
+    "amos_mask_person_masks_at_priors_device": (_i, (_v, _v, _v, _v, _v, _v, _v, _v, _i, _i, _i, _v, _v, _v, _v, _i, _i, _i, _i, _i, _i, _i, _i, _v, _z, _v, _v)),
+    "amos_mask_person_masks_scores_at_priors_device": (_i, (_v, _v, _v, _v, _v, _v, _v, _v, _i, _i, _i, _v, _v, _v, _v, _i, _i, _i, _i, _i, _i, _i, _i, _v, _z, _v, _v)),
     "amos_slic_center_count": (_i, (_i, _i, _i, _v, _v)),
     "amos_slic_create": (_i, (_i, _v, _i, _i, _i, _v)),
     "amos_slic_destroy": (None, (_v,)),
@@ -767,6 +770,36 @@ def mask_person_masks(stream_ptr, loc_ptr, conf_ptr, coef_ptr, priors_ptr, proto
     _check(lib().amos_mask_person_masks_device(stream_ptr, loc_ptr, conf_ptr, coef_ptr, priors_ptr, proto_ptr, batch, n_priors, n_classes_with_background, mask_dim,
                                                proto_h, proto_w, out_h, out_w, workspace_ptr, workspace_bytes, masks_ptr, found_ptr),
            "amos_mask_person_masks_device")
+
+
+def _coef_levels(level_ptrs, level_hw, level_blocked, anchors):
+    """The host arrays amos_mask_coef_at_priors_device reads: (pointers, heights, widths, blocked flags, prior offsets, count)"""
+    n = len(level_ptrs)
+    offs, off = [], 0
+    for h, w in level_hw:
+        offs.append(off)
+        off += h * w * anchors
+    ints = C.c_int * n
+    return ((C.c_void_p * n)(*level_ptrs), ints(*[h for h, _ in level_hw]), ints(*[w for _, w in level_hw]), ints(*[int(bool(f)) for f in level_blocked]),
+            ints(*offs), n)
+
+
+def mask_coef_at_priors(stream_ptr, level_ptrs, level_hw, level_blocked, cin, weight_ptr, bias_ptr, prior_idx_ptr, batch, n_slots, anchors, mask_dim, out_ptr):
+    """amos_mask_coef_at_priors_device: the head's mask layer (weight channels-last [anchors x mask_dim][3][3][cin]) at the int32 priors
+    [batch][n_slots] of the `upfeature` levels (device pointers, (h, w) pairs, channel-blocked flags) -> out [batch][n_slots][mask_dim]."""
+    _check(lib().amos_mask_coef_at_priors_device(stream_ptr, *_coef_levels(level_ptrs, level_hw, level_blocked, anchors), cin, weight_ptr, bias_ptr, prior_idx_ptr,
+                                                 batch, n_slots, anchors, mask_dim, out_ptr), "amos_mask_coef_at_priors_device")
+
+
+def mask_person_masks_at_priors(stream_ptr, loc_ptr, scores_ptr, scores_are_class_scores, level_ptrs, level_hw, level_blocked, cin, anchors, mask_weight_ptr,
+                                mask_bias_ptr, priors_ptr, proto_ptr, batch, n_priors, n_classes_with_background, mask_dim, proto_h, proto_w, out_h, out_w,
+                                workspace_ptr, workspace_bytes, masks_ptr, found_ptr):
+    """amos_mask_person_masks_at_priors_device (scores_ptr: the softmax tensor) or amos_mask_person_masks_scores_at_priors_device (Detect's class
+    scores): mask_person_masks with the displayed detections' coefficients evaluated from the `upfeature` levels instead of read from a tensor."""
+    name = "amos_mask_person_masks_scores_at_priors_device" if scores_are_class_scores else "amos_mask_person_masks_at_priors_device"
+    _check(getattr(lib(), name)(stream_ptr, loc_ptr, scores_ptr, *_coef_levels(level_ptrs, level_hw, level_blocked, anchors), cin, anchors, mask_weight_ptr,
+                                mask_bias_ptr, priors_ptr, proto_ptr, batch, n_priors, n_classes_with_background, mask_dim, proto_h, proto_w, out_h, out_w,
+                                workspace_ptr, workspace_bytes, masks_ptr, found_ptr), name)
 
 
 def mask_nms_column_max(stream_ptr, boxes_ptr, out_ptr, n_lists, k):

@@ -125,6 +125,8 @@ __global__ __launch_bounds__(256) void k_person_mask(const float *__restrict__ m
 // here each level's tensor is read once and the three outputs are written once, as contiguous runs (the priors of consecutive cells are
 // consecutive).  A work-group stages kHeadCells cells in LDS.  Softmax as PyTorch's: max, exp(x - max), sum, divide -- the sum is taken
 // sequentially here and by a butterfly there, so conf agrees to float32 rounding (1 - 2 ulp), loc and coef bit for bit.
+// coef == nullptr: the layer carries no coefficient channels ([A x 4 box | A x (1 + C) class | padding], SharedHead's scores-and-boxes layer);
+// the displayed detections' coefficients then come from k_coef_at_priors.
 // grid = (ceil(cells / kHeadCells), B), block = 256.
 constexpr int kHeadCells = 16;
 __global__ __launch_bounds__(256) void k_head_outputs(const float *__restrict__ raw, const float *__restrict__ bias, float *__restrict__ loc, float *__restrict__ conf,
@@ -133,7 +135,7 @@ __global__ __launch_bounds__(256) void k_head_outputs(const float *__restrict__ 
 {
     extern __shared__ float sh[];  // [kHeadCells][cpad]
     const int b = blockIdx.y, c0 = blockIdx.x * kHeadCells, nc = min(kHeadCells, cells - c0);
-    const int nLoc = A * 4, nConf = A * C1, nCoef = A * D;
+    const int nLoc = A * 4, nConf = A * C1, nCoef = coef ? A * D : 0;
     const float *src = raw + ((size_t)b * cells + c0) * cpad;
     for (int e = threadIdx.x * 4; e < nc * cpad; e += 256 * 4) {  // cpad % 4 == 0
         float4 v = *reinterpret_cast<const float4 *>(src + e);
@@ -173,7 +175,7 @@ __global__ __launch_bounds__(256) void k_head_outputs(const float *__restrict__ 
         a += (a + 1) * C1 <= r ? 1 : 0;
         *v = expf(__fsub_rn(*v, sMax[cell * A + a]));
     })
-    AMOS_HEAD_FOREACH(nCoef, {
+    if (nCoef) AMOS_HEAD_FOREACH(nCoef, {
         float *v = sh + cell * cpad + nLoc + nConf + r;
         *v = tanhf(*v);
     })
@@ -188,7 +190,7 @@ __global__ __launch_bounds__(256) void k_head_outputs(const float *__restrict__ 
     __syncthreads();
     const size_t prior0 = (size_t)b * P + pOff + (size_t)c0 * A;  // first prior of this work-group
     AMOS_HEAD_FOREACH(nLoc, loc[prior0 * 4 + e] = sh[cell * cpad + r])
-    AMOS_HEAD_FOREACH(nCoef, coef[prior0 * D + e] = sh[cell * cpad + nLoc + nConf + r])
+    if (nCoef) AMOS_HEAD_FOREACH(nCoef, coef[prior0 * D + e] = sh[cell * cpad + nLoc + nConf + r])
     if (!scores) {
         AMOS_HEAD_FOREACH(nConf, {
             int a = (int)((float)r * invC1);
@@ -779,11 +781,12 @@ __global__ __launch_bounds__(256) void k_nms_alive(const float4 *__restrict__ bo
 // person_mask_batch's best 15 of those: the same set; order: score descending, equal scores lowest flat index first, as k_topk_rows
 // orders them) that exceed the score threshold.  For each: its class (flat index / k), its box as the crop rectangle of box_utils.crop
 // on the prototype grid (`_sanitize`: scale, order, pad by 1, clamp), its 32 mask coefficients, and the flag "valid and a person".
-// found[b] = some score exceeds the threshold.  grid = B, block = 256.
+// With selPrior: instead of the coefficients, the prior index of every valid slot (-1 for an empty one) -- k_coef_at_priors then evaluates
+// the mask layer at those priors and `coef` is not read.  found[b] = some score exceeds the threshold.  grid = B, block = 256.
 __global__ __launch_bounds__(256) void k_select_display(const float *__restrict__ alive, const long long *__restrict__ idx, const float4 *__restrict__ boxes,
                                                        const float *__restrict__ coef, float *__restrict__ selCoef, float4 *__restrict__ selRect,
                                                        uint8_t *__restrict__ flags, uint8_t *__restrict__ found, int n, int k, int P, int D, int nDisplay,
-                                                       float scoreThresh, int personClass, int pw, int ph)
+                                                       float scoreThresh, int personClass, int pw, int ph, int *__restrict__ selPrior)
 {
     // Only scores above the threshold can be displayed: they are first compacted into a list of (score key, ~flat index) in LDS (a frame
     // has a few hundred at most: Fast NMS has already thinned 80 x 200 candidates), and the nDisplay rounds of "largest key below the last
@@ -851,8 +854,10 @@ __global__ __launch_bounds__(256) void k_select_display(const float *__restrict_
         selRect[(size_t)b * nDisplay + t] = rc;  // (x1, x2, y1, y2)
         flags[(size_t)b * nDisplay + t] = (valid && cls == personClass) ? 1 : 0;
         if (t == 0) found[b] = valid ? 1 : 0;
+        if (selPrior) selPrior[(size_t)b * nDisplay + t] = valid ? (int)prior : -1;
         sSel[t] = (unsigned long long)prior;  // for the coefficient copy below
     }
+    if (selPrior) return;  // (uniform)
     __syncthreads();
     for (int e = t; e < nDisplay * D; e += 256) {
         const int r = e / D, c = e - r * D;
@@ -883,6 +888,57 @@ __global__ __launch_bounds__(256) void k_assemble_masks(const float *__restrict_
         v = 1.f / (1.f + expf(-acc));
     }
     masks[((size_t)b * nDisplay + n) * ph * pw + pix] = v;
+}
+
+// The mask layer (prediction head: 3 x 3, cin -> A x D, tanh) evaluated at GIVEN priors instead of everywhere: the display selection keeps
+// at most 15 of a frame's 19 248 priors, and k_assemble_masks reads the coefficients of no other.  One work-group per (slot, frame): the
+// zero-padded 3 x 3 x cin patch of the prior's cell goes to LDS in [tap][channel] order from either layout of the level's tensor
+// (channels-last [b][h][w][c] or channel-blocked [b][c / 8][h][w][8]); then D x kCoefParts threads: output d sums its 9 x cin products in
+// kCoefParts interleaved strands of float4s (strand s takes the float4s q with q % kCoefParts == s, in order, fused multiply-adds), the
+// strands meet in a fixed butterfly, + bias, tanhf as k_head_outputs takes it.  The order depends on nothing but cin: both layouts and every
+// call give the same bits.  Slots with a negative index (or one past the last level) are written as zeros.
+constexpr int kCoefLevels = 8, kCoefParts = 8;
+struct CoefLevels {
+    const float *x[kCoefLevels];
+    int h[kCoefLevels], w[kCoefLevels], blocked[kCoefLevels], off[kCoefLevels];
+    int n;
+};
+// grid = (n slots, B), block = D * kCoefParts (D = 32: 256); dynamic LDS: 9 * cin floats.
+__global__ __launch_bounds__(256) void k_coef_at_priors(CoefLevels lv, int cin, const float *__restrict__ weight, const float *__restrict__ bias,
+                                                       const int *__restrict__ idx, int n, int A, int D, float *__restrict__ out)
+{
+    extern __shared__ __align__(16) float patch[];  // [9][cin]
+    const int slot = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
+    const int p = idx[(size_t)b * n + slot];
+    float *dst = out + ((size_t)b * n + slot) * D;
+    int l = -1;
+    for (int i = 0; i < lv.n; i++) l = p >= lv.off[i] ? i : l;  // (offsets ascend)
+    const int rel = l >= 0 ? p - lv.off[l] : 0, cell = rel / A, a = rel - cell * A;
+    if (p < 0 || l < 0 || cell >= lv.h[l] * lv.w[l]) {  // uniform over the work-group
+        if (t < D) dst[t] = 0.f;
+        return;
+    }
+    const int h = lv.h[l], w = lv.w[l], cy = cell / w, cx = cell - cy * w;
+    const float *x = lv.x[l];
+    const bool blocked = lv.blocked[l] != 0;
+    for (int e = t; e < 9 * cin; e += blockDim.x) {
+        const int tap = e / cin, c = e - tap * cin, y = cy + tap / 3 - 1, xx = cx + tap % 3 - 1;
+        float v = 0.f;
+        if (y >= 0 && y < h && xx >= 0 && xx < w)
+            v = blocked ? x[((((size_t)b * (cin / 8) + c / 8) * h + y) * w + xx) * 8 + (c & 7)] : x[(((size_t)b * h + y) * w + xx) * cin + c];
+        patch[e] = v;
+    }
+    __syncthreads();
+    const int d = t / kCoefParts, s = t - d * kCoefParts;
+    const float4 *wv = reinterpret_cast<const float4 *>(weight + (size_t)(a * D + d) * 9 * cin);
+    const float4 *pv = reinterpret_cast<const float4 *>(patch);
+    float acc = 0.f;
+    for (int q = s; q < 9 * cin / 4; q += kCoefParts) {
+        const float4 u = wv[q], v = pv[q];
+        acc = __fmaf_rn(u.x, v.x, acc); acc = __fmaf_rn(u.y, v.y, acc); acc = __fmaf_rn(u.z, v.z, acc); acc = __fmaf_rn(u.w, v.w, acc);
+    }
+    for (int m = 1; m < kCoefParts; m <<= 1) acc = __fadd_rn(acc, __shfl_xor(acc, m, 64));  // (a + b == b + a: every strand ends with the same sum)
+    if (s == 0) dst[d] = tanhf(__fadd_rn(acc, bias[a * D + d]));
 }
 
 }  // namespace amos
@@ -933,8 +989,8 @@ int amos_mask_head_outputs_scores_device(void *stream, const float *d_raw, const
                                          float threshold, int batch, int cells, int channels_padded, int anchors, int n_classes_with_background, int mask_dim,
                                          int n_priors_total, int prior_offset)
 {
-    const long long used = (long long)anchors * (4 + n_classes_with_background + mask_dim);
-    if (!d_raw || !d_bias || !d_loc || (!d_conf && !d_scores) || (d_scores && n_classes_with_background < 2) || !d_coef || batch < 0 || cells < 1 || anchors < 1 || n_classes_with_background < 1 || mask_dim < 1 ||
+    const long long used = (long long)anchors * (4 + n_classes_with_background + (d_coef ? mask_dim : 0));  // d_coef NULL: no coefficient channels
+    if (!d_raw || !d_bias || !d_loc || (!d_conf && !d_scores) || (d_scores && n_classes_with_background < 2) || batch < 0 || cells < 1 || anchors < 1 || n_classes_with_background < 1 || mask_dim < 1 ||
         channels_padded % 4 != 0 || used > channels_padded || channels_padded > 1000 || prior_offset < 0 ||  // 16 x channels floats of LDS
        
         (long long)prior_offset + (long long)cells * anchors > n_priors_total || batch > 65535 || kHeadCells * anchors > 256 ||
@@ -993,7 +1049,7 @@ int amos_mask_topk_rows_sparse_device(void *stream, const float *d_x, float *d_v
 // ---- the whole post-processing chain as one call (seven launches on `stream`)
 namespace {
 struct PostLayout {
-    size_t boxes, cls, topv, topi, alive, selCoef, selRect, flags, masks, total;
+    size_t boxes, cls, topv, topi, alive, selCoef, selRect, flags, masks, selPrior, total;
 };
 inline size_t post_align(size_t v) { return (v + 255) & ~(size_t)255; }
 PostLayout post_layout(int B, int P, int C1, int D, int ph, int pw)
@@ -1010,6 +1066,7 @@ PostLayout post_layout(int B, int P, int C1, int D, int ph, int pw)
     l.selRect = o; o += post_align((size_t)B * nd * 16);
     l.flags = o; o += post_align((size_t)B * nd);
     l.masks = o; o += post_align((size_t)B * nd * ph * pw * 4);
+    l.selPrior = o; o += post_align((size_t)B * nd * 4);
     l.total = o;
     return l;
 }
@@ -1021,16 +1078,26 @@ size_t amos_mask_post_workspace_bytes(int batch, int n_priors, int n_classes_wit
     return post_layout(batch, n_priors, n_classes_with_background, mask_dim, proto_h, proto_w).total;
 }
 
-static int person_masks(void *stream, const float *d_loc, const float *d_conf, const float *d_scores, const float *d_coef, const float *d_priors, const float *d_proto,
-                        int batch, int n_priors, int n_classes_with_background, int mask_dim, int proto_h, int proto_w, int out_h, int out_w, void *d_workspace,
-                        size_t workspace_bytes, uint8_t *d_masks, uint8_t *d_found);
+// where the displayed detections' coefficients come from: the head's tensor d_coef, or (lazy != nullptr) the mask layer evaluated at their priors
+struct LazyCoef {
+    CoefLevels lv;
+    int cin, anchors;
+    const float *weight, *bias;
+};
+static int fill_coef_levels(const char *who, CoefLevels &lv, const float *const *d_levels, const int *level_h, const int *level_w, const int *level_blocked,
+                            const int *level_offsets, int n_levels, int batch, int cin, int anchors, int mask_dim, const float *d_weight, const float *d_bias);
+static int launch_coef_at_priors(hipStream_t st, const CoefLevels &lv, int cin, const float *d_weight, const float *d_bias, const int *d_idx, int batch, int n,
+                                 int anchors, int mask_dim, float *d_out);
+static int person_masks(void *stream, const float *d_loc, const float *d_conf, const float *d_scores, const float *d_coef, const LazyCoef *lazy, const float *d_priors,
+                        const float *d_proto, int batch, int n_priors, int n_classes_with_background, int mask_dim, int proto_h, int proto_w, int out_h, int out_w,
+                        void *d_workspace, size_t workspace_bytes, uint8_t *d_masks, uint8_t *d_found);
 
 int amos_mask_person_masks_device(void *stream, const float *d_loc, const float *d_conf, const float *d_coef, const float *d_priors, const float *d_proto,
                                   int batch, int n_priors, int n_classes_with_background, int mask_dim, int proto_h, int proto_w, int out_h, int out_w,
                                   void *d_workspace, size_t workspace_bytes, uint8_t *d_masks, uint8_t *d_found)
 {
     if (!d_conf) { set_error("amos_mask_person_masks_device: invalid argument"); return AMOS_ERR_INVALID; }
-    return person_masks(stream, d_loc, d_conf, nullptr, d_coef, d_priors, d_proto, batch, n_priors, n_classes_with_background, mask_dim, proto_h, proto_w, out_h, out_w,
+    return person_masks(stream, d_loc, d_conf, nullptr, d_coef, nullptr, d_priors, d_proto, batch, n_priors, n_classes_with_background, mask_dim, proto_h, proto_w, out_h, out_w,
                         d_workspace, workspace_bytes, d_masks, d_found);
 }
 
@@ -1039,20 +1106,105 @@ int amos_mask_person_masks_scores_device(void *stream, const float *d_loc, const
                                          void *d_workspace, size_t workspace_bytes, uint8_t *d_masks, uint8_t *d_found)
 {
     if (!d_scores) { set_error("amos_mask_person_masks_scores_device: invalid argument"); return AMOS_ERR_INVALID; }
-    return person_masks(stream, d_loc, nullptr, d_scores, d_coef, d_priors, d_proto, batch, n_priors, n_classes_with_background, mask_dim, proto_h, proto_w, out_h, out_w,
+    return person_masks(stream, d_loc, nullptr, d_scores, d_coef, nullptr, d_priors, d_proto, batch, n_priors, n_classes_with_background, mask_dim, proto_h, proto_w, out_h, out_w,
                         d_workspace, workspace_bytes, d_masks, d_found);
 }
 
-static int person_masks(void *stream, const float *d_loc, const float *d_conf, const float *d_scores, const float *d_coef, const float *d_priors, const float *d_proto,
-                        int batch, int n_priors, int n_classes_with_background, int mask_dim, int proto_h, int proto_w, int out_h, int out_w, void *d_workspace,
-                        size_t workspace_bytes, uint8_t *d_masks, uint8_t *d_found)
+static int fill_coef_levels(const char *who, CoefLevels &lv, const float *const *d_levels, const int *level_h, const int *level_w, const int *level_blocked,
+                            const int *level_offsets, int n_levels, int batch, int cin, int anchors, int mask_dim, const float *d_weight, const float *d_bias)
+{
+    bool ok = d_levels && level_h && level_w && level_blocked && level_offsets && d_weight && d_bias && n_levels >= 1 && n_levels <= kCoefLevels && batch >= 0 &&
+              batch <= 65535 && cin >= 8 && cin % 8 == 0 && cin <= 1024 && anchors >= 1 && mask_dim >= 1 && mask_dim * kCoefParts <= 256 &&
+              (mask_dim * kCoefParts) % 64 == 0 && (uintptr_t)d_weight % 16 == 0;  // 9 x cin floats of LDS; whole waves, so every strand has its partners
+    long long next = 0;
+    for (int i = 0; ok && i < n_levels; i++) {
+        ok = d_levels[i] && level_h[i] >= 1 && level_w[i] >= 1 && level_offsets[i] == next &&
+             (long long)batch * level_h[i] * level_w[i] * cin < (1ll << 40);
+        next += (long long)level_h[i] * level_w[i] * anchors;
+        ok = ok && next < (1ll << 31);
+    }
+    if (!ok) {
+        set_error("%s: invalid argument (1 - %d levels, offsets = the running sum of h x w x anchors, cin %% 8 == 0 and <= 1024, mask_dim x %d a multiple of 64 up to 256)",
+                  who, kCoefLevels, kCoefParts);
+        return AMOS_ERR_INVALID;
+    }
+    lv = CoefLevels{};
+    lv.n = n_levels;
+    for (int i = 0; i < n_levels; i++) {
+        lv.x[i] = d_levels[i]; lv.h[i] = level_h[i]; lv.w[i] = level_w[i]; lv.blocked[i] = level_blocked[i]; lv.off[i] = level_offsets[i];
+    }
+    return AMOS_OK;
+}
+
+static int launch_coef_at_priors(hipStream_t st, const CoefLevels &lv, int cin, const float *d_weight, const float *d_bias, const int *d_idx, int batch, int n,
+                                 int anchors, int mask_dim, float *d_out)
+{
+    hipLaunchKernelGGL(k_coef_at_priors, dim3(n, batch), dim3(mask_dim * kCoefParts), (size_t)9 * cin * sizeof(float), st, lv, cin, d_weight, d_bias, d_idx, n, anchors,
+                       mask_dim, d_out);
+    AMOS_HIP_CHECK(hipGetLastError());
+    return AMOS_OK;
+}
+
+int amos_mask_coef_at_priors_device(void *stream, const float *const *d_levels, const int *level_h, const int *level_w, const int *level_blocked,
+                                    const int *level_offsets, int n_levels, int cin, const float *d_weight, const float *d_bias, const int *d_prior_idx, int batch,
+                                    int n_slots, int anchors, int mask_dim, float *d_out)
+{
+    CoefLevels lv;
+    if (!d_prior_idx || !d_out || n_slots < 0 || n_slots > 65535) { set_error("amos_mask_coef_at_priors_device: invalid argument"); return AMOS_ERR_INVALID; }
+    const int rc = fill_coef_levels("amos_mask_coef_at_priors_device", lv, d_levels, level_h, level_w, level_blocked, level_offsets, n_levels, batch, cin, anchors,
+                                    mask_dim, d_weight, d_bias);
+    if (rc != AMOS_OK) return rc;
+    if (batch == 0 || n_slots == 0) return AMOS_OK;
+    return launch_coef_at_priors((hipStream_t)stream, lv, cin, d_weight, d_bias, d_prior_idx, batch, n_slots, anchors, mask_dim, d_out);
+}
+
+int amos_mask_person_masks_at_priors_device(void *stream, const float *d_loc, const float *d_conf, const float *const *d_levels, const int *level_h,
+                                            const int *level_w, const int *level_blocked, const int *level_offsets, int n_levels, int cin, int anchors,
+                                            const float *d_mask_weight, const float *d_mask_bias, const float *d_priors, const float *d_proto, int batch,
+                                            int n_priors, int n_classes_with_background, int mask_dim, int proto_h, int proto_w, int out_h, int out_w,
+                                            void *d_workspace, size_t workspace_bytes, uint8_t *d_masks, uint8_t *d_found)
+{
+    LazyCoef lazy;
+    if (!d_conf) { set_error("amos_mask_person_masks_at_priors_device: invalid argument"); return AMOS_ERR_INVALID; }
+    const int rc = fill_coef_levels("amos_mask_person_masks_at_priors_device", lazy.lv, d_levels, level_h, level_w, level_blocked, level_offsets, n_levels, batch, cin,
+                                    anchors, mask_dim, d_mask_weight, d_mask_bias);
+    if (rc != AMOS_OK) return rc;
+    lazy.cin = cin; lazy.anchors = anchors; lazy.weight = d_mask_weight; lazy.bias = d_mask_bias;
+    return person_masks(stream, d_loc, d_conf, nullptr, nullptr, &lazy, d_priors, d_proto, batch, n_priors, n_classes_with_background, mask_dim, proto_h, proto_w, out_h,
+                        out_w, d_workspace, workspace_bytes, d_masks, d_found);
+}
+
+int amos_mask_person_masks_scores_at_priors_device(void *stream, const float *d_loc, const float *d_scores, const float *const *d_levels, const int *level_h,
+                                                   const int *level_w, const int *level_blocked, const int *level_offsets, int n_levels, int cin, int anchors,
+                                                   const float *d_mask_weight, const float *d_mask_bias, const float *d_priors, const float *d_proto, int batch,
+                                                   int n_priors, int n_classes_with_background, int mask_dim, int proto_h, int proto_w, int out_h, int out_w,
+                                                   void *d_workspace, size_t workspace_bytes, uint8_t *d_masks, uint8_t *d_found)
+{
+    LazyCoef lazy;
+    if (!d_scores) { set_error("amos_mask_person_masks_scores_at_priors_device: invalid argument"); return AMOS_ERR_INVALID; }
+    const int rc = fill_coef_levels("amos_mask_person_masks_scores_at_priors_device", lazy.lv, d_levels, level_h, level_w, level_blocked, level_offsets, n_levels, batch,
+                                    cin, anchors, mask_dim, d_mask_weight, d_mask_bias);
+    if (rc != AMOS_OK) return rc;
+    lazy.cin = cin; lazy.anchors = anchors; lazy.weight = d_mask_weight; lazy.bias = d_mask_bias;
+    return person_masks(stream, d_loc, nullptr, d_scores, nullptr, &lazy, d_priors, d_proto, batch, n_priors, n_classes_with_background, mask_dim, proto_h, proto_w, out_h,
+                        out_w, d_workspace, workspace_bytes, d_masks, d_found);
+}
+
+static int person_masks(void *stream, const float *d_loc, const float *d_conf, const float *d_scores, const float *d_coef, const LazyCoef *lazy, const float *d_priors,
+                        const float *d_proto, int batch, int n_priors, int n_classes_with_background, int mask_dim, int proto_h, int proto_w, int out_h, int out_w,
+                        void *d_workspace, size_t workspace_bytes, uint8_t *d_masks, uint8_t *d_found)
 {
     const int B = batch, P = n_priors, C1 = n_classes_with_background, C = C1 - 1, D = mask_dim, k = AMOS_MASK_NMS_TOP_K, nd = AMOS_MASK_TOP_K_DISPLAY;
-    if (!d_loc || (!d_conf && !d_scores) || !d_coef || !d_priors || !d_proto || !d_workspace || !d_masks || !d_found || B < 1 || B > 65535 || P < k || C1 < 2 || C1 > 200 ||
+    if (!d_loc || (!d_conf && !d_scores) || (!d_coef && !lazy) || !d_priors || !d_proto || !d_workspace || !d_masks || !d_found || B < 1 || B > 65535 || P < k || C1 < 2 || C1 > 200 ||
         D < 4 || D % 4 != 0 || proto_h < 1 || proto_w < 1 || out_h < 1 || out_w < 1 || (size_t)C * k * 4 > 64 * 1024 ||
         ((uintptr_t)d_loc | (uintptr_t)d_priors | (uintptr_t)d_proto | (uintptr_t)d_coef | (uintptr_t)d_workspace) % 16 != 0) {
         set_error("amos_mask_person_masks_device: invalid argument (16-byte aligned tensors, mask_dim %% 4 == 0, at most %d class lists of %d)", 16384 / k, k);
         return AMOS_ERR_INVALID;
+    }
+    if (lazy) {  // the levels together are the P priors the other tensors speak of
+        const CoefLevels &lv = lazy->lv;
+        const long long last = (long long)lv.off[lv.n - 1] + (long long)lv.h[lv.n - 1] * lv.w[lv.n - 1] * lazy->anchors;
+        if (last != P) { set_error("amos_mask_person_masks_at_priors_device: the levels hold %lld priors, n_priors is %d", last, P); return AMOS_ERR_INVALID; }
     }
     const PostLayout l = post_layout(B, P, C1, D, proto_h, proto_w);
     if (workspace_bytes < l.total) { set_error("amos_mask_person_masks_device: workspace of %zu bytes, %zu needed", workspace_bytes, l.total); return AMOS_ERR_CAPACITY; }
@@ -1072,8 +1224,13 @@ static int person_masks(void *stream, const float *d_loc, const float *d_conf, c
     rc = amos_mask_topk_rows_sparse_device(stream, cls, topv, topi, B * C, P, k, -1.f);  // (k_class_scores writes -1 for every prior under the threshold)
     if (rc != AMOS_OK) return rc;
     hipLaunchKernelGGL(k_nms_alive, dim3(B * C), dim3(256), 0, st, boxes, topi, topv, alive, k, P, C, AMOS_MASK_NMS_THRESH);
+    int *selPrior = lazy ? (int *)(ws + l.selPrior) : nullptr;
     hipLaunchKernelGGL(k_select_display, dim3(B), dim3(256), 0, st, alive, topi, boxes, d_coef, selCoef, selRect, flags, d_found, C * k, k,
-                       P, D, nd, AMOS_MASK_SCORE_THRESHOLD, AMOS_MASK_PERSON_CLASS, proto_w, proto_h);
+                       P, D, nd, AMOS_MASK_SCORE_THRESHOLD, AMOS_MASK_PERSON_CLASS, proto_w, proto_h, selPrior);
+    if (lazy) {  // the mask layer at the selected priors -> selCoef
+        rc = launch_coef_at_priors(st, lazy->lv, lazy->cin, lazy->weight, lazy->bias, selPrior, B, nd, lazy->anchors, D, selCoef);
+        if (rc != AMOS_OK) return rc;
+    }
     hipLaunchKernelGGL(k_assemble_masks, dim3((proto_h * proto_w + 255) / 256, nd, B), dim3(256), 0, st, d_proto, selCoef, selRect, flags, masks, proto_h, proto_w, D, nd);
     AMOS_HIP_CHECK(hipGetLastError());
     return amos_mask_person_mask_device(stream, masks, flags, d_masks, B, nd, proto_h, proto_w, out_h, out_w);

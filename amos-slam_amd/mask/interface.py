@@ -9,7 +9,7 @@ import os
 import torch
 
 from .detect import detect, detect_batch
-from .net import YolactR50, _stem_eligible, stem_kernel_enabled
+from .net import YolactR50, _stem_eligible, lazy_coef_enabled, stem_kernel_enabled
 from .post import person_mask, person_mask_batch, person_masks_fused
 from .pre import cxx_marshalling, fast_base_transform, resize_f32_cv
 
@@ -91,10 +91,19 @@ class MaskEngine:
         """(masks, found) of a network input: the detector's own pass.  With AMOS_MASK_HEAD_SCORES=1, where the fused post-processing will take
         the outputs, the head's kernel writes Detect's class scores directly and no softmax tensor (YolactR50.forward(scores_only=True)): 0.4 GB
         less traffic per 64 frames and one launch less, but the kernel's extra steps cost what they save (0.55 ms against 0.39 + 0.16 at 64
-        frames; 107 against 80 + 9 us at one frame), so the default stays the softmax tensor and the separate class-score pass."""
-        scores_only = (self.device.type == "cuda" and self.conv_dtype is None and x.dtype == torch.float32
-                       and os.environ.get("AMOS_MASK_HEAD_SCORES", "0") == "1" and os.environ.get("AMOS_MASK_FUSED_POST", "1") != "0")
-        return self._person_masks(self._forward(x, scores_only), width, height)
+        frames; 107 against 80 + 9 us at one frame), so the default stays the softmax tensor and the separate class-score pass.
+        Under the same conditions (AMOS_MASK_LAZY_COEF=0 turns it off) the pass is lazy about the mask coefficients: the head's output
+        convolution leaves their 96 channels out and the post-processing evaluates the mask layer at the displayed detections' priors
+        (net.lazy_coef_enabled, SharedHead.merge_output_layers).  The mode reaches the network as an attribute set around the call."""
+        fused_post = (self.device.type == "cuda" and self.conv_dtype is None and x.dtype == torch.float32 and x.is_cuda
+                      and not torch.is_autocast_enabled() and os.environ.get("AMOS_MASK_FUSED_POST", "1") != "0")
+        scores_only = fused_post and os.environ.get("AMOS_MASK_HEAD_SCORES", "0") == "1"
+        before, self.net.lazy_coef = getattr(self.net, "lazy_coef", False), fused_post and lazy_coef_enabled()
+        try:
+            pred = self._forward(x, scores_only)
+        finally:
+            self.net.lazy_coef = before
+        return self._person_masks(pred, width, height)
 
     def _forward(self, x, scores_only=False):
         # (the project's stem kernel reads the input through its strides: no layout copy of the network input for it)
@@ -132,8 +141,8 @@ class MaskEngine:
     def _person_masks(pred, width, height):
         """(masks uint8 [B, height, width], found bool [B]) of a forward's outputs: the fused library call on the GPU, the torch ops elsewhere"""
         fused = person_masks_fused(pred, width, height)
-        if fused is None and "conf" not in pred:
-            raise RuntimeError("the pass was run for the fused post-processing (class scores only), which does not apply to its outputs")
+        if fused is None and ("conf" not in pred or "mask" not in pred):
+            raise RuntimeError("the pass was run for the fused post-processing (class scores only, or no coefficient tensor), which does not apply to its outputs")
         return fused if fused is not None else person_mask_batch(detect_batch(pred), width, height)
 
     @torch.no_grad()

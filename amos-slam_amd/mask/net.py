@@ -97,7 +97,13 @@ def winograd_rule(cin, cout, kernel, stride, padding, dilation, groups, batch, h
 
 
 def _winograd_conv(conv, x):
-    return winograd_rule(conv.in_channels, conv.out_channels, conv.kernel_size, conv.stride, conv.padding, conv.dilation, conv.groups,
+    # (the head's scores-and-boxes layer goes where the merged layer it stands in for goes: `rule_like`, SharedHead.merge_output_layers)
+    like = getattr(conv, "rule_like", None)
+    if like is not None:
+        from .. import mask_winograd_supported
+        if not mask_winograd_supported(conv.in_channels, conv.out_channels):
+            return False
+    return winograd_rule(conv.in_channels, (conv if like is None else like).out_channels, conv.kernel_size, conv.stride, conv.padding, conv.dilation, conv.groups,
                          x.shape[0], x.shape[2], x.shape[3])
 
 
@@ -180,7 +186,7 @@ def prepare_winograd_weights(module):
     on any stream creates a shared tensor.  Returns the number of layers transformed."""
     from .. import mask_winograd_supported
     convs = [m for m in module.modules() if isinstance(m, nn.Conv2d)]
-    merged = [getattr(m, "merged", None) for m in module.modules()]
+    merged = [getattr(m, name, None) for m in module.modules() for name in ("merged", "scores_boxes")]  # the head's unregistered layers
     n = 0
     for conv in convs + [m for m in merged if isinstance(m, nn.Conv2d)]:
         if (conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1
@@ -623,13 +629,36 @@ class SharedHead(nn.Module):
                 merged.bias[:n].copy_(torch.cat([l.bias for l in layers], 0))
             # not a registered sub-module: the state dict keeps the reference's keys
             object.__setattr__(self, "merged", merged.requires_grad_(False))
+        if getattr(self, "scores_boxes", None) is None:
+            # The same without the coefficient filters: 12 + 243 (+ 1 zero filter: 256).  Top-k, Fast NMS and the display selection read class
+            # scores and boxes only; the coefficients of the at most 15 displayed detections are then evaluated from the upfeature tensors
+            # (amos_mask_coef_at_priors_device) instead of for all 19 248 priors: a third less work in the head's output convolution
+            # (lazy_coef_enabled; `merged` stays for every caller that wants the full "mask" tensor).
+            layers = (self.bbox_layer, self.conf_layer)
+            n = sum(l.out_channels for l in layers)
+            lean = nn.Conv2d(FPN_FEATURES, n + (-n) % 64, 3, padding=1).to(device=self.bbox_layer.weight.device, dtype=self.bbox_layer.weight.dtype)
+            with torch.no_grad():
+                lean.weight.zero_()
+                lean.bias.zero_()
+                lean.weight[:n].copy_(torch.cat([l.weight for l in layers], 0))
+                lean.bias[:n].copy_(torch.cat([l.bias for l in layers], 0))
+            # at every launch size the layer runs on the kernel the merged layer would run on (winograd_rule asked with ITS width): a pass takes
+            # the same path through the levels, the channel-blocked chain included, whichever of the two layers it runs
+            object.__setattr__(lean, "rule_like", self.merged)
+            object.__setattr__(self, "scores_boxes", lean.requires_grad_(False))
         return self
+
+    def lazy_applies(self, x0):
+        """May a pass leave the coefficient channels out of the head (fused_outputs(lazy=True))?  Where the fused head applies and the
+        scores-and-boxes layer exists; the caller (MaskEngine._masks_of) has already established that the fused post-processing takes the outputs."""
+        return self.fused_applies(x0) and getattr(self, "scores_boxes", None) is not None and self.mask_layer.weight.dtype == torch.float32 and (
+            self.mask_layer.in_channels % 8 == 0 and MASK_DIM % 8 == 0 and MASK_DIM <= 32)
 
     def fused_applies(self, x0):
         merged = getattr(self, "merged", None)
         return not (merged is None or not x0.is_cuda or x0.dtype != torch.float32 or torch.is_autocast_enabled() or os.environ.get("AMOS_MASK_FUSED_HEAD", "1") == "0")
 
-    def fused_outputs(self, pyramid, n_priors, br=None, out=None, scores=None):
+    def fused_outputs(self, pyramid, n_priors, br=None, out=None, scores=None, lazy=False):
         """All levels' outputs, concatenated, softmax / tanh applied: (loc [B, P, 4], conf [B, P, 81], coef [B, P, 32]), or None when the
         fused path does not apply (no merged layer, not float32 channels-last on the GPU).  Per level: the upfeature convolution, the
         merged output convolution WITHOUT its bias, then ONE HIP kernel (amos_mask_head_outputs_device) that adds the bias, takes the
@@ -639,11 +668,16 @@ class SharedHead(nn.Module):
         side 1) and level 0 on side 2, so the caller's stream is free for the prototype network; `out` = the three tensors, allocated by the
         caller BEFORE any side stream started (they are written there and read on the caller's stream after its join).
         scores: a [B, classes, P] tensor (alloc_scores) -> Detect's class scores come out of the same kernel (amos_mask_head_outputs_scores_device:
-        what amos_mask_class_scores_device would make of conf, bit for bit); with out[1] None the softmax tensor itself is not written."""
+        what amos_mask_class_scores_device would make of conf, bit for bit); with out[1] None the softmax tensor itself is not written.
+        lazy: the output convolution is the scores-and-boxes layer (256 channels instead of 384), no coefficient tensor is written (out[2] None)
+        and the third result is instead the list of the five levels' upfeature tensors (Blocked where the level travels channel-blocked), which
+        mask/post.py hands to amos_mask_person_masks_at_priors_device; with br they are held like every tensor that crosses streams, and the
+        caller keeps them alive until that call is enqueued."""
         x0 = pyramid[0]
         if not self.fused_applies(x0):
             return None
-        merged = self.merged
+        merged = self.scores_boxes if lazy else self.merged
+        ups = [None] * len(pyramid)
         from .. import mask_head_outputs_scores
         b, dev = x0.shape[0], x0.device
         n_anchor = self.bbox_layer.out_channels // 4
@@ -662,12 +696,17 @@ class SharedHead(nn.Module):
         def level(i):
             x = pyramid[i]
             u = conv_bias_act(self.upfeature[0], x, True, out_blocked=isinstance(x, Blocked))
+            if lazy:
+                ups[i] = u if isinstance(u, Blocked) or u.is_contiguous(memory_format=torch.channels_last) else u.contiguous(memory_format=torch.channels_last)
+                if br is not None:
+                    br.hold(ups[i].data if isinstance(u, Blocked) else ups[i])
             raw = conv_raw(merged, u)
             if not raw.is_contiguous(memory_format=torch.channels_last):
                 raw = raw.contiguous(memory_format=torch.channels_last)
             cells = raw.shape[2] * raw.shape[3]
             mask_head_outputs_scores(torch.cuda.current_stream(dev).cuda_stream, raw.data_ptr(), merged.bias.data_ptr(), loc.data_ptr(),
-                                     conf.data_ptr() if conf is not None else None, coef.data_ptr(), scores.data_ptr() if scores is not None else None,
+                                     conf.data_ptr() if conf is not None else None, coef.data_ptr() if coef is not None else None,
+                                     scores.data_ptr() if scores is not None else None,
                                      CONF_THRESH, b, cells, raw.shape[1], n_anchor, NUM_CLASSES, MASK_DIM, n_priors, offs[i])
 
         if br is not None and len(pyramid) == 5:
@@ -681,12 +720,12 @@ class SharedHead(nn.Module):
         else:
             for i in range(len(pyramid)):
                 level(i)
-        return loc, conf, coef
+        return loc, conf, (ups if lazy else coef)
 
-    def alloc_outputs(self, b, n_priors, dev, conf=True):
+    def alloc_outputs(self, b, n_priors, dev, conf=True, coef=True):
         return (torch.empty((b, n_priors, 4), dtype=torch.float32, device=dev),
                 torch.empty((b, n_priors, NUM_CLASSES), dtype=torch.float32, device=dev) if conf else None,
-                torch.empty((b, n_priors, MASK_DIM), dtype=torch.float32, device=dev))
+                torch.empty((b, n_priors, MASK_DIM), dtype=torch.float32, device=dev) if coef else None)
 
     def alloc_scores(self, b, n_priors, dev):
         return torch.empty((b, NUM_CLASSES - 1, n_priors), dtype=torch.float32, device=dev)
@@ -731,8 +770,18 @@ def build_priors(conv_sizes, device="cpu"):
     return torch.tensor(rows, dtype=torch.float32, device=device)
 
 
-def _outputs(loc, conf, cls, coef, priors, proto):
-    out = {"loc": loc, "mask": coef, "priors": priors, "proto": proto}
+def lazy_coef_enabled():
+    """AMOS_MASK_LAZY_COEF=0: the detector's own passes compute the mask coefficients of every prior in the head's output convolution, as
+    before (A/B runs, tests); default: only those of the displayed detections, after the selection (SharedHead.merge_output_layers)."""
+    return os.environ.get("AMOS_MASK_LAZY_COEF", "1") != "0"
+
+
+def _outputs(loc, conf, cls, coef, priors, proto, head=None):
+    out = {"loc": loc, "priors": priors, "proto": proto}
+    if head is None:
+        out["mask"] = coef
+    else:  # a lazy pass: what the mask layer would be evaluated from, instead of its values
+        out["upfeature"], out["mask_layer"] = coef, head.mask_layer
     if conf is not None:
         out["conf"] = conf
     if cls is not None:
@@ -778,20 +827,25 @@ class YolactR50(nn.Module):
         self.prediction_layers[0].merge_output_layers()
         return self
 
-    def _apply(self, fn, *args, **kwargs):  # .to(device / memory format) after the merge carries the merged layer along
+    def _apply(self, fn, *args, **kwargs):  # .to(device / memory format) after the merge carries the merged layers along
         super()._apply(fn, *args, **kwargs)
-        merged = getattr(self.prediction_layers[0], "merged", None)
-        if merged is not None:
-            merged._apply(fn, *args, **kwargs)
+        for name in ("merged", "scores_boxes"):
+            layer = getattr(self.prediction_layers[0], name, None)
+            if layer is not None:
+                layer._apply(fn, *args, **kwargs)
         return self
 
     def forward(self, x, scores_only=False):
         """x: [B, 3, 550, 550] normalised RGB.  Returns raw network outputs (before Detect):
         loc [B, P, 4], conf [B, P, 81] (softmax), mask [B, P, 32] (tanh), priors [P, 4], proto [B, 138, 138, 32] (ReLU).
         scores_only (the detector's own passes, where the fused head applies): instead of conf, "cls" [B, 80, P] -- Detect's thresholded,
-        transposed class scores, written by the head's output kernel (fused_outputs); mask/post.py takes either."""
+        transposed class scores, written by the head's output kernel (fused_outputs); mask/post.py takes either.
+        With the attribute `lazy_coef` set (MaskEngine._masks_of sets it around its call; not an argument: forward keeps its signature), where
+        the fused head applies: no "mask" either, but "upfeature" (the head's five upfeature tensors) and "mask_layer", from which the fused
+        post-processing evaluates the coefficients of the displayed detections alone (SharedHead.fused_outputs(lazy=True))."""
         feats = self.backbone(x)[1:]
         head = self.prediction_layers[0]
+        lazy = bool(getattr(self, "lazy_coef", False)) and len(feats) == 3 and head.lazy_applies(feats[0])
         pn = self.proto_net  # conv, relu, conv, relu, conv, relu, upsample, relu, conv, relu, conv (+ the final ReLU)
 
         def prototypes(p3):
@@ -809,7 +863,7 @@ class YolactR50(nn.Module):
 
         # level 0 of the pyramid channel-blocked through the prototype network and its head, where every layer on the way is an F(2 x 4) launch
         chain = (len(feats) == 3 and head.fused_applies(feats[0]) and getattr(head, "merged", None) is not None and
-                 blocked_chain_for(feats[0], (self.fpn.pred_layers[2], pn[0], pn[2], pn[4], head.upfeature[0], head.merged), (pn[8],)))
+                 blocked_chain_for(feats[0], (self.fpn.pred_layers[2], pn[0], pn[2], pn[4], head.upfeature[0], head.merged), (pn[8],)))  # (lazy: scores_boxes follows merged)
         br = branches_for(x) if head.fused_applies(feats[0]) and len(feats) == 3 else None
         if br is not None:
             # a small pass: the pyramid's side levels and the prediction head on side streams, the prototype network on this one (Branches)
@@ -817,22 +871,22 @@ class YolactR50(nn.Module):
             for _ in range(2):  # the two extra levels: 3 x 3, stride 2, padding 1
                 sizes.append(((sizes[-1][0] - 1) // 2 + 1, (sizes[-1][1] - 1) // 2 + 1))
             n_priors = sum(h * w for h, w in sizes) * (head.bbox_layer.out_channels // 4)
-            out = head.alloc_outputs(x.shape[0], n_priors, x.device, conf=not scores_only)  # before any side stream starts
+            out = head.alloc_outputs(x.shape[0], n_priors, x.device, conf=not scores_only, coef=not lazy)  # before any side stream starts
             cls = head.alloc_scores(x.shape[0], n_priors, x.device) if scores_only else None
             pyramid = self.fpn(feats, br, chain)
             priors = priors_of(pyramid)
-            loc, conf, coef = head.fused_outputs(pyramid, priors.shape[0], br, out, cls)
+            loc, conf, coef = head.fused_outputs(pyramid, priors.shape[0], br, out, cls, lazy)
             proto = prototypes(pyramid[0])
-            br.join()
-            return _outputs(loc, conf, cls, coef, priors, proto)
+            br.join()  # (a lazy pass: the upfeature tensors made on side streams are read on this one from here on, and live on in the result)
+            return _outputs(loc, conf, cls, coef, priors, proto, head if lazy else None)
         pyramid = self.fpn(feats, None, chain)
         proto = prototypes(pyramid[0])
         priors = priors_of(pyramid)
         if head.fused_applies(pyramid[0]):
-            out = head.alloc_outputs(x.shape[0], priors.shape[0], x.device, conf=not scores_only)
+            out = head.alloc_outputs(x.shape[0], priors.shape[0], x.device, conf=not scores_only, coef=not lazy)
             cls = head.alloc_scores(x.shape[0], priors.shape[0], x.device) if scores_only else None
-            loc, conf, coef = head.fused_outputs(pyramid, priors.shape[0], None, out, cls)
-            return _outputs(loc, conf, cls, coef, priors, proto)
+            loc, conf, coef = head.fused_outputs(pyramid, priors.shape[0], None, out, cls, lazy)
+            return _outputs(loc, conf, cls, coef, priors, proto, head if lazy else None)
         locs, confs, coefs = zip(*(head(p) for p in pyramid))
         return {"loc": torch.cat(locs, 1), "conf": F.softmax(torch.cat(confs, 1), -1), "mask": torch.cat(coefs, 1),
                 "priors": priors, "proto": proto}

@@ -95,8 +95,15 @@ def person_masks_fused(pred, w, h):
     ~75 small launches the torch ops above cost per pass -- a fifth of a one-frame mask pass): the same selection rules and the same float32
     arithmetic operation by operation, except the 32-term prototype sums (sequential fused multiply-adds here, a BLAS kernel's order there:
     float32 rounding).  Returns (uint8 [B, h, w], bool [B]) like person_mask_batch, or None where it does not apply (not float32 on a
-    GPU): the caller then takes the torch path."""
-    loc, coef, priors, proto = pred["loc"], pred["mask"], pred["priors"], pred["proto"]
+    GPU): the caller then takes the torch path.
+    A lazy pass (YolactR50.forward with lazy_coef: no "mask", but "upfeature" and "mask_layer") goes to amos_mask_person_masks_at_priors_device:
+    the mask layer is evaluated at the displayed detections' priors, after the selection, from the head's upfeature tensors -- direct float32
+    sums where the full pass has the Winograd or library convolution's, so the coefficients agree to float32 rounding of a 2 304-term sum."""
+    ups = pred.get("upfeature")
+    loc, coef, priors, proto = pred["loc"], pred.get("mask"), pred["priors"], pred["proto"]
+    if ups is not None:
+        layer = pred["mask_layer"]
+        coef = layer.weight  # (stands in for the dtype checks below)
     cls = pred.get("cls")          # Detect's class scores [B, classes, P] from the head's own kernel (YolactR50.forward(scores_only=True)) ...
     conf = pred.get("conf")        # ... or the softmax tensor [B, P, 1 + classes]
     scores = cls if cls is not None else conf
@@ -106,7 +113,7 @@ def person_masks_fused(pred, w, h):
     if os.environ.get("AMOS_MASK_FUSED_POST", "1") == "0":   # A/B runs and the tests that compare the two paths
         return None
     from .. import mask_person_masks, mask_person_masks_scores, mask_post_workspace_bytes
-    loc, scores, coef, priors, proto = (t.contiguous() for t in (loc, scores, coef, priors, proto))
+    loc, scores, priors, proto = (t.contiguous() for t in (loc, scores, priors, proto))
     B, P = loc.shape[:2]
     ph, pw, D = proto.shape[1:]
     c1 = cls.shape[1] + 1 if cls is not None else conf.shape[2]
@@ -116,7 +123,26 @@ def person_masks_fused(pred, w, h):
     ws = torch.empty(nbytes, dtype=torch.uint8, device=loc.device)
     out = torch.empty((B, h, w), dtype=torch.uint8, device=loc.device)
     found = torch.empty(B, dtype=torch.uint8, device=loc.device)
+    stream = torch.cuda.current_stream(loc.device).cuda_stream
+    if ups is not None:
+        from .. import mask_person_masks_at_priors
+        from .net import Blocked
+        weight = layer.weight.contiguous(memory_format=torch.channels_last)  # [anchors x D][3][3][cin] in memory (the engine's layout: no copy)
+        anchors = layer.out_channels // D
+        if layer.kernel_size != (3, 3) or layer.padding != (1, 1) or layer.stride != (1, 1) or layer.out_channels != anchors * D or layer.bias is None:
+            raise RuntimeError("person_masks_fused: the mask layer is not the 3 x 3, padding 1 convolution the lazy pass evaluates")
+        blocked = [isinstance(u, Blocked) for u in ups]
+        if any(tuple(u.shape[:2]) != (B, layer.in_channels) or u.dtype != torch.float32 for u in ups):
+            raise RuntimeError("person_masks_fused: upfeature tensors of another batch, width or type than the pass")
+        data = [u.data if f else u for u, f in zip(ups, blocked)]  # held until the call below is enqueued
+        if not all(d.is_contiguous() if f else d.is_contiguous(memory_format=torch.channels_last) for d, f in zip(data, blocked)):
+            raise RuntimeError("person_masks_fused: an upfeature tensor is neither channels-last nor channel-blocked")
+        mask_person_masks_at_priors(stream, loc.data_ptr(), scores.data_ptr(), cls is not None, [d.data_ptr() for d in data], [tuple(u.shape[2:]) for u in ups], blocked,
+                                    layer.in_channels, anchors, weight.data_ptr(), layer.bias.data_ptr(), priors.data_ptr(), proto.data_ptr(), B, P, c1, D, ph, pw,
+                                    h, w, ws.data_ptr(), nbytes, out.data_ptr(), found.data_ptr())
+        return out, found.bool()
+    coef = coef.contiguous()
     (mask_person_masks_scores if cls is not None else mask_person_masks)(
-        torch.cuda.current_stream(loc.device).cuda_stream, loc.data_ptr(), scores.data_ptr(), coef.data_ptr(), priors.data_ptr(), proto.data_ptr(),
+        stream, loc.data_ptr(), scores.data_ptr(), coef.data_ptr(), priors.data_ptr(), proto.data_ptr(),
         B, P, c1, D, ph, pw, h, w, ws.data_ptr(), nbytes, out.data_ptr(), found.data_ptr())
     return out, found.bool()

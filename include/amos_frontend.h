@@ -706,7 +706,8 @@ int amos_mask_head_outputs_device(void *stream, const float *d_raw, const float 
                                   int n_priors_total, int prior_offset);
 /* The same with Detect's class scores written by the same kernel: d_scores [batch][classes][n_priors_total] (background column dropped, -1 for
  * every prior whose best class is not above `threshold`) exactly as amos_mask_class_scores_device makes them from d_conf -- one pass over the
- * softmax tensor saved, and d_conf itself may be NULL when only the detector reads the head (d_scores may be NULL instead: the plain form). */
+ * softmax tensor saved, and d_conf itself may be NULL when only the detector reads the head (d_scores may be NULL instead: the plain form).
+ * d_coef NULL: the layer has no coefficient channels (channels [anchors x 4 | anchors x n_classes_with_background | padding]). */
 int amos_mask_head_outputs_scores_device(void *stream, const float *d_raw, const float *d_bias, float *d_loc, float *d_conf, float *d_coef, float *d_scores,
                                          float threshold, int batch, int cells, int channels_padded, int anchors, int n_classes_with_background,
                                          int mask_dim, int n_priors_total, int prior_offset);
@@ -747,6 +748,35 @@ int amos_mask_person_masks_scores_device(void *stream, const float *d_loc, const
                                          const float *d_proto, int batch, int n_priors, int n_classes_with_background, int mask_dim, int proto_h,
                                          int proto_w, int out_h, int out_w, void *d_workspace, size_t workspace_bytes, uint8_t *d_masks,
                                          uint8_t *d_found);
+
+/* The mask layer of the prediction head (3 x 3, cin -> anchors x mask_dim, + bias, tanh) evaluated at GIVEN priors rather than at every cell:
+ * the display selection keeps at most AMOS_MASK_TOP_K_DISPLAY priors of a frame, and nothing else reads a coefficient.  The levels are the
+ * head's `upfeature` outputs (after ReLU), float32 on the device: d_levels, level_h, level_w, level_blocked, level_offsets are HOST arrays of
+ * n_levels (<= 8) entries, read during the call -- level i is [batch][h][w][cin] (channels-last) or, with level_blocked[i] != 0,
+ * [batch][cin / 8][h][w][8]; its priors (cell-major, anchor-minor) start at level_offsets[i] = the sum of h x w x anchors over the levels
+ * before it.  d_weight: the layer's weight in channels-last memory [anchors x mask_dim][3][3][cin] (16-byte aligned), d_bias [anchors x
+ * mask_dim].  d_prior_idx int32 [batch][n_slots]: prior p of level l is cell (p - offset_l) / anchors, anchor (p - offset_l) % anchors; a
+ * negative index (or one past the last level) is an empty slot.  d_out [batch][n_slots][mask_dim]: tanh(patch . filter[anchor x mask_dim + d]
+ * + bias), zeros for empty slots.  Float32 sums in an order fixed by cin alone: either layout and every call give the same bits.
+ * cin % 8 == 0, cin <= 1024; mask_dim a multiple of 8, at most 32. */
+int amos_mask_coef_at_priors_device(void *stream, const float *const *d_levels, const int *level_h, const int *level_w, const int *level_blocked,
+                                    const int *level_offsets, int n_levels, int cin, const float *d_weight, const float *d_bias,
+                                    const int *d_prior_idx, int batch, int n_slots, int anchors, int mask_dim, float *d_out);
+/* amos_mask_person_masks_device / amos_mask_person_masks_scores_device without a coefficient tensor: the display selection records its
+ * priors, amos_mask_coef_at_priors_device's kernel evaluates the mask layer there (levels, weight and bias as above; the levels together
+ * hold n_priors priors), the rest is unchanged.  One launch more; the head then needs no coefficient channels at all. */
+int amos_mask_person_masks_at_priors_device(void *stream, const float *d_loc, const float *d_conf, const float *const *d_levels, const int *level_h,
+                                            const int *level_w, const int *level_blocked, const int *level_offsets, int n_levels, int cin,
+                                            int anchors, const float *d_mask_weight, const float *d_mask_bias, const float *d_priors,
+                                            const float *d_proto, int batch, int n_priors, int n_classes_with_background, int mask_dim, int proto_h,
+                                            int proto_w, int out_h, int out_w, void *d_workspace, size_t workspace_bytes, uint8_t *d_masks,
+                                            uint8_t *d_found);
+int amos_mask_person_masks_scores_at_priors_device(void *stream, const float *d_loc, const float *d_scores, const float *const *d_levels,
+                                                   const int *level_h, const int *level_w, const int *level_blocked, const int *level_offsets,
+                                                   int n_levels, int cin, int anchors, const float *d_mask_weight, const float *d_mask_bias,
+                                                   const float *d_priors, const float *d_proto, int batch, int n_priors,
+                                                   int n_classes_with_background, int mask_dim, int proto_h, int proto_w, int out_h, int out_w,
+                                                   void *d_workspace, size_t workspace_bytes, uint8_t *d_masks, uint8_t *d_found);
 
 
 /* ---------------------------------------------------------------- SLIC superpixels (8f-2) ---- */
