@@ -274,7 +274,8 @@ __global__ __launch_bounds__(1024) void k_corner_select(CornerWork wk, int w, in
     }
 }
 
-constexpr int kSubpixWavesPerGroup = 4;
+constexpr int kSubpixWavesPerGroup = 4;       // at most; fewer where the window's LDS does not fit four times (amos_corners_subpix_device)
+constexpr size_t kSubpixLdsLimit = 160 * 1024;  // a gfx950 CU's LDS
 
 // getRectSubPix element (i, j) of the (pw x pw) patch whose top-left sample is (ipx, ipy): samplers.cpp's two formulas with replicated borders
 __device__ __forceinline__ float subpix_sample(const uint8_t *img, size_t stride, int sw, int sh, int pw, int ipx, int ipy, int rx, int rw, int i, int j,
@@ -290,13 +291,15 @@ __device__ __forceinline__ float subpix_sample(const uint8_t *img, size_t stride
     return __fadd_rn(__fmul_rn((float)s[sw - 1], b1), __fmul_rn((float)s2[sw - 1], b2));
 }
 
-__global__ __launch_bounds__(64 * kSubpixWavesPerGroup) void k_corner_subpix(const uint8_t *__restrict__ img, size_t stride, int w, int h, float *__restrict__ xy,
-                                                                             const int *__restrict__ countPtr, int nGiven, int win, int maxIters, double eps,
-                                                                             const float *__restrict__ mask)
+// WAVES corners per work-group: kSubpixWavesPerGroup wherever that many patches fit the LDS (the product's window), three at win 15
+template <int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void k_corner_subpix(const uint8_t *__restrict__ img, size_t stride, int w, int h, float *__restrict__ xy,
+                                                              const int *__restrict__ countPtr, int nGiven, int win, int maxIters, double eps,
+                                                              const float *__restrict__ mask)
 {
     extern __shared__ __align__(16) unsigned char subpix_smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int n = countPtr ? *countPtr : nGiven, p = blockIdx.x * kSubpixWavesPerGroup + wave;
+    const int n = countPtr ? *countPtr : nGiven, p = blockIdx.x * WAVES + wave;
     if (p >= n) return;  // wave-uniform; no work-group barrier below
     const int ww = 2 * win + 1, pw = ww + 2, nWin = ww * ww, nPatch = pw * pw;
     const size_t waveBytes = (((size_t)nPatch * 4 + 15) & ~(size_t)15) + (size_t)5 * nWin * 8 + 64;
@@ -484,11 +487,19 @@ int amos_corners_subpix_device(amos_corners *c, const uint8_t *d_gray, size_t st
     eps *= eps;
     const int iters = max_count < 1 ? 1 : (max_count > 100 ? 100 : max_count);
     const size_t waveBytes = (((size_t)pw * pw * 4 + 15) & ~(size_t)15) + (size_t)5 * ww * ww * 8 + 64;
-    const size_t lds = waveBytes * kSubpixWavesPerGroup;
-    static DeviceOnce ldsAttr;  // per device (amos_common.h)
-    AMOS_HIP_CHECK(set_max_dynamic_lds(ldsAttr, reinterpret_cast<const void *>(k_corner_subpix), 160 * 1024));
-    hipLaunchKernelGGL(k_corner_subpix, dim3((n + kSubpixWavesPerGroup - 1) / kSubpixWavesPerGroup), dim3(64 * kSubpixWavesPerGroup), lds, c->stream, d_gray, stride,
-                       width, height, d_xy, d_count, n, win, iters, eps, c->dMask);
+    // four waves per work-group while their LDS fits a CU's (win <= 14: 150 240 bytes); three at win 15 (128 616 bytes; four would need 171 488)
+    static_assert(kSubpixMaxWin == 15 && kSubpixWavesPerGroup == 4, "the two launch shapes below are worked out for win <= 15");
+    if (waveBytes * kSubpixWavesPerGroup <= kSubpixLdsLimit) {
+        static DeviceOnce ldsAttr;  // per device (amos_common.h)
+        AMOS_HIP_CHECK(set_max_dynamic_lds(ldsAttr, reinterpret_cast<const void *>(k_corner_subpix<kSubpixWavesPerGroup>), (int)kSubpixLdsLimit));
+        hipLaunchKernelGGL(k_corner_subpix<kSubpixWavesPerGroup>, dim3((n + kSubpixWavesPerGroup - 1) / kSubpixWavesPerGroup), dim3(64 * kSubpixWavesPerGroup),
+                           waveBytes * kSubpixWavesPerGroup, c->stream, d_gray, stride, width, height, d_xy, d_count, n, win, iters, eps, c->dMask);
+    } else {
+        static DeviceOnce ldsAttr3;
+        AMOS_HIP_CHECK(set_max_dynamic_lds(ldsAttr3, reinterpret_cast<const void *>(k_corner_subpix<3>), (int)kSubpixLdsLimit));
+        hipLaunchKernelGGL(k_corner_subpix<3>, dim3((n + 2) / 3), dim3(64 * 3), waveBytes * 3, c->stream, d_gray, stride, width, height, d_xy, d_count, n, win, iters, eps,
+                           c->dMask);
+    }
     AMOS_HIP_CHECK(hipGetLastError());
     return AMOS_OK;
 }

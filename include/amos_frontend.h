@@ -846,7 +846,9 @@ int amos_flow_epipolar_device(void *stream, const double *d_F, const float *d_pr
                               const uint8_t *d_state, int n, double *d_dd);
 /* (:955-990, 1153-1183): per match the world point of the LAST frame's pixel (pre_3d, through mLastFrame.mTcw), of the
  * CURRENT frame's pixel (cur_3d, through mRwc / mOw), the flow norm sqrt(dx^2 + dz^2) and a validity flag (z1 > 0 &&
- * z2 > 0): out[i] = {pre_3d.xyz, cur_3d.xyz, sf_norm, valid}.  Depth maps are float32 (rows `stride` floats apart). */
+ * z2 > 0): out[i] = {pre_3d.xyz, cur_3d.xyz, sf_norm, valid}.  Depth maps are float32 (rows `stride` floats apart).
+ * PRECONDITION: the call has no width or height and reads depth[(int)y][(int)x] unguarded, as the reference does after its border
+ * check: every match position must lie inside both depth maps (what amos_flow_check_device's survivors do). */
 typedef struct amos_scene_flow_camera {
     float cx, cy, invfx, invfy; /* Frame::cx, cy, invfx, invfy */
     float Tlw[12];              /* mLastFrame.mTcw, first three rows (row-major 3 x 4) */
@@ -891,7 +893,9 @@ int amos_lk_track_device(amos_lk *k, const uint8_t *d_prev_gray, size_t prev_str
  * Harris detector, blockSize 3, Sobel aperture 3, no mask (what the reference passes).  d_xy receives (x, y) pairs in the library's
  * order (strongest first, equal responses: the later pixel first), d_count their number (<= max_corners, <= xy_capacity);
  * d_response (or NULL) the Harris response plane [height][width].  amos_corners_subpix_device refines d_xy in place for the first
- * *d_count points (d_count == NULL: n points).  Restated from OpenCV 4.5's published algorithms; PARITY UNPINNED like the other
+ * *d_count points (d_count == NULL: n points); 1 <= win <= 15 and a frame of at least (2 win + 5) pixels either way, anything else
+ * is AMOS_ERR_INVALID (every window of that range launches: four corners per work-group up to win 14, three at 15, whose patch and
+ * products fit a CU's LDS only three times).  Restated from OpenCV 4.5's published algorithms; PARITY UNPINNED like the other
  * OpenCV-derived stages.  A frame with more than 65 536 local maxima above the quality threshold is truncated:
  * amos_corners_candidate_count (synchronising) reports AMOS_ERR_CAPACITY then.  Asynchronous on the handle's stream. */
 typedef struct amos_corners amos_corners;
