@@ -85,6 +85,15 @@ PROTOTYPES = {
     "amos_match_local_points": (_i, (_v, _v, _v, _v, _i, _v, _i, _v, _v, _v, _i, _f, _f, _f, _f, _v, _v, _v, _v)),
     "amos_match_motion_model_batch_device": (_i, (_v, _v)),
     "amos_match_motion_model": (_i, (_v, _v, _v, _v, _i, _v, _i, _v, _v, _i, _f, _f, _f, _f, _v, _v, _v, _v)),
+    "amos_bow_create": (_i, (_i, _v, _i, _i, _i, _i, _i, _v, _v, _v, _v, _v)),
+    "amos_bow_destroy": (None, (_v,)),
+    "amos_bow_sync": (_i, (_v,)),
+    "amos_bow_stream": (_v, (_v,)),
+    "amos_bow_check": (_i, (_i, _i, _i, _i, _i, _v, _v, _v)),
+    "amos_bow_transform_batch_device": (_i, (_v, _v, _v, _i, _i, _i, _v, _v, _v, _v, _v, _v, _v, _v, _v, _v)),
+    "amos_bow_transform": (_i, (_v, _v, _i, _i, _v, _v, _v, _v, _v, _v, _v, _v)),
+    "amos_match_bow_batch_device": (_i, (_v, _v)),
+    "amos_match_bow": (_i, (_v, _v, _v, _f, _i, _v, _v)),
     "amos_mask_pre_create": (_i, (_i, _v, _i, _i, _i, _v)),
     "amos_mask_pre_destroy": (None, (_v,)),
     "amos_mask_pre_stream": (_v, (_v,)),
@@ -923,6 +932,84 @@ class MotionSearch(C.Structure):
                 ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float)]
 
 
+BOW_L1_NORM, BOW_TF_IDF = 0, 0  # DBoW2::ScoringType, DBoW2::WeightingType: what a vocabulary handle is built for
+BOW_MAX_CHILDREN, BOW_MAX_CAPACITY, BOW_NO_WORD, BOW_STATUS_EARLY_LEAF = 32, 16384, 0xFFFFFFFF, 1
+BOW_STATS_DTYPE = np.dtype([("n_words", "<i4"), ("n_nodes", "<i4"), ("n_stopped", "<i4"), ("status", "<i4")])
+BOW_SEARCH_STATS_DTYPE = np.dtype([("n_queries", "<i4"), ("n_matches", "<i4"), ("n_researched", "<i4"), ("status", "<i4")])
+assert BOW_STATS_DTYPE.itemsize == BOW_SEARCH_STATS_DTYPE.itemsize == 16
+
+
+class BowSearch(C.Structure):
+    """amos_bow_search (include/amos_frontend.h)."""
+    _fields_ = [("d_kps", C.c_void_p), ("d_desc", C.c_void_p), ("d_counts", C.c_void_p), ("d_n_nodes", C.c_void_p), ("d_node_ids", C.c_void_p),
+                ("d_node_off", C.c_void_p), ("d_node_idx", C.c_void_p), ("d_has_point", C.c_void_p), ("d_pairs_kf", C.c_void_p),
+                ("d_pairs_f", C.c_void_p), ("d_match", C.c_void_p), ("d_stats", C.c_void_p), ("n_pairs", C.c_int32), ("capacity", C.c_int32),
+                ("nn_ratio", C.c_float), ("check_orientation", C.c_int32)]
+
+
+class BowView(C.Structure):
+    """amos_bow_view (include/amos_host_types.h)."""
+    _fields_ = [("n", C.c_int32), ("keys", C.c_void_p), ("descriptors", C.c_void_p), ("has_point", C.c_void_p), ("u_right", C.c_void_p),
+                ("n_nodes", C.c_int32), ("node_ids", C.c_void_p), ("node_off", C.c_void_p), ("node_idx", C.c_void_p)]
+
+
+def bow_vocabulary_arrays(parent, is_leaf, desc, weight):
+    """The four node arrays of amos_bow_create / amos_bow_check as contiguous arrays of one entry per node (entry 0, the root's, is not read)."""
+    parent = np.ascontiguousarray(parent, np.int32)
+    is_leaf = np.ascontiguousarray(is_leaf, np.uint8)
+    desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+    weight = np.ascontiguousarray(weight, np.float64)
+    if not (len(parent) == len(is_leaf) == len(desc) == len(weight)):
+        raise ValueError("parent, is_leaf, desc and weight hold one entry per node")
+    return parent, is_leaf, desc, weight
+
+
+def bow_check(k, L, scoring, weighting, parent, is_leaf):
+    """amos_bow_check: (rc, n_words) of the vocabulary checks alone; no device is touched."""
+    parent, is_leaf = np.ascontiguousarray(parent, np.int32), np.ascontiguousarray(is_leaf, np.uint8)
+    n_words = C.c_int32(0)
+    rc = lib().amos_bow_check(k, L, scoring, weighting, len(parent), _p(parent), _p(is_leaf), C.byref(n_words))
+    return rc, n_words.value
+
+
+class BowVocabulary(_Handle):
+    """A DBoW2 vocabulary tree on the device and Frame::ComputeBoW over it: TemplatedVocabulary::transform(features, BowVector&,
+    FeatureVector&, levelsup) (TemplatedVocabulary.h:1127-1259).  Built from the arrays loadFromTextFile reads (:1338-1424): for node i >= 1
+    its parent, leaf flag, descriptor and weight; node 0 is the root."""
+
+    _kind = "bow"
+
+    def __init__(self, k, L, parent, is_leaf, desc, weight, scoring=BOW_L1_NORM, weighting=BOW_TF_IDF, device=0, stream=None):
+        parent, is_leaf, desc, weight = bow_vocabulary_arrays(parent, is_leaf, desc, weight)
+        self.branching, self.levels, self.n_nodes = k, L, len(parent)
+        self._open(device, stream, k, L, scoring, weighting, len(parent), _p(parent), _p(is_leaf), _p(desc), _p(weight))
+
+    def transform_batch_device(self, d_desc, d_counts, n_frames, capacity, levelsup, d_feat_word, d_feat_node, d_n_nodes, d_node_ids, d_node_off,
+                               d_node_idx, d_n_words, d_words, d_word_weights, d_stats):
+        """The transform of resident frames (amos_bow_transform_batch_device); asynchronous on the handle's stream."""
+        _check(self.L.amos_bow_transform_batch_device(self.h, d_desc, d_counts, n_frames, capacity, levelsup, d_feat_word, d_feat_node, d_n_nodes,
+                                                       d_node_ids, d_node_off, d_node_idx, d_n_words, d_words, d_word_weights, d_stats),
+               "amos_bow_transform_batch_device")
+
+    def transform(self, desc, levelsup=4):
+        """ONE frame from a host array (amos_bow_transform).  Returns a dict: feat_word, feat_node [n]; node_ids [n_nodes], node_off
+        [n_nodes + 1], node_idx (the FeatureVector as CSR); words, word_weights [n_words] (the BowVector); stats."""
+        desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        n = len(desc)
+        fw, fn, ids, idx, words = (np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.int32),
+                                   np.zeros(n, np.uint32))
+        off, wts, stats = np.zeros(n + 1, np.int32), np.zeros(n, np.float64), np.zeros(1, BOW_STATS_DTYPE)
+        _check(self.L.amos_bow_transform(self.h, _p(desc), n, levelsup, _p(fw), _p(fn), _p(ids), _p(off), _p(idx), _p(words), _p(wts), _p(stats)),
+               "amos_bow_transform")
+        s = stats[0]
+        nn, nw = int(s["n_nodes"]), int(s["n_words"])
+        return {"feat_word": fw, "feat_node": fn, "node_ids": ids[:nn], "node_off": off[:nn + 1], "node_idx": idx[:n - int(s["n_stopped"])],
+                "words": words[:nw], "word_weights": wts[:nw], "stats": s}
+
+    def sync(self):
+        _check(self.L.amos_bow_sync(self.h), "amos_bow_sync")
+
+
 class OrbMatcher(_Handle):
     """The distance / best-two primitives every ORBmatcher::Search* inner loop reduces to
     (ORBmatcher.cc:1913-1933 and the candidate loops at :127-148, :278-304, :560-580, :1644-1690)."""
@@ -1050,6 +1137,37 @@ class OrbMatcher(_Handle):
         _check(self.L.amos_match_motion_model(self.h, _p(kps_un), _p(desc), _p(ur), n, _p(points), m, _p(cam), _p(sf), len(sf), *bounds,
                                               _p(query), _p(projected), _p(match), _p(stats)), "amos_match_motion_model")
         return query, projected, match, stats[0]
+
+    def bow_batch_device(self, d_kps, d_desc, d_counts, d_n_nodes, d_node_ids, d_node_off, d_node_idx, d_pairs_kf, d_pairs_f, n_pairs, capacity,
+                         d_match, d_stats, nn_ratio=0.7, check_orientation=True, d_has_point=None):
+        """ORBmatcher::SearchByBoW(pKF, F, vpMapPointMatches) (ORBmatcher.cc:230-382) for (keyframe slot, frame slot) pairs of resident frames
+        whose FeatureVectors are BowVocabulary.transform_batch_device's CSR.  Asynchronous on the matcher's stream."""
+        s = BowSearch(d_kps, d_desc, d_counts, d_n_nodes, d_node_ids, d_node_off, d_node_idx, d_has_point, d_pairs_kf, d_pairs_f, d_match, d_stats,
+                      n_pairs, capacity, nn_ratio, int(bool(check_orientation)))
+        _check(self.L.amos_match_bow_batch_device(self.h, C.byref(s)), "amos_match_bow_batch_device")
+
+    @staticmethod
+    def _bow_view(keys, desc, node_ids, node_off, node_idx, has_point=None):
+        """-> (BowView, the arrays it points into)"""
+        keys = np.ascontiguousarray(keys, KP_DTYPE)
+        desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        ids, off, idx = np.ascontiguousarray(node_ids, np.uint32), np.ascontiguousarray(node_off, np.int32), np.ascontiguousarray(node_idx, np.int32)
+        hp = None if has_point is None else np.ascontiguousarray(has_point, np.uint8)
+        if len(desc) != len(keys) or (hp is not None and len(hp) != len(keys)) or (len(ids) and len(off) != len(ids) + 1):
+            raise ValueError("desc and has_point hold one entry per keypoint, node_off one more than node_ids")
+        keep = (keys, desc, ids, off, idx, hp)
+        return BowView(len(keys), keys.ctypes.data, desc.ctypes.data, None if hp is None else hp.ctypes.data, None, len(ids), ids.ctypes.data,
+                       off.ctypes.data, idx.ctypes.data), keep
+
+    def bow(self, kf, f, nn_ratio=0.7, check_orientation=True):
+        """The same for ONE keyframe and ONE frame from host arrays (amos_match_bow).  kf and f are dicts with keys, desc, node_ids, node_off,
+        node_idx and, for kf, optionally has_point.  Returns (matches_f, stats)."""
+        vk, keep_k = self._bow_view(kf["keys"], kf["desc"], kf["node_ids"], kf["node_off"], kf["node_idx"], kf.get("has_point"))
+        vf, keep_f = self._bow_view(f["keys"], f["desc"], f["node_ids"], f["node_off"], f["node_idx"])
+        matches, stats = np.full(vf.n, -1, np.int32), np.zeros(1, BOW_SEARCH_STATS_DTYPE)
+        _check(self.L.amos_match_bow(self.h, C.byref(vk), C.byref(vf), nn_ratio, int(bool(check_orientation)), _p(matches), _p(stats)),
+               "amos_match_bow")
+        return matches, stats[0]
 
     def sync(self):
         _check(self.L.amos_match_sync(self.h), "amos_match_sync")

@@ -49,4 +49,23 @@ __device__ __forceinline__ int block_compact(int cnt, int *sWave, Sel sel_of, Fn
     return total;
 }
 
+// Ascending bitonic sort of the n (a power of two) 64-bit keys in LDS by the whole work-group; every thread calls.  The keys on either
+// side of a call are separated from the caller's own accesses by the barriers at its start and end.
+template <int kThreads>
+__device__ __forceinline__ void block_sort_u64(unsigned long long *keys, int n)
+{
+    __syncthreads();
+    for (int k = 2; k <= n; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = threadIdx.x; t < (n >> 1); t += kThreads) {
+                const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;  // the t-th pair of distance j
+                const unsigned long long a = keys[lo], b = keys[hi];
+                const bool up = (lo & k) == 0;
+                if ((a > b) == up) { keys[lo] = b; keys[hi] = a; }
+            }
+            __syncthreads();
+        }
+    }
+}
+
 }  // namespace amos

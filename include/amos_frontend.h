@@ -525,6 +525,119 @@ int amos_match_motion_model(amos_match *m, const amos_keypoint *kps_un, const ui
                             int n_levels, float min_x, float max_x, float min_y, float max_y, struct amos_proj_query *query,
                             uint8_t *projected, int32_t *match, amos_motion_stats *stats);
 
+/* ---------------------------------------------------------------- bag of words --------------- */
+
+/* Tracking::TrackReferenceKeyFrame's two steps (Tracking.cc:1736-1794) for resident frames: Frame::ComputeBoW (Frame.cc:1033-1049), which is
+ * TemplatedVocabulary::transform(features, BowVector&, FeatureVector&, levelsup) (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1127-1259), and
+ * ORBmatcher::SearchByBoW(KeyFrame*, Frame&, vpMapPointMatches) (ORBmatcher.cc:230-382).  Tracking::Relocalization runs the same two calls
+ * against every candidate keyframe (Tracking.cc:2595, 2634).
+ *
+ * The vocabulary handle is built from host arrays that hold what TemplatedVocabulary::loadFromTextFile (:1338-1424) reads: k, L, scoring,
+ * weighting and, for the nodes 1 .. n_nodes - 1 in file order, parent, is_leaf, descriptor and weight (entry 0 of each array belongs to
+ * the implicit root and is not read).  Creation builds the children lists in ascending node id (the file's push_back order), numbers the
+ * words over the leaves in node order, and lays the tree out so that the child descriptors of one node are contiguous on the device.
+ * AMOS_ERR_INVALID, before the device is touched: a NULL argument; scoring other than AMOS_BOW_L1_NORM or weighting other than
+ * AMOS_BOW_TF_IDF (ORBvoc.txt's 0 / 0: nothing else is built); L outside 1 .. 10; n_nodes < 2; parent[i] < 0 or >= i; a node that is no
+ * leaf and has no children (the root too) or a leaf with children; more than AMOS_BOW_MAX_CHILDREN children on one node.
+ *
+ * Arithmetic (PINNED: restated from the reference's loops, integers and IEEE doubles, nothing reassociated or fused):
+ *   descent (:1218-1259): from the root, at each level the child with the smallest Hamming distance, compared as integers, the FIRST child
+ *   of equal distances (the loop's strict d < best_d); it stops at a leaf.  word = the leaf's word id, weight = the leaf's weight.
+ *   nid: the node chosen at level L - levelsup (the root's children are level 1); node 0 when L - levelsup <= 0.  When the walk ends at a
+ *   leaf ABOVE that level the reference leaves nid uninitialised: here it is the leaf's node id, and bit 0 (value 1) of the frame's status
+ *   is set (whether or not the word is stopped).
+ *   a feature whose word is stopped (not weight > 0, :1157) enters neither vector; its d_feat_word is AMOS_BOW_NO_WORD.
+ *   FeatureVector (FeatureVector.cpp addFeature): node ids ascending, the features of a node ascending.
+ *   BowVector (:1145-1162, BowVector.cpp:34-46): the value of a word is the double sum of its weight over its features in ascending
+ *   feature order, starting FROM the first weight (v, then v + w, ...).  normalize (BowVector.cpp:62-84): norm = the double sum of
+ *   fabs(value) from 0.0 in ascending word order, one addition per word; when norm > 0 every value becomes value / norm (correctly rounded). */
+typedef struct amos_bow amos_bow;
+#define AMOS_BOW_L1_NORM 0            /* DBoW2::ScoringType */
+#define AMOS_BOW_TF_IDF 0             /* DBoW2::WeightingType */
+#define AMOS_BOW_MAX_CHILDREN 32
+#define AMOS_BOW_MAX_CAPACITY 16384   /* features per frame of a transform: its sort keys, 8 bytes each, live in 128 KB of the CU's 160 KB LDS */
+#define AMOS_BOW_NO_WORD 0xFFFFFFFFu
+#define AMOS_BOW_STATUS_EARLY_LEAF 1  /* amos_bow_stats.status bit 0 */
+
+typedef struct amos_bow_stats {        /* 16 bytes */
+    int32_t n_words;                   /* entries of the BowVector */
+    int32_t n_nodes;                   /* entries of the FeatureVector */
+    int32_t n_stopped;                 /* features whose word is stopped */
+    int32_t status;                    /* bit 0: a walk reached a leaf above level L - levelsup */
+} amos_bow_stats;
+
+int amos_bow_create(int device, void *stream, int k, int L, int scoring, int weighting, int n_nodes, const int32_t *parent,
+                    const uint8_t *is_leaf, const uint8_t *desc, const double *weight, amos_bow **out);
+void amos_bow_destroy(amos_bow *b);
+int amos_bow_sync(amos_bow *b);
+void *amos_bow_stream(amos_bow *b);
+/* The argument checks of amos_bow_create alone (no device is touched): AMOS_OK or AMOS_ERR_INVALID; *n_words, if not NULL, gets the word count. */
+int amos_bow_check(int k, int L, int scoring, int weighting, int n_nodes, const int32_t *parent, const uint8_t *is_leaf, int32_t *n_words);
+/* The transform of n_frames resident frames: descriptors d_desc [frames][capacity][32], counts d_counts [frames] (a count above capacity is
+ * read as capacity, one below 0 as 0).  Two launches, asynchronous on the handle's stream; nothing returns to the host.  Outputs, per frame f:
+ *   d_feat_word, d_feat_node [frames][capacity]   per feature: its word id (AMOS_BOW_NO_WORD when stopped) and its nid
+ *   d_n_nodes [frames]; d_node_ids [frames][capacity] ascending; d_node_off [frames][capacity + 1], n_nodes + 1 entries;
+ *   d_node_idx [frames][capacity] feature indices, ascending inside a node: the FeatureVector as the CSR amos_bow_view reads
+ *   d_n_words [frames]; d_words [frames][capacity] ascending; d_word_weights [frames][capacity] doubles: the BowVector
+ *   d_stats [frames]
+ * Entries past a frame's counts (features, nodes + 1 offsets, indexed features, words) are not written.  capacity 1 ..
+ * AMOS_BOW_MAX_CAPACITY, AMOS_ERR_CAPACITY above it; AMOS_ERR_INVALID for a NULL argument, n_frames < 1 or levelsup < 0. */
+int amos_bow_transform_batch_device(amos_bow *b, const uint8_t *d_desc, const int32_t *d_counts, int n_frames, int capacity, int levelsup,
+                                    uint32_t *d_feat_word, uint32_t *d_feat_node, int32_t *d_n_nodes, uint32_t *d_node_ids,
+                                    int32_t *d_node_off, int32_t *d_node_idx, int32_t *d_n_words, uint32_t *d_words,
+                                    double *d_word_weights, amos_bow_stats *d_stats);
+/* The host form: ONE frame of n descriptors, host arrays in and out, synchronous: one upload, the two launches, one download.  feat_word,
+ * feat_node, node_ids, node_idx, words, word_weights hold n entries, node_off n + 1; entries past the counts in stats are left as they are. */
+int amos_bow_transform(amos_bow *b, const uint8_t *desc, int n, int levelsup, uint32_t *feat_word, uint32_t *feat_node, uint32_t *node_ids,
+                       int32_t *node_off, int32_t *node_idx, uint32_t *words, double *word_weights, amos_bow_stats *stats);
+
+/* ORBmatcher::SearchByBoW(pKF, F, vpMapPointMatches) (ORBmatcher.cc:230-382) for n_pairs (keyframe slot, frame slot) pairs of resident
+ * frames whose FeatureVectors are the transform's CSR.  Two launches (eight lanes per keyframe feature find the best two frame features
+ * of its node, taken or not; ONE wave per pair then runs the reference's sequential loop), nothing returns to the host.
+ *   Only nodes present on both sides take part.  Keyframe features are visited in FeatureVector order (nodes ascending, in-node order);
+ *   one without a good map point (d_has_point, NULL = all have one) is skipped.  Its candidates are the frame features of the same node
+ *   that no earlier keyframe feature was matched to; best and second best start at 256 under strict <, the first of equal distances
+ *   wins.  Accepted when best <= AMOS_TH_LOW and (float) best < nn_ratio * (float) second: d_match[best feature] = the keyframe feature.
+ *   A frame feature is never overwritten.  Rotation consistency (check_orientation): rot = angleKF - angleF, + 360.0f when rot < 0,
+ *   bin = (int) roundf(rot * (30 / 360.0f)), 30 becomes 0; one entry per accepted match; every entry of a bin that is not one of
+ *   ComputeThreeMaxima's three (see the motion-model search) sets its frame feature to -1 and lowers n_matches.
+ *   n_researched counts the keyframe features whose best or second best over ALL frame features of the node (the first of equal
+ *   distances in list order each) had been taken when their turn came: their list is searched again against the taken features.
+ *   A feature index outside [0, count) in a FeatureVector is never dereferenced: such a keyframe feature is skipped and sets bit 0 of the
+ *   pair's status, such a frame feature is no candidate. */
+typedef struct amos_bow_search_stats { /* 16 bytes */
+    int32_t n_queries;                 /* keyframe features that reached the candidate loop: in a shared node, with a map point */
+    int32_t n_matches;                 /* the search's return value */
+    int32_t n_researched;
+    int32_t status;                    /* bit 0: a keyframe feature index outside the keyframe's features */
+} amos_bow_search_stats;
+
+typedef struct amos_bow_search {
+    const amos_keypoint *d_kps;        /* [frames][capacity]: KF mvKeysUn, F mvKeys (only .angle is read) */
+    const uint8_t *d_desc;             /* [frames][capacity][32] */
+    const int32_t *d_counts;           /* [frames] */
+    const int32_t *d_n_nodes;          /* [frames]                 the FeatureVectors (amos_bow_transform_batch_device) */
+    const uint32_t *d_node_ids;        /* [frames][capacity] */
+    const int32_t *d_node_off;         /* [frames][capacity + 1] */
+    const int32_t *d_node_idx;         /* [frames][capacity] */
+    const uint8_t *d_has_point;        /* [frames][capacity] or NULL: vpMapPointsKF[i] && !isBad() */
+    const int32_t *d_pairs_kf, *d_pairs_f; /* [n_pairs] frame slots */
+    int32_t *d_match;                  /* out, [n_pairs][capacity]: the keyframe feature matched to frame feature i, or -1 (reset by the call) */
+    amos_bow_search_stats *d_stats;    /* out, [n_pairs] */
+    int32_t n_pairs, capacity;         /* capacity 1 .. 65536 */
+    float nn_ratio;
+    int32_t check_orientation;
+} amos_bow_search;
+/* Asynchronous on the matcher's stream.  AMOS_ERR_INVALID, before the device is touched, for a NULL handle or argument (d_has_point apart),
+ * n_pairs < 1 or a capacity out of range. */
+int amos_match_bow_batch_device(amos_match *m, const amos_bow_search *s);
+struct amos_bow_view;                  /* include/amos_host_types.h */
+/* The host form: one keyframe and one frame as amos_bow_view, host arrays in and out, synchronous: one upload, the two launches, one
+ * download.  matches_f holds f->n entries.  AMOS_ERR_INVALID also for a view whose node ids do not ascend, whose offsets do not ascend from 0
+ * to at most n, or whose feature indices leave [0, n). */
+int amos_match_bow(amos_match *m, const struct amos_bow_view *kf, const struct amos_bow_view *f, float nn_ratio, int check_orientation,
+                   int32_t *matches_f, amos_bow_search_stats *stats);
+
 /* ---------------------------------------------------------------- mask pre-processing (8f-4) - */
 
 /* The pre-processing chain of the mask pass on the device, from the raw BGR frame to the network input:
