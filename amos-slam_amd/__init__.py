@@ -94,6 +94,10 @@ PROTOTYPES = {
     "amos_bow_transform": (_i, (_v, _v, _i, _i, _v, _v, _v, _v, _v, _v, _v, _v)),
     "amos_match_bow_batch_device": (_i, (_v, _v)),
     "amos_match_bow": (_i, (_v, _v, _v, _f, _i, _v, _v)),
+    "amos_match_bow_kf_batch_device": (_i, (_v, _v, _f, _i)),
+    "amos_match_triangulation_batch_device": (_i, (_v, _v, _v, _v, _v, _i, _i, _i)),
+    "amos_match_bow_kf": (_i, (_v, _v, _v, _f, _i, _v, _v)),
+    "amos_match_triangulation": (_i, (_v, _v, _v, _i, _v, _v, _v, _i, _i, _i, _v, _v)),
     "amos_mask_pre_create": (_i, (_i, _v, _i, _i, _i, _v)),
     "amos_mask_pre_destroy": (None, (_v,)),
     "amos_mask_pre_stream": (_v, (_v,)),
@@ -947,6 +951,19 @@ class BowSearch(C.Structure):
                 ("nn_ratio", C.c_float), ("check_orientation", C.c_int32)]
 
 
+class KfPairSearch(C.Structure):
+    """amos_kf_pair_search (include/amos_frontend.h)."""
+    _fields_ = [("d_kps", C.c_void_p), ("d_desc", C.c_void_p), ("d_counts", C.c_void_p), ("d_n_nodes", C.c_void_p), ("d_node_ids", C.c_void_p),
+                ("d_node_off", C.c_void_p), ("d_node_idx", C.c_void_p), ("d_has_point", C.c_void_p), ("d_u_right", C.c_void_p),
+                ("d_pairs_1", C.c_void_p), ("d_pairs_2", C.c_void_p), ("d_match12", C.c_void_p), ("d_stats", C.c_void_p), ("n_pairs", C.c_int32),
+                ("capacity", C.c_int32)]
+
+
+KF_GEOMETRY_DTYPE = np.dtype([("f12", "<f4", (9,)), ("ex", "<f4"), ("ey", "<f4")])  # amos_kf_geometry
+assert KF_GEOMETRY_DTYPE.itemsize == 44
+KF_STATUS_BAD_INDEX, KF_STATUS_BAD_OCTAVE = 1, 2  # amos_bow_search_stats.status of the keyframe pair searches
+
+
 class BowView(C.Structure):
     """amos_bow_view (include/amos_host_types.h)."""
     _fields_ = [("n", C.c_int32), ("keys", C.c_void_p), ("descriptors", C.c_void_p), ("has_point", C.c_void_p), ("u_right", C.c_void_p),
@@ -1147,17 +1164,19 @@ class OrbMatcher(_Handle):
         _check(self.L.amos_match_bow_batch_device(self.h, C.byref(s)), "amos_match_bow_batch_device")
 
     @staticmethod
-    def _bow_view(keys, desc, node_ids, node_off, node_idx, has_point=None):
+    def _bow_view(keys, desc, node_ids, node_off, node_idx, has_point=None, u_right=None):
         """-> (BowView, the arrays it points into)"""
         keys = np.ascontiguousarray(keys, KP_DTYPE)
         desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
         ids, off, idx = np.ascontiguousarray(node_ids, np.uint32), np.ascontiguousarray(node_off, np.int32), np.ascontiguousarray(node_idx, np.int32)
         hp = None if has_point is None else np.ascontiguousarray(has_point, np.uint8)
-        if len(desc) != len(keys) or (hp is not None and len(hp) != len(keys)) or (len(ids) and len(off) != len(ids) + 1):
-            raise ValueError("desc and has_point hold one entry per keypoint, node_off one more than node_ids")
-        keep = (keys, desc, ids, off, idx, hp)
-        return BowView(len(keys), keys.ctypes.data, desc.ctypes.data, None if hp is None else hp.ctypes.data, None, len(ids), ids.ctypes.data,
-                       off.ctypes.data, idx.ctypes.data), keep
+        ur = None if u_right is None else np.ascontiguousarray(u_right, np.float32)
+        if len(desc) != len(keys) or (hp is not None and len(hp) != len(keys)) or (ur is not None and len(ur) != len(keys)) or \
+                (len(ids) and len(off) != len(ids) + 1):
+            raise ValueError("desc, has_point and u_right hold one entry per keypoint, node_off one more than node_ids")
+        keep = (keys, desc, ids, off, idx, hp, ur)
+        return BowView(len(keys), keys.ctypes.data, desc.ctypes.data, None if hp is None else hp.ctypes.data, None if ur is None else ur.ctypes.data,
+                       len(ids), ids.ctypes.data, off.ctypes.data, idx.ctypes.data), keep
 
     def bow(self, kf, f, nn_ratio=0.7, check_orientation=True):
         """The same for ONE keyframe and ONE frame from host arrays (amos_match_bow).  kf and f are dicts with keys, desc, node_ids, node_off,
@@ -1168,6 +1187,54 @@ class OrbMatcher(_Handle):
         _check(self.L.amos_match_bow(self.h, C.byref(vk), C.byref(vf), nn_ratio, int(bool(check_orientation)), _p(matches), _p(stats)),
                "amos_match_bow")
         return matches, stats[0]
+
+    def bow_kf_batch_device(self, d_kps, d_desc, d_counts, d_n_nodes, d_node_ids, d_node_off, d_node_idx, d_pairs_1, d_pairs_2, n_pairs, capacity,
+                            d_match12, d_stats, nn_ratio=0.75, check_orientation=True, d_has_point=None):
+        """ORBmatcher::SearchByBoW(pKF1, pKF2, vpMatches12) (ORBmatcher.cc:656-799) for (keyframe-1 slot, keyframe-2 slot) pairs of resident
+        frames (LoopClosing::ComputeSim3's call, once per loop candidate).  Asynchronous on the matcher's stream."""
+        s = KfPairSearch(d_kps, d_desc, d_counts, d_n_nodes, d_node_ids, d_node_off, d_node_idx, d_has_point, None, d_pairs_1, d_pairs_2, d_match12,
+                         d_stats, n_pairs, capacity)
+        _check(self.L.amos_match_bow_kf_batch_device(self.h, C.byref(s), nn_ratio, int(bool(check_orientation))), "amos_match_bow_kf_batch_device")
+
+    def bow_kf(self, k1, k2, nn_ratio=0.75, check_orientation=True):
+        """The same for two keyframes from host arrays (amos_match_bow_kf).  k1 and k2 are dicts with keys, desc, node_ids, node_off, node_idx
+        and optionally has_point.  Returns (match12, stats)."""
+        v1, keep1 = self._bow_view(k1["keys"], k1["desc"], k1["node_ids"], k1["node_off"], k1["node_idx"], k1.get("has_point"))
+        v2, keep2 = self._bow_view(k2["keys"], k2["desc"], k2["node_ids"], k2["node_off"], k2["node_idx"], k2.get("has_point"))
+        match12, stats = np.full(v1.n, -1, np.int32), np.zeros(1, BOW_SEARCH_STATS_DTYPE)
+        _check(self.L.amos_match_bow_kf(self.h, C.byref(v1), C.byref(v2), nn_ratio, int(bool(check_orientation)), _p(match12), _p(stats)),
+               "amos_match_bow_kf")
+        return match12, stats[0]
+
+    def triangulation_batch_device(self, d_kps, d_desc, d_counts, d_n_nodes, d_node_ids, d_node_off, d_node_idx, d_pairs_1, d_pairs_2, n_pairs,
+                                   capacity, d_geometry, d_scale_factors, d_level_sigma2, n_levels, d_match12, d_stats, only_stereo=False,
+                                   check_orientation=True, d_has_point=None, d_u_right=None):
+        """ORBmatcher::SearchForTriangulation (ORBmatcher.cc:810-1009) for (keyframe-1 slot, keyframe-2 slot) pairs of resident frames
+        (LocalMapping::CreateNewMapPoints' call, once per neighbour).  d_geometry: KF_GEOMETRY_DTYPE records, one per pair.  Asynchronous on
+        the matcher's stream."""
+        s = KfPairSearch(d_kps, d_desc, d_counts, d_n_nodes, d_node_ids, d_node_off, d_node_idx, d_has_point, d_u_right, d_pairs_1, d_pairs_2,
+                         d_match12, d_stats, n_pairs, capacity)
+        _check(self.L.amos_match_triangulation_batch_device(self.h, C.byref(s), d_geometry, d_scale_factors, d_level_sigma2, n_levels,
+                                                            int(bool(only_stereo)), int(bool(check_orientation))),
+               "amos_match_triangulation_batch_device")
+
+    def triangulation(self, k1, k2s, geometry, scale_factors, level_sigma2, only_stereo=False, check_orientation=True):
+        """The same for ONE keyframe 1 against the keyframes k2s from host arrays (amos_match_triangulation): dicts as for bow_kf, has_point
+        meaning "has a map point" and u_right optional.  geometry: KF_GEOMETRY_DTYPE records, one per keyframe 2.  Returns (match12
+        [len(k2s)][n1], stats [len(k2s)])."""
+        def view(k):
+            return self._bow_view(k["keys"], k["desc"], k["node_ids"], k["node_off"], k["node_idx"], k.get("has_point"), k.get("u_right"))
+        v1, keep1 = view(k1)
+        views = [view(k) for k in k2s]
+        geo = np.ascontiguousarray(geometry, KF_GEOMETRY_DTYPE).reshape(-1)
+        sf, sg = np.ascontiguousarray(scale_factors, np.float32), np.ascontiguousarray(level_sigma2, np.float32)
+        if len(geo) != len(views) or len(sf) != len(sg):
+            raise ValueError("geometry holds one record per keyframe 2, scale_factors and level_sigma2 one entry per level")
+        ptrs = (C.c_void_p * max(len(views), 1))(*[C.addressof(v) for v, _ in views])
+        match12, stats = np.full((len(views), v1.n), -1, np.int32), np.zeros(len(views), BOW_SEARCH_STATS_DTYPE)
+        _check(self.L.amos_match_triangulation(self.h, C.byref(v1), ptrs, len(views), _p(geo), _p(sf), _p(sg), len(sf), int(bool(only_stereo)),
+                                               int(bool(check_orientation)), _p(match12), _p(stats)), "amos_match_triangulation")
+        return match12, stats
 
     def sync(self):
         _check(self.L.amos_match_sync(self.h), "amos_match_sync")

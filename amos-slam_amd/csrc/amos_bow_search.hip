@@ -4,9 +4,7 @@
 // Launches on the matcher's stream: k_bow_best2 (eight lanes per keyframe feature: the best two frame features of its node, taken or not)
 // and k_bow_accept (one wave per pair: the reference's sequential loop over those records, then the rotation histogram's pruning).  The
 // semantics are defined in include/amos_frontend.h, "bag of words".
-#include "amos_projection_search.h"  // TakenBitmap, best-two keys, the matcher's staging
-
-#include "../../include/amos_host_types.h"  // amos_bow_view
+#include "amos_bow_list.h"  // BowSide, the wave's list search, bow_view_ok
 
 #include <vector>
 
@@ -32,26 +30,6 @@ struct BowSearchArgs {
     float nnRatio;
     int checkOri;
 };
-
-// one frame's FeatureVector and features; whatever is read of the arrays is clamped into them
-struct BowSide {
-    int n, nNodes;
-    const uint32_t *ids;
-    const int *off, *idx;
-    const uint8_t *desc;
-    const amos_keypoint *kps;
-};
-__device__ __forceinline__ BowSide bow_side(const BowSearchArgs &a, int slot)
-{
-    const size_t o = (size_t)slot * a.capacity;
-    BowSide s;
-    s.n = min(max(a.counts[slot], 0), a.capacity);
-    s.nNodes = min(max(a.nNodes[slot], 0), a.capacity);
-    s.ids = a.nodeIds + o; s.off = a.nodeOff + (size_t)slot * (a.capacity + 1); s.idx = a.nodeIdx + o;
-    s.desc = a.desc + o * 32; s.kps = a.kps + o;
-    return s;
-}
-__device__ __forceinline__ int bow_off(const BowSearchArgs &a, const BowSide &s, int node) { return min(max(s.off[node], 0), a.capacity); }
 
 // ---- the candidate loop of ORBmatcher.cc:278-304 against the frame with nothing matched yet (list order is candidate order: the first of
 // equal distances wins).  grid = (ceil(capacity * 8 / 256), pairs), block = 256.
@@ -102,26 +80,6 @@ __global__ __launch_bounds__(256) void k_bow_best2(const BowSearchArgs a)
         a.best2[o] = best2_from_keys(best, second, fr.idx + b0, kInitDist);
         a.part[o] = part;
     }
-}
-
-// the whole wave searches a node's list again, against the taken features; the record comes back wave-uniform
-__device__ __forceinline__ amos_best2 wave_list_best2(const BowSide &fr, int b0, int b1, const Desc &q, const TakenBitmap &taken, int lane)
-{
-    unsigned best = 0xffffffffu, second = 0xffffffffu;
-    for (int j = b0 + lane; j < b1; j += 64) {
-        const int idx = fr.idx[j];
-        if ((unsigned)idx >= (unsigned)fr.n || taken.test(idx)) continue;
-        const int d = hamming256(q, load_desc(fr.desc + (size_t)idx * 32));
-        if (d < kInitDist) top2_push(best, second, ((unsigned)d << 16) | (unsigned)(j - b0));
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned ob = __shfl_xor(best, off, 64), os = __shfl_xor(second, off, 64);
-        top2_merge(best, second, ob, os);
-    }
-    best = __builtin_amdgcn_readfirstlane(best);
-    second = __builtin_amdgcn_readfirstlane(second);
-    return best2_from_keys(best, second, fr.idx + b0, kInitDist);
 }
 
 // ---- the sequential loop of ORBmatcher.cc:254-345 and the pruning of :348-361.  One wave per pair walks the keyframe's list in order with
@@ -234,21 +192,6 @@ __global__ __launch_bounds__(64) void k_bow_accept(const BowSearchArgs a)
         s.n_queries = nQueries; s.n_matches = nMatches; s.n_researched = nResearched; s.status = anyBad ? 1 : 0;
         a.stats[p] = s;
     }
-}
-
-// what the host form asks of a view before its arrays go to the device
-static bool bow_view_ok(const amos_bow_view *v)
-{
-    if (!v || v->n < 0 || v->n > 65536 || v->n_nodes < 0 || v->n_nodes > std::max(v->n, 1)) return false;
-    if (v->n > 0 && (!v->keys || !v->descriptors)) return false;
-    if (v->n_nodes == 0) return true;
-    if (!v->node_ids || !v->node_off || !v->node_idx || v->node_off[0] != 0) return false;
-    for (int i = 0; i < v->n_nodes; i++) {
-        if (v->node_off[i + 1] < v->node_off[i] || (i > 0 && v->node_ids[i] <= v->node_ids[i - 1])) return false;
-    }
-    if (v->node_off[v->n_nodes] > v->n) return false;
-    for (int j = 0; j < v->node_off[v->n_nodes]; j++) if (v->node_idx[j] < 0 || v->node_idx[j] >= v->n) return false;
-    return true;
 }
 
 }  // namespace amos

@@ -72,6 +72,15 @@ inline V3 centre(const Pose &p)
     for (int c = 0; c < 3; c++) o[c] = (float)(-((double)p.R[c] * p.t[0] + (double)p.R[3 + c] * p.t[1] + (double)p.R[6 + c] * p.t[2]));
     return V3{o[0], o[1], o[2]};
 }
+// the epipole of pKF1's camera centre in pKF2's image (ORBmatcher.cc:818-826)
+template <class KeyFrameT>
+inline void epipole_in(KeyFrameT *pKF1, KeyFrameT *pKF2, float &ex, float &ey)
+{
+    const V3 C2 = transform(pose_of(pKF2->GetRotation(), pKF2->GetTranslation()), vec3(pKF1->GetCameraCenter()));
+    const float invz = 1.0f / C2.z;
+    ex = pKF2->fx * C2.x * invz + pKF2->cx;
+    ey = pKF2->fy * C2.y * invz + pKF2->cy;
+}
 inline V3 sub(const V3 &a, const V3 &b) { return V3{a.x - b.x, a.y - b.y, a.z - b.z}; }
 inline double dot(const V3 &a, const V3 &b) { return (double)a.x * b.x + (double)a.y * b.y + (double)a.z * b.z; }  // Mat::dot
 inline double norm(const V3 &a) { return std::sqrt(dot(a, a)); }                                                // cv::norm
@@ -339,11 +348,8 @@ public:
     int SearchForTriangulation(KeyFrameT *pKF1, KeyFrameT *pKF2, cv::Mat F12, std::vector<std::pair<size_t, size_t> > &vMatchedPairs, const bool bOnlyStereo)
     {
         using namespace amos_adapt;
-        // the epipole of pKF1's camera centre in pKF2, :818-826
-        const V3 C2 = transform(pose_of(pKF2->GetRotation(), pKF2->GetTranslation()), vec3(pKF1->GetCameraCenter()));
-        const float invz = 1.0f / C2.z;
-        const float ex = pKF2->fx * C2.x * invz + pKF2->cx;
-        const float ey = pKF2->fy * C2.y * invz + pKF2->cy;
+        float ex, ey;
+        epipole_in(pKF1, pKF2, ex, ey);
         std::vector<uint8_t> has1(pKF1->N, 0), has2(pKF2->N, 0);
         for (int i = 0; i < pKF1->N; i++) has1[i] = pKF1->GetMapPoint(i) != NULL;  // :846-849
         for (int i = 0; i < pKF2->N; i++) has2[i] = pKF2->GetMapPoint(i) != NULL;  // :874-877

@@ -638,6 +638,71 @@ struct amos_bow_view;                  /* include/amos_host_types.h */
 int amos_match_bow(amos_match *m, const struct amos_bow_view *kf, const struct amos_bow_view *f, float nn_ratio, int check_orientation,
                    int32_t *matches_f, amos_bow_search_stats *stats);
 
+/* The two searches over a PAIR of keyframes' FeatureVectors, for n_pairs (keyframe-1 slot, keyframe-2 slot) pairs of resident frames:
+ * ORBmatcher::SearchForTriangulation (ORBmatcher.cc:810-1009, CheckDistEpipolarLine :188-215), which LocalMapping::CreateNewMapPoints
+ * calls once per neighbour of the current keyframe (LocalMapping.cc:324), and ORBmatcher::SearchByBoW(pKF1, pKF2, vpMatches12) (:656-799),
+ * which LoopClosing::ComputeSim3 calls once per loop candidate (LoopClosing.cc:346).  Two launches each (eight lanes per list position of
+ * keyframe 1 find the best two keyframe-2 features of its node, taken or not; ONE wave per pair then runs the reference's sequential
+ * loop with the taken keyframe-2 features as a bitmap), nothing returns to the host.
+ *   Common: only nodes present on both sides take part; keyframe-1 features are visited in FeatureVector order.  d_match12[i] = the
+ *   keyframe-2 feature matched to keyframe-1 feature i, or -1 (reset by the call; vMatchedPairs is its ascending scan); a keyframe-2
+ *   feature is matched once.  Rotation consistency (check_orientation): rot = angle1 - angle2 and the bins as in the search above; one
+ *   entry per accepted keyframe-1 feature; an entry of a losing bin sets d_match12[idx1] = -1 and lowers n_matches.  n_queries counts the
+ *   keyframe-1 features that reach the candidate loop.  A keyframe-1 index outside [0, count) is skipped and sets status bit 0, a
+ *   keyframe-2 index outside is no candidate.
+ *   SearchByBoW(KF, KF): d_has_point[i] = the feature has a good map point (NULL = all have one); a keyframe-1 feature without one is
+ *   skipped, a keyframe-2 feature without one is no candidate.  Best and second best start at 256 under strict <, the FIRST of equal
+ *   distances wins; accepted when best < AMOS_TH_LOW (strictly) and (float) best < nn_ratio * (float) second.  n_researched counts
+ *   the queries whose best or second best over all candidates of the node had been taken when their turn came.
+ *   SearchForTriangulation: d_has_point[i] = GetMapPoint(i) != NULL (NULL = none has one): such a feature is skipped on side 1 and is
+ *   no candidate on side 2.  A feature is stereo when d_u_right[i] >= 0 (NULL: none is); under only_stereo a mono feature is skipped /
+ *   no candidate.  A candidate must have dist <= AMOS_TH_LOW; when both features are mono it must NOT lie near the epipole:
+ *   (ex - x2) * (ex - x2) + (ey - y2) * (ey - y2) < 100 * scale_factors[octave2] rejects (float32, every operation rounded in source
+ *   order); and it must pass the line test: a = x1 * F[0] + y1 * F[3] + F[6], b = x1 * F[1] + y1 * F[4] + F[7], c = x1 * F[2] + y1 * F[5]
+ *   + F[8], num = a * x2 + b * y2 + c, den = a * a + b * b, den == 0 rejects, dsqr = num * num / den (float32, left to right), accepted
+ *   when (double) dsqr < 3.84 * (double) level_sigma2[octave2].  The reference's running bound (dist > bestDist skips, an equal distance
+ *   passes) makes the result the LAST candidate of the smallest distance in list order among those that pass every test and are not
+ *   taken; there is no ratio test.  When that candidate over ALL passing candidates is taken the next one in the same order (if any)
+ *   is the result when it is free; when both are taken the list is searched again against the taken features and the query counts in
+ *   n_researched.  A keyframe-2 keypoint that passes the other filters and whose octave is outside [0, n_levels) is no candidate and
+ *   sets status bit 1. */
+typedef struct amos_kf_pair_search {
+    const amos_keypoint *d_kps;        /* [frames][capacity]: mvKeysUn (x, y, angle, octave are read) */
+    const uint8_t *d_desc;             /* [frames][capacity][32] */
+    const int32_t *d_counts;           /* [frames] */
+    const int32_t *d_n_nodes;          /* [frames]                 the FeatureVectors (amos_bow_transform_batch_device) */
+    const uint32_t *d_node_ids;        /* [frames][capacity] */
+    const int32_t *d_node_off;         /* [frames][capacity + 1] */
+    const int32_t *d_node_idx;         /* [frames][capacity] */
+    const uint8_t *d_has_point;        /* [frames][capacity] or NULL.  SearchByBoW(KF, KF): a good map point (NULL = all);
+                                          SearchForTriangulation: any map point (NULL = none) */
+    const float *d_u_right;            /* [frames][capacity] or NULL (monocular).  SearchForTriangulation only */
+    const int32_t *d_pairs_1, *d_pairs_2; /* [n_pairs] frame slots */
+    int32_t *d_match12;                /* out, [n_pairs][capacity] */
+    amos_bow_search_stats *d_stats;    /* out, [n_pairs]; status bit 0: a keyframe-1 index outside the keyframe, bit 1: an octave outside */
+    int32_t n_pairs, capacity;         /* capacity 1 .. 65536 */
+} amos_kf_pair_search;
+typedef struct amos_kf_geometry {      /* 44 bytes, per pair: the caller's, from the two poses */
+    float f12[9];                      /* the fundamental matrix, row-major */
+    float ex, ey;                      /* keyframe 1's camera centre in keyframe 2's image (ORBmatcher.cc:818-825) */
+} amos_kf_geometry;
+/* Asynchronous on the matcher's stream.  AMOS_ERR_INVALID, before the device is touched, for a NULL handle or argument (d_has_point and
+ * d_u_right apart), n_pairs < 1, a capacity out of range or n_levels outside 1 .. AMOS_MAX_LEVELS.  d_geometry [n_pairs],
+ * d_scale_factors and d_level_sigma2 [n_levels] are device arrays. */
+int amos_match_bow_kf_batch_device(amos_match *m, const amos_kf_pair_search *s, float nn_ratio, int check_orientation);
+int amos_match_triangulation_batch_device(amos_match *m, const amos_kf_pair_search *s, const amos_kf_geometry *d_geometry,
+                                          const float *d_scale_factors, const float *d_level_sigma2, int n_levels, int only_stereo,
+                                          int check_orientation);
+/* The host forms, synchronous: one upload, the two launches, one download.  amos_match_bow_kf: two views; match12 holds k1->n entries.
+ * amos_match_triangulation: ONE keyframe 1 against n2 keyframes 2 (keyframe 1 is staged once); geometry holds n2 records, scale_factors
+ * and level_sigma2 n_levels floats (host arrays); match12 holds n2 rows of k1->n entries, stats n2.  AMOS_ERR_INVALID, before the device
+ * is touched, for a NULL argument, n2 < 1, n_levels out of range or a view that amos_match_bow rejects. */
+int amos_match_bow_kf(amos_match *m, const struct amos_bow_view *k1, const struct amos_bow_view *k2, float nn_ratio, int check_orientation,
+                      int32_t *match12, amos_bow_search_stats *stats);
+int amos_match_triangulation(amos_match *m, const struct amos_bow_view *k1, const struct amos_bow_view *const *k2s, int n2,
+                             const amos_kf_geometry *geometry, const float *scale_factors, const float *level_sigma2, int n_levels,
+                             int only_stereo, int check_orientation, int32_t *match12, amos_bow_search_stats *stats);
+
 /* ---------------------------------------------------------------- mask pre-processing (8f-4) - */
 
 /* The pre-processing chain of the mask pass on the device, from the raw BGR frame to the network input:
