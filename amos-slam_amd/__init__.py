@@ -144,6 +144,12 @@ PROTOTYPES = {
     "amos_mask_coef_at_priors_device": (_i, (_v, _v, _v, _v, _v, _v, _i, _i, _v, _v, _v, _i, _i, _i, _i, _v)),
     "amos_mask_person_masks_at_priors_device": (_i, (_v, _v, _v, _v, _v, _v, _v, _v, _i, _i, _i, _v, _v, _v, _v, _i, _i, _i, _i, _i, _i, _i, _i, _v, _z, _v, _v)),
     "amos_mask_person_masks_scores_at_priors_device": (_i, (_v, _v, _v, _v, _v, _v, _v, _v, _i, _i, _i, _v, _v, _v, _v, _i, _i, _i, _i, _i, _i, _i, _i, _v, _z, _v, _v)),
+    "amos_mask_candidates_bytes": (_z, (_i, _i, _i)),
+    "amos_mask_candidates_reset_device": (_i, (_v, _v, _i, _i)),
+    "amos_mask_head_candidates_device": (_i, (_v, _v, _v, _v, _v, _v, _f, _i, _i, _i, _i, _i, _i, _i, _i)),
+    "amos_mask_topk_lists_device": (_i, (_v, _v, _v, _i, _v, _v, _i, _i)),
+    "amos_mask_person_masks_candidates_device": (_i, (_v, _v, _v, _v, _v, _v, _i, _i, _i, _i, _i, _i, _i, _i, _v, _z, _v, _v)),
+    "amos_mask_person_masks_candidates_at_priors_device": (_i, (_v, _v, _v, _v, _v, _v, _v, _v, _i, _i, _i, _v, _v, _v, _v, _i, _i, _i, _i, _i, _i, _i, _i, _v, _z, _v, _v)),
     "amos_slic_center_count": (_i, (_i, _i, _i, _v, _v)),
     "amos_slic_create": (_i, (_i, _v, _i, _i, _i, _v)),
     "amos_slic_destroy": (None, (_v,)),
@@ -804,12 +810,45 @@ def mask_coef_at_priors(stream_ptr, level_ptrs, level_hw, level_blocked, cin, we
                                                  batch, n_slots, anchors, mask_dim, out_ptr), "amos_mask_coef_at_priors_device")
 
 
+def mask_candidates_bytes(batch, n_priors, n_classes_with_background):
+    """amos_mask_candidates_bytes: the size of the candidate lists' buffer (counters + batch x classes lists of n_priors entries)."""
+    return int(lib().amos_mask_candidates_bytes(batch, n_priors, n_classes_with_background))
+
+
+def mask_candidates_reset(stream_ptr, candidates_ptr, batch, n_classes_with_background):
+    """amos_mask_candidates_reset_device: the lists' counters to zero (one memset on the stream), before the first level's mask_head_candidates."""
+    _check(lib().amos_mask_candidates_reset_device(stream_ptr, candidates_ptr, batch, n_classes_with_background), "amos_mask_candidates_reset_device")
+
+
+def mask_head_candidates(stream_ptr, raw_ptr, bias_ptr, loc_ptr, coef_ptr, candidates_ptr, threshold, batch, cells, channels_padded, anchors,
+                         n_classes_with_background, mask_dim, n_priors_total, prior_offset):
+    """amos_mask_head_candidates_device: mask_head_outputs with, instead of a softmax tensor, every class score above `threshold` appended to the
+    list of its (frame, class)."""
+    _check(lib().amos_mask_head_candidates_device(stream_ptr, raw_ptr, bias_ptr, loc_ptr, coef_ptr, candidates_ptr, threshold, batch, cells, channels_padded,
+                                                  anchors, n_classes_with_background, mask_dim, n_priors_total, prior_offset), "amos_mask_head_candidates_device")
+
+
+def mask_topk_lists(stream_ptr, counts_ptr, entries_ptr, capacity, values_ptr, indices_ptr, rows, k):
+    """amos_mask_topk_lists_device: top-k (score descending, lowest index first) of lists of (score key << 32 | ~index) entries."""
+    _check(lib().amos_mask_topk_lists_device(stream_ptr, counts_ptr, entries_ptr, capacity, values_ptr, indices_ptr, rows, k), "amos_mask_topk_lists_device")
+
+
+def mask_person_masks_candidates(stream_ptr, loc_ptr, candidates_ptr, coef_ptr, priors_ptr, proto_ptr, batch, n_priors, n_classes_with_background, mask_dim,
+                                 proto_h, proto_w, out_h, out_w, workspace_ptr, workspace_bytes, masks_ptr, found_ptr):
+    """amos_mask_person_masks_candidates_device: mask_person_masks from the candidate lists mask_head_candidates wrote."""
+    _check(lib().amos_mask_person_masks_candidates_device(stream_ptr, loc_ptr, candidates_ptr, coef_ptr, priors_ptr, proto_ptr, batch, n_priors,
+                                                          n_classes_with_background, mask_dim, proto_h, proto_w, out_h, out_w, workspace_ptr, workspace_bytes,
+                                                          masks_ptr, found_ptr), "amos_mask_person_masks_candidates_device")
+
+
 def mask_person_masks_at_priors(stream_ptr, loc_ptr, scores_ptr, scores_are_class_scores, level_ptrs, level_hw, level_blocked, cin, anchors, mask_weight_ptr,
                                 mask_bias_ptr, priors_ptr, proto_ptr, batch, n_priors, n_classes_with_background, mask_dim, proto_h, proto_w, out_h, out_w,
                                 workspace_ptr, workspace_bytes, masks_ptr, found_ptr):
-    """amos_mask_person_masks_at_priors_device (scores_ptr: the softmax tensor) or amos_mask_person_masks_scores_at_priors_device (Detect's class
-    scores): mask_person_masks with the displayed detections' coefficients evaluated from the `upfeature` levels instead of read from a tensor."""
-    name = "amos_mask_person_masks_scores_at_priors_device" if scores_are_class_scores else "amos_mask_person_masks_at_priors_device"
+    """amos_mask_person_masks_at_priors_device (scores_ptr: the softmax tensor), amos_mask_person_masks_scores_at_priors_device (True: Detect's class
+    scores) or amos_mask_person_masks_candidates_at_priors_device ("candidates": the lists of mask_head_candidates): mask_person_masks with the
+    displayed detections' coefficients evaluated from the `upfeature` levels instead of read from a tensor."""
+    name = ("amos_mask_person_masks_candidates_at_priors_device" if scores_are_class_scores == "candidates" else
+            "amos_mask_person_masks_scores_at_priors_device" if scores_are_class_scores else "amos_mask_person_masks_at_priors_device")
     _check(getattr(lib(), name)(stream_ptr, loc_ptr, scores_ptr, *_coef_levels(level_ptrs, level_hw, level_blocked, anchors), cin, anchors, mask_weight_ptr,
                                 mask_bias_ptr, priors_ptr, proto_ptr, batch, n_priors, n_classes_with_background, mask_dim, proto_h, proto_w, out_h, out_w,
                                 workspace_ptr, workspace_bytes, masks_ptr, found_ptr), name)

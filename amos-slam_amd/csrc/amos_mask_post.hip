@@ -128,10 +128,17 @@ __global__ __launch_bounds__(256) void k_person_mask(const float *__restrict__ m
 // coef == nullptr: the layer carries no coefficient channels ([A x 4 box | A x (1 + C) class | padding], SharedHead's scores-and-boxes layer);
 // the displayed detections' coefficients then come from k_coef_at_priors.
 // grid = (ceil(cells / kHeadCells), B), block = 256.
+// kCand (amos_mask_head_candidates_device): neither conf nor scores; every class c >= 1 of prior p whose softmax quotient (the one conf would
+// hold) exceeds thresh is appended as (topk_key(q) << 32 | ~p) to the list of row (frame, c - 1): candEntries + row * P, its length in
+// candCount[row].  The work-group counts its entries per row in LDS, reserves each row's run by ONE global atomic, then writes them.  The order
+// inside a list depends on the run; the entries are unique, and k_topk_lists sorts them.
 constexpr int kHeadCells = 16;
+__device__ __forceinline__ unsigned topk_key(float f);
+template <bool kCand>
 __global__ __launch_bounds__(256) void k_head_outputs(const float *__restrict__ raw, const float *__restrict__ bias, float *__restrict__ loc, float *__restrict__ conf,
                                                      float *__restrict__ coef, int cells, int cpad, int A, int C1, int D, int P, int pOff,
-                                                     float *__restrict__ scores, float thresh)
+                                                     float *__restrict__ scores, float thresh, int *__restrict__ candCount,
+                                                     unsigned long long *__restrict__ candEntries)
 {
     extern __shared__ float sh[];  // [kHeadCells][cpad]
     const int b = blockIdx.y, c0 = blockIdx.x * kHeadCells, nc = min(kHeadCells, cells - c0);
@@ -143,6 +150,8 @@ __global__ __launch_bounds__(256) void k_head_outputs(const float *__restrict__ 
         v.x = __fadd_rn(v.x, bb.x); v.y = __fadd_rn(v.y, bb.y); v.z = __fadd_rn(v.z, bb.z); v.w = __fadd_rn(v.w, bb.w);
         *reinterpret_cast<float4 *>(sh + e) = v;
     }
+    __shared__ unsigned sCnt[kCand ? 256 : 1], sBase[kCand ? 256 : 1];  // kCand, per class row (C <= 256): this group's entries; its run's start in the list
+    if constexpr (kCand) sCnt[threadIdx.x] = 0u;
     __syncthreads();
     // softmax over each prior's 1 + C class values, in place.  The maximum and the sum are taken by ONE thread per prior (sequential
     // order: the same bits whatever the work-group shape); the exponentials and the divisions by all threads.  The element loops walk
@@ -159,7 +168,20 @@ __global__ __launch_bounds__(256) void k_head_outputs(const float *__restrict__ 
             if (r >= (n)) { r -= (n); cell++; }                                                \
         }                                                                                      \
     }
-    if ((int)threadIdx.x < nc * A) {
+    if constexpr (kCand) {
+        // (the maximum does not depend on the order it is taken in -- fmaxf skips NaNs either way, and a zero of either sign gives the same
+        // exponentials: `parts` adjacent lanes share a prior's values and meet in a butterfly; the sum below keeps its one order)
+        int parts = 1;
+        while (parts * 2 * kHeadCells * A <= 256) parts *= 2;  // (a power of two: whole groups inside a wave)
+        const int prior = (int)threadIdx.x / parts, part = (int)threadIdx.x - prior * parts;
+        const bool have = prior < nc * A;
+        const int cell = have ? prior / A : 0, a = have ? prior - cell * A : 0;
+        const float *v = sh + cell * cpad + nLoc + a * C1;
+        float m = v[min(part, C1 - 1)];
+        for (int c = part + parts; c < C1; c += parts) m = fmaxf(m, v[c]);
+        for (int d = 1; d < parts; d <<= 1) m = fmaxf(m, __shfl_xor(m, d, 64));
+        if (have && part == 0) sMax[prior] = m;
+    } else if ((int)threadIdx.x < nc * A) {
         const int cell = threadIdx.x / A, a = threadIdx.x - cell * A;
         const float *v = sh + cell * cpad + nLoc + a * C1;
         float m = v[0];
@@ -184,11 +206,55 @@ __global__ __launch_bounds__(256) void k_head_outputs(const float *__restrict__ 
         const int cell = threadIdx.x / A, a = threadIdx.x - cell * A;
         const float *v = sh + cell * cpad + nLoc + a * C1;
         float sum = 0.f;
-        for (int c = 0; c < C1; c++) sum = __fadd_rn(sum, v[c]);
+#pragma unroll 16
+        for (int c = 0; c < C1; c++) sum = __fadd_rn(sum, v[c]);  // (unrolled: sixteen LDS reads under way per step of the chain; the order of the sum is unchanged)
         sSum[threadIdx.x] = sum;
     }
     __syncthreads();
     const size_t prior0 = (size_t)b * P + pOff + (size_t)c0 * A;  // first prior of this work-group
+    if constexpr (kCand) {
+        // Only the few quotients that can pass are divided: exp / sum > thresh implies exp > sum * (thresh * 0.99) (two roundings of 2^-24
+        // against a margin of 1 %), and the exact test follows for those.  A thread remembers its passing trips in a bit mask (at most 63
+        // trips: cpad <= 1000) and writes only those once its rows' runs are reserved.
+        const int C = C1 - 1;
+        const float pre = thresh * 0.99f;
+        unsigned long long mine = 0ull;
+        int trip = 0;
+        AMOS_HEAD_FOREACH(nConf, {
+            int a = (int)((float)r * invC1);
+            a -= a * C1 > r ? 1 : 0;
+            a += (a + 1) * C1 <= r ? 1 : 0;
+            const int c = r - a * C1;
+            const float ev = sh[cell * cpad + nLoc + r];
+            const float s = sSum[cell * A + a];
+            if (c >= 1 && ev > s * pre && ev / s > thresh) {  // (NaN compares false)
+                mine |= 1ull << trip;
+                atomicAdd(&sCnt[c - 1], 1u);
+            }
+            trip++;
+        })
+        __syncthreads();
+        unsigned base = 0u;
+        if ((int)threadIdx.x < C && sCnt[threadIdx.x]) base = (unsigned)atomicAdd(&candCount[(size_t)b * C + threadIdx.x], (int)sCnt[threadIdx.x]);
+        AMOS_HEAD_FOREACH(nLoc, loc[prior0 * 4 + e] = sh[cell * cpad + r])  // (while the atomics are under way)
+        if (nCoef) AMOS_HEAD_FOREACH(nCoef, coef[prior0 * D + e] = sh[cell * cpad + nLoc + nConf + r])
+        if ((int)threadIdx.x < C) {
+            sBase[threadIdx.x] = base;
+            sCnt[threadIdx.x] = 0u;
+        }
+        __syncthreads();
+        while (mine) {
+            const int tr = (int)__builtin_ctzll(mine);
+            mine &= mine - 1ull;
+            const int e = (int)threadIdx.x + 256 * tr, cell = e / nConf, r = e - cell * nConf, a = r / C1, c = r - a * C1;
+            const float q = sh[cell * cpad + nLoc + r] / sSum[cell * A + a];  // the quotient conf would hold
+            const unsigned slot = sBase[c - 1] + atomicAdd(&sCnt[c - 1], 1u);
+            const unsigned prior = (unsigned)(pOff + (c0 + cell) * A + a);
+            if (slot < (unsigned)P)  // (always, with counters zeroed before the pass: a prior enters a row once)
+                candEntries[((size_t)b * C + (c - 1)) * P + slot] = ((unsigned long long)topk_key(q) << 32) | (0xffffffffu - prior);
+        }
+        return;
+    }
     AMOS_HEAD_FOREACH(nLoc, loc[prior0 * 4 + e] = sh[cell * cpad + r])
     if (nCoef) AMOS_HEAD_FOREACH(nCoef, coef[prior0 * D + e] = sh[cell * cpad + nLoc + nConf + r])
     if (!scores) {
@@ -722,6 +788,167 @@ __global__ __launch_bounds__(kTopkLdsThreads) void k_topk_rows_lds(const float *
     }
 }
 
+// The same selection over a LIST of candidates instead of a dense row (amos_mask_head_candidates_device writes the lists): `count` unique
+// 64-bit entries (key << 32 | ~index) in any order.  One work-group per list.  Nothing: -1 / index 0 in every slot.  Up to kTopkList entries:
+// loaded into LDS and sorted by the bitonic network of k_topk_rows' sparse path.  More: the k-th largest ENTRY by a radix select over the 64
+// bits (11 + 11 + 10 bits of the key, then of the index word; a pass whose bin is wanted whole ends the search early -- with distinct
+// scores the index word is never looked at), the k entries from there up gathered and sorted.  The entries are unique, so the result is the
+// same whatever order the list came in.  Slots past `count` hold -1 / index 0.  grid = lists, block = kListThreads; k <= 256.
+constexpr int kListThreads = 256, kListLoads = 16;  // (sixteen independent loads under way per thread and trip of a scan)
+__device__ __forceinline__ void hist_count(unsigned *hist, bool in, unsigned bin, int lane)
+{   // (a list that is mostly one value: one lane adds the wave's count instead of 64 atomics on one address)
+    const unsigned long long m = __ballot(in);
+    if (m) {
+        const int first = (int)__builtin_ctzll(m);
+        const unsigned b0 = __builtin_amdgcn_readlane(bin, first);  // the first counting lane's bin
+        const bool same = __ballot(in && bin != b0) == 0ull;
+        if (same) {
+            if (lane == first) atomicAdd(&hist[b0], (unsigned)__popcll(m));
+        } else if (in) {
+            atomicAdd(&hist[bin], 1u);
+        }
+    }
+}
+__global__ __launch_bounds__(kListThreads) void k_topk_lists(const int *__restrict__ counts, const unsigned long long *__restrict__ entries, int cap,
+                                                   float *__restrict__ values, long long *__restrict__ indices, int k, int perFrame)
+{
+    // Work-group g takes list (g % frames) * perFrame + g / frames: the lists of ONE class in consecutive work-groups.  A frame's long lists
+    // are those of the same few classes in every frame; in list order they are perFrame apart (80: a multiple of the eight XCDs the groups
+    // are dealt over), so every person list of a pass would land on the same XCD's 32 compute units.
+    const int frames = (int)gridDim.x / perFrame, row = ((int)blockIdx.x % frames) * perFrame + (int)blockIdx.x / frames;
+    __shared__ unsigned long long list[kTopkList];
+    __shared__ unsigned hist[kTopkBins];
+    __shared__ unsigned part[256];
+    __shared__ unsigned long long sel[256];
+    __shared__ unsigned long long sPrefix, sMask;
+    __shared__ unsigned sNeed, sTaken, sDone;
+    const int t = threadIdx.x, lane = t & 63;
+    const int count = min(max(counts[row], 0), cap);
+    const unsigned long long *src = entries + (size_t)row * cap;
+    float *val = values + (size_t)row * k;
+    long long *idx = indices + (size_t)row * k;
+    if (count == 0) {
+        if (t < k) { val[t] = -1.f; idx[t] = 0; }
+        return;
+    }
+    if (count <= kTopkList) {
+        unsigned n2 = 64;
+        while (n2 < (unsigned)count) n2 <<= 1;
+        for (unsigned i = t; i < n2; i += kListThreads) list[i] = i < (unsigned)count ? src[i] : 0ull;  // padding sorts last
+        __syncthreads();
+        for (unsigned size = 2; size <= n2; size <<= 1)
+            for (unsigned stride = size >> 1; stride > 0; stride >>= 1) {
+                for (unsigned i = t; i < n2 / 2; i += kListThreads) {  // pair (lo, lo + stride) of the bitonic network, descending overall
+                    const unsigned lo = ((i / stride) * stride * 2) + (i % stride), hi = lo + stride;
+                    const unsigned long long a = list[lo], b = list[hi];
+                    const bool descending = (lo & size) == 0;
+                    if (descending ? a < b : a > b) { list[lo] = b; list[hi] = a; }
+                }
+                __syncthreads();
+            }
+        if (t < k) {
+            const unsigned long long v = t < count ? list[t] : 0ull;
+            val[t] = t < count ? topk_value((unsigned)(v >> 32)) : -1.f;
+            idx[t] = t < count ? (long long)(0xffffffffu - (unsigned)(v & 0xffffffffu)) : 0;
+        }
+        return;
+    }
+    // ---- radix select of the k-th largest entry (count > kTopkList >= k)
+    if (t == 0) { sPrefix = 0ull; sMask = 0ull; sNeed = (unsigned)k; sTaken = 0u; sDone = 0u; }
+    __syncthreads();
+    const int shifts[6] = {53, 42, 32, 21, 10, 0}, widths[6] = {11, 11, 10, 11, 11, 10};
+    for (int pass = 0; pass < 6; pass++) {
+        const int shift = shifts[pass];
+        const unsigned bins = 1u << widths[pass];
+        for (int b = t; b < kTopkBins; b += kListThreads) hist[b] = 0;
+        __syncthreads();
+        const unsigned long long prefix = sPrefix, mask = sMask;
+        const unsigned need = sNeed;
+        for (int i0 = 0; i0 < count; i0 += kListThreads * kListLoads) {
+            unsigned long long e[kListLoads];
+#pragma unroll
+            for (int u = 0; u < kListLoads; u++) {
+                const int i = i0 + u * kListThreads + t;
+                e[u] = i < count ? src[i] : 0ull;
+            }
+#pragma unroll
+            for (int u = 0; u < kListLoads; u++) {
+                const int i = i0 + u * kListThreads + t;
+                hist_count(hist, i < count && (e[u] & mask) == prefix, (unsigned)(e[u] >> shift) & (bins - 1u), lane);
+            }
+        }
+        __syncthreads();
+        if (t < 256) {  // partial sums of 8 bins per thread
+            unsigned p = 0;
+            for (int b = 0; b < 8; b++) p += hist[8 * t + b];
+            part[t] = p;
+        }
+        __syncthreads();
+        if (t < 64) {  // wave 0: the bin where the count from the top reaches `need`
+            const unsigned q = part[4 * lane] + part[4 * lane + 1] + part[4 * lane + 2] + part[4 * lane + 3];  // bins 32 lane .. 32 lane + 31
+            unsigned suffix = q;  // inclusive suffix sum over lanes >= lane
+            for (int d = 1; d < 64; d <<= 1) {
+                const unsigned o = __shfl_down(suffix, d, 64);
+                if (lane + d < 64) suffix += o;
+            }
+            const unsigned above = suffix - q;
+            if (above < need && suffix >= need) {  // exactly one lane
+                unsigned acc = above;
+                int bin = 32 * lane + 31;
+                for (; bin > 32 * lane; bin--) {
+                    const unsigned c = hist[bin];
+                    if (acc + c >= need) break;
+                    acc += c;
+                }
+                sPrefix = prefix | ((unsigned long long)bin << shift);
+                sMask = mask | ((unsigned long long)(bins - 1u) << shift);
+                sNeed = need - acc;  // how many of this bin's entries are still wanted ...
+                sDone = hist[bin] == need - acc ? 1u : 0u;  // ... all of them: every entry >= the bin's lowest value belongs to the top k
+            }
+        }
+        __syncthreads();
+        if (sDone) break;  // (uniform; the last pass always ends here: the entries are unique)
+    }
+    const unsigned long long T = sPrefix;  // the remaining low bits zero: the lowest value of the last bin
+    for (int i0 = 0; i0 < count; i0 += kListThreads * kListLoads) {
+        unsigned long long e[kListLoads];
+#pragma unroll
+        for (int u = 0; u < kListLoads; u++) {
+            const int i = i0 + u * kListThreads + t;
+            e[u] = i < count ? src[i] : 0ull;
+        }
+#pragma unroll
+        for (int u = 0; u < kListLoads; u++) {
+            const int i = i0 + u * kListThreads + t;
+            if (i < count && e[u] >= T) {
+                const unsigned slot = atomicAdd(&sTaken, 1u);
+                if (slot < 256u) sel[slot] = e[u];  // (exactly k of them)
+            }
+        }
+    }
+    __syncthreads();
+    for (unsigned i = min(sTaken, 256u) + t; i < 256u; i += kListThreads) sel[i] = 0ull;  // padding sorts last
+    __syncthreads();
+    // ---- bitonic sort of 256 entries, descending (the first 256 threads; everybody keeps the barriers)
+    for (int size = 2; size <= 256; size <<= 1)
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            unsigned long long a = 0ull, b = 0ull;
+            if (t < 256) { a = sel[t]; b = sel[t ^ stride]; }
+            __syncthreads();
+            if (t < 256) {
+                const bool descending = (t & size) == 0, lower = (t & stride) == 0;
+                const unsigned long long hi = a > b ? a : b, lo = a > b ? b : a;
+                sel[t] = (descending == lower) ? hi : lo;
+            }
+            __syncthreads();
+        }
+    if (t < k) {
+        const unsigned long long v = sel[t];
+        val[t] = topk_value((unsigned)(v >> 32));
+        idx[t] = (long long)(0xffffffffu - (unsigned)(v & 0xffffffffu));
+    }
+}
+
 
 // ---- the rest of Detect + postprocess + prep_display for the static-shape batch path (mask/detect.py detect_batch, mask/post.py
 // person_mask_batch), fused: PyTorch spends ~75 small launches per pass on these steps (box decoding, two gathers, where / topk / gathers of
@@ -749,7 +976,13 @@ __global__ __launch_bounds__(256) void k_nms_alive(const float4 *__restrict__ bo
 {
     __shared__ float4 sb[256];
     __shared__ float sarea[256];
-    const int j = threadIdx.x, list = blockIdx.x, b = list / C;
+    // (work-group g takes list (g % frames) * C + g / frames: one class's lists in consecutive groups, dealt over all XCDs -- see k_topk_lists)
+    const int frames = (int)gridDim.x / C, list = ((int)blockIdx.x % frames) * C + (int)blockIdx.x / frames;
+    const int j = threadIdx.x, b = list / C;
+    if (scores[(size_t)list * k] <= 0.f) {  // (uniform) sorted descending: no score of the list is > 0, so nothing is alive -- an empty candidate list
+        if (j < k) out[(size_t)list * k + j] = -1.f;
+        return;
+    }
     float4 me = {0.f, 0.f, 0.f, 0.f};
     float myArea = 0.f;
     if (j < k) {
@@ -999,11 +1232,71 @@ int amos_mask_head_outputs_scores_device(void *stream, const float *d_raw, const
         return AMOS_ERR_INVALID;
     }
     if (batch == 0) return AMOS_OK;
-    hipLaunchKernelGGL(k_head_outputs, dim3((cells + kHeadCells - 1) / kHeadCells, batch), dim3(256), (size_t)kHeadCells * channels_padded * sizeof(float),
+    hipLaunchKernelGGL(k_head_outputs<false>, dim3((cells + kHeadCells - 1) / kHeadCells, batch), dim3(256), (size_t)kHeadCells * channels_padded * sizeof(float),
                        (hipStream_t)stream, d_raw, d_bias, d_loc, d_conf, d_coef, cells, channels_padded, anchors, n_classes_with_background, mask_dim,
-                       n_priors_total, prior_offset, d_scores, threshold);
+                       n_priors_total, prior_offset, d_scores, threshold, (int *)nullptr, (unsigned long long *)nullptr);
     AMOS_HIP_CHECK(hipGetLastError());
     return AMOS_OK;
+}
+
+// ---- candidate lists: [batch x classes int32 counters, padded to 256 bytes][batch x classes lists of n_priors 8-byte entries]
+static size_t cand_counts_bytes(int batch, int classes) { return ((size_t)batch * classes * sizeof(int) + 255) & ~(size_t)255; }
+
+size_t amos_mask_candidates_bytes(int batch, int n_priors, int n_classes_with_background)
+{
+    if (batch < 1 || n_priors < 1 || n_classes_with_background < 2) return 0;
+    const int C = n_classes_with_background - 1;
+    return cand_counts_bytes(batch, C) + (size_t)batch * C * n_priors * sizeof(unsigned long long);
+}
+
+int amos_mask_candidates_reset_device(void *stream, void *d_candidates, int batch, int n_classes_with_background)
+{
+    if (!d_candidates || batch < 0 || n_classes_with_background < 2) { set_error("amos_mask_candidates_reset_device: invalid argument"); return AMOS_ERR_INVALID; }
+    if (batch == 0) return AMOS_OK;
+    AMOS_HIP_CHECK(hipMemsetAsync(d_candidates, 0, (size_t)batch * (n_classes_with_background - 1) * sizeof(int), (hipStream_t)stream));
+    return AMOS_OK;
+}
+
+int amos_mask_head_candidates_device(void *stream, const float *d_raw, const float *d_bias, float *d_loc, float *d_coef, void *d_candidates, float threshold,
+                                     int batch, int cells, int channels_padded, int anchors, int n_classes_with_background, int mask_dim, int n_priors_total,
+                                     int prior_offset)
+{
+    const long long used = (long long)anchors * (4 + n_classes_with_background + (d_coef ? mask_dim : 0));  // d_coef NULL: no coefficient channels
+    if (!d_raw || !d_bias || !d_loc || !d_candidates || !(threshold >= 0.f) || batch < 0 || cells < 1 || anchors < 1 || n_classes_with_background < 2 ||
+        n_classes_with_background > 257 || mask_dim < 1 || channels_padded % 4 != 0 || used > channels_padded || channels_padded > 1000 || prior_offset < 0 ||
+        (long long)prior_offset + (long long)cells * anchors > n_priors_total || batch > 65535 || kHeadCells * anchors > 256 ||
+        ((uintptr_t)d_raw | (uintptr_t)d_bias | (uintptr_t)d_candidates) % 16 != 0) {
+        set_error("amos_mask_head_candidates_device: invalid argument (2 <= classes incl. background <= 257, threshold >= 0)");
+        return AMOS_ERR_INVALID;
+    }
+    if (batch == 0) return AMOS_OK;
+    uint8_t *cand = (uint8_t *)d_candidates;
+    hipLaunchKernelGGL(k_head_outputs<true>, dim3((cells + kHeadCells - 1) / kHeadCells, batch), dim3(256), (size_t)kHeadCells * channels_padded * sizeof(float),
+                       (hipStream_t)stream, d_raw, d_bias, d_loc, (float *)nullptr, d_coef, cells, channels_padded, anchors, n_classes_with_background, mask_dim,
+                       n_priors_total, prior_offset, (float *)nullptr, threshold, (int *)cand,
+                       (unsigned long long *)(cand + cand_counts_bytes(batch, n_classes_with_background - 1)));
+    AMOS_HIP_CHECK(hipGetLastError());
+    return AMOS_OK;
+}
+
+static int launch_topk_lists(hipStream_t stream, const int *d_counts, const unsigned long long *d_entries, int capacity, float *d_values, long long *d_indices, int rows,
+                             int k, int per_frame)
+{
+    hipLaunchKernelGGL(k_topk_lists, dim3(rows), dim3(kListThreads), 0, stream, d_counts, d_entries, capacity, d_values, d_indices, k,
+                       per_frame >= 1 && rows % per_frame == 0 ? per_frame : 1);
+    AMOS_HIP_CHECK(hipGetLastError());
+    return AMOS_OK;
+}
+
+int amos_mask_topk_lists_device(void *stream, const int *d_counts, const unsigned long long *d_entries, int capacity, float *d_values, long long *d_indices,
+                                int rows, int k)
+{
+    if (!d_counts || !d_entries || !d_values || !d_indices || rows < 0 || capacity < 1 || k < 1 || k > 256 || (uintptr_t)d_entries % 8 != 0) {
+        set_error("amos_mask_topk_lists_device: invalid argument (1 <= k <= 256)");
+        return AMOS_ERR_INVALID;
+    }
+    if (rows == 0) return AMOS_OK;
+    return launch_topk_lists((hipStream_t)stream, d_counts, d_entries, capacity, d_values, d_indices, rows, k, 1);
 }
 
 // rows that fit LDS as keys take k_topk_rows_lds (AMOS_TOPK_LDS=0 in the environment: always the five-scan kernel -- A/B runs)
@@ -1088,7 +1381,7 @@ static int fill_coef_levels(const char *who, CoefLevels &lv, const float *const 
                             const int *level_offsets, int n_levels, int batch, int cin, int anchors, int mask_dim, const float *d_weight, const float *d_bias);
 static int launch_coef_at_priors(hipStream_t st, const CoefLevels &lv, int cin, const float *d_weight, const float *d_bias, const int *d_idx, int batch, int n,
                                  int anchors, int mask_dim, float *d_out);
-static int person_masks(void *stream, const float *d_loc, const float *d_conf, const float *d_scores, const float *d_coef, const LazyCoef *lazy, const float *d_priors,
+static int person_masks(void *stream, const float *d_loc, const float *d_conf, const float *d_scores, const void *d_cand, const float *d_coef, const LazyCoef *lazy, const float *d_priors,
                         const float *d_proto, int batch, int n_priors, int n_classes_with_background, int mask_dim, int proto_h, int proto_w, int out_h, int out_w,
                         void *d_workspace, size_t workspace_bytes, uint8_t *d_masks, uint8_t *d_found);
 
@@ -1097,7 +1390,7 @@ int amos_mask_person_masks_device(void *stream, const float *d_loc, const float 
                                   void *d_workspace, size_t workspace_bytes, uint8_t *d_masks, uint8_t *d_found)
 {
     if (!d_conf) { set_error("amos_mask_person_masks_device: invalid argument"); return AMOS_ERR_INVALID; }
-    return person_masks(stream, d_loc, d_conf, nullptr, d_coef, nullptr, d_priors, d_proto, batch, n_priors, n_classes_with_background, mask_dim, proto_h, proto_w, out_h, out_w,
+    return person_masks(stream, d_loc, d_conf, nullptr, nullptr, d_coef, nullptr, d_priors, d_proto, batch, n_priors, n_classes_with_background, mask_dim, proto_h, proto_w, out_h, out_w,
                         d_workspace, workspace_bytes, d_masks, d_found);
 }
 
@@ -1106,7 +1399,7 @@ int amos_mask_person_masks_scores_device(void *stream, const float *d_loc, const
                                          void *d_workspace, size_t workspace_bytes, uint8_t *d_masks, uint8_t *d_found)
 {
     if (!d_scores) { set_error("amos_mask_person_masks_scores_device: invalid argument"); return AMOS_ERR_INVALID; }
-    return person_masks(stream, d_loc, nullptr, d_scores, d_coef, nullptr, d_priors, d_proto, batch, n_priors, n_classes_with_background, mask_dim, proto_h, proto_w, out_h, out_w,
+    return person_masks(stream, d_loc, nullptr, d_scores, nullptr, d_coef, nullptr, d_priors, d_proto, batch, n_priors, n_classes_with_background, mask_dim, proto_h, proto_w, out_h, out_w,
                         d_workspace, workspace_bytes, d_masks, d_found);
 }
 
@@ -1170,7 +1463,7 @@ int amos_mask_person_masks_at_priors_device(void *stream, const float *d_loc, co
                                     anchors, mask_dim, d_mask_weight, d_mask_bias);
     if (rc != AMOS_OK) return rc;
     lazy.cin = cin; lazy.anchors = anchors; lazy.weight = d_mask_weight; lazy.bias = d_mask_bias;
-    return person_masks(stream, d_loc, d_conf, nullptr, nullptr, &lazy, d_priors, d_proto, batch, n_priors, n_classes_with_background, mask_dim, proto_h, proto_w, out_h,
+    return person_masks(stream, d_loc, d_conf, nullptr, nullptr, nullptr, &lazy, d_priors, d_proto, batch, n_priors, n_classes_with_background, mask_dim, proto_h, proto_w, out_h,
                         out_w, d_workspace, workspace_bytes, d_masks, d_found);
 }
 
@@ -1186,18 +1479,43 @@ int amos_mask_person_masks_scores_at_priors_device(void *stream, const float *d_
                                     cin, anchors, mask_dim, d_mask_weight, d_mask_bias);
     if (rc != AMOS_OK) return rc;
     lazy.cin = cin; lazy.anchors = anchors; lazy.weight = d_mask_weight; lazy.bias = d_mask_bias;
-    return person_masks(stream, d_loc, nullptr, d_scores, nullptr, &lazy, d_priors, d_proto, batch, n_priors, n_classes_with_background, mask_dim, proto_h, proto_w, out_h,
+    return person_masks(stream, d_loc, nullptr, d_scores, nullptr, nullptr, &lazy, d_priors, d_proto, batch, n_priors, n_classes_with_background, mask_dim, proto_h, proto_w, out_h,
                         out_w, d_workspace, workspace_bytes, d_masks, d_found);
 }
 
-static int person_masks(void *stream, const float *d_loc, const float *d_conf, const float *d_scores, const float *d_coef, const LazyCoef *lazy, const float *d_priors,
+int amos_mask_person_masks_candidates_device(void *stream, const float *d_loc, const void *d_candidates, const float *d_coef, const float *d_priors,
+                                             const float *d_proto, int batch, int n_priors, int n_classes_with_background, int mask_dim, int proto_h, int proto_w,
+                                             int out_h, int out_w, void *d_workspace, size_t workspace_bytes, uint8_t *d_masks, uint8_t *d_found)
+{
+    if (!d_candidates) { set_error("amos_mask_person_masks_candidates_device: invalid argument"); return AMOS_ERR_INVALID; }
+    return person_masks(stream, d_loc, nullptr, nullptr, d_candidates, d_coef, nullptr, d_priors, d_proto, batch, n_priors, n_classes_with_background, mask_dim, proto_h, proto_w,
+                        out_h, out_w, d_workspace, workspace_bytes, d_masks, d_found);
+}
+
+int amos_mask_person_masks_candidates_at_priors_device(void *stream, const float *d_loc, const void *d_candidates, const float *const *d_levels, const int *level_h,
+                                                       const int *level_w, const int *level_blocked, const int *level_offsets, int n_levels, int cin, int anchors,
+                                                       const float *d_mask_weight, const float *d_mask_bias, const float *d_priors, const float *d_proto, int batch,
+                                                       int n_priors, int n_classes_with_background, int mask_dim, int proto_h, int proto_w, int out_h, int out_w,
+                                                       void *d_workspace, size_t workspace_bytes, uint8_t *d_masks, uint8_t *d_found)
+{
+    LazyCoef lazy;
+    if (!d_candidates) { set_error("amos_mask_person_masks_candidates_at_priors_device: invalid argument"); return AMOS_ERR_INVALID; }
+    const int rc = fill_coef_levels("amos_mask_person_masks_candidates_at_priors_device", lazy.lv, d_levels, level_h, level_w, level_blocked, level_offsets, n_levels, batch,
+                                    cin, anchors, mask_dim, d_mask_weight, d_mask_bias);
+    if (rc != AMOS_OK) return rc;
+    lazy.cin = cin; lazy.anchors = anchors; lazy.weight = d_mask_weight; lazy.bias = d_mask_bias;
+    return person_masks(stream, d_loc, nullptr, nullptr, d_candidates, nullptr, &lazy, d_priors, d_proto, batch, n_priors, n_classes_with_background, mask_dim, proto_h, proto_w,
+                        out_h, out_w, d_workspace, workspace_bytes, d_masks, d_found);
+}
+
+static int person_masks(void *stream, const float *d_loc, const float *d_conf, const float *d_scores, const void *d_cand, const float *d_coef, const LazyCoef *lazy, const float *d_priors,
                         const float *d_proto, int batch, int n_priors, int n_classes_with_background, int mask_dim, int proto_h, int proto_w, int out_h, int out_w,
                         void *d_workspace, size_t workspace_bytes, uint8_t *d_masks, uint8_t *d_found)
 {
     const int B = batch, P = n_priors, C1 = n_classes_with_background, C = C1 - 1, D = mask_dim, k = AMOS_MASK_NMS_TOP_K, nd = AMOS_MASK_TOP_K_DISPLAY;
-    if (!d_loc || (!d_conf && !d_scores) || (!d_coef && !lazy) || !d_priors || !d_proto || !d_workspace || !d_masks || !d_found || B < 1 || B > 65535 || P < k || C1 < 2 || C1 > 200 ||
+    if (!d_loc || (!d_conf && !d_scores && !d_cand) || (!d_coef && !lazy) || !d_priors || !d_proto || !d_workspace || !d_masks || !d_found || B < 1 || B > 65535 || P < k || C1 < 2 || C1 > 200 ||
         D < 4 || D % 4 != 0 || proto_h < 1 || proto_w < 1 || out_h < 1 || out_w < 1 || (size_t)C * k * 4 > 64 * 1024 ||
-        ((uintptr_t)d_loc | (uintptr_t)d_priors | (uintptr_t)d_proto | (uintptr_t)d_coef | (uintptr_t)d_workspace) % 16 != 0) {
+        ((uintptr_t)d_loc | (uintptr_t)d_priors | (uintptr_t)d_proto | (uintptr_t)d_coef | (uintptr_t)d_workspace | (uintptr_t)d_cand) % 16 != 0) {
         set_error("amos_mask_person_masks_device: invalid argument (16-byte aligned tensors, mask_dim %% 4 == 0, at most %d class lists of %d)", 16384 / k, k);
         return AMOS_ERR_INVALID;
     }
@@ -1219,9 +1537,15 @@ static int person_masks(void *stream, const float *d_loc, const float *d_conf, c
     hipStream_t st = (hipStream_t)stream;
     const int total = B * P;
     hipLaunchKernelGGL(k_decode_boxes, dim3((total + 255) / 256), dim3(256), 0, st, (const float4 *)d_loc, (const float4 *)d_priors, boxes, P, total);
-    int rc = d_scores ? AMOS_OK : amos_mask_class_scores_device(stream, d_conf, (float *)(ws + l.cls), B, P, C1, AMOS_MASK_CONF_THRESH);
-    if (rc != AMOS_OK) return rc;
-    rc = amos_mask_topk_rows_sparse_device(stream, cls, topv, topi, B * C, P, k, -1.f);  // (k_class_scores writes -1 for every prior under the threshold)
+    int rc;
+    if (d_cand) {  // the lists of amos_mask_head_candidates_device: no dense score rows at all
+        const uint8_t *cand = (const uint8_t *)d_cand;
+        rc = launch_topk_lists(st, (const int *)cand, (const unsigned long long *)(cand + cand_counts_bytes(B, C)), P, topv, topi, B * C, k, C);
+    } else {
+        rc = d_scores ? AMOS_OK : amos_mask_class_scores_device(stream, d_conf, (float *)(ws + l.cls), B, P, C1, AMOS_MASK_CONF_THRESH);
+        if (rc != AMOS_OK) return rc;
+        rc = amos_mask_topk_rows_sparse_device(stream, cls, topv, topi, B * C, P, k, -1.f);  // (k_class_scores writes -1 for every prior under the threshold)
+    }
     if (rc != AMOS_OK) return rc;
     hipLaunchKernelGGL(k_nms_alive, dim3(B * C), dim3(256), 0, st, boxes, topi, topv, alive, k, P, C, AMOS_MASK_NMS_THRESH);
     int *selPrior = lazy ? (int *)(ws + l.selPrior) : nullptr;

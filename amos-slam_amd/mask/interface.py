@@ -9,7 +9,7 @@ import os
 import torch
 
 from .detect import detect, detect_batch
-from .net import YolactR50, _stem_eligible, lazy_coef_enabled, stem_kernel_enabled
+from .net import YolactR50, _stem_eligible, candidates_enabled, lazy_coef_enabled, stem_kernel_enabled
 from .post import person_mask, person_mask_batch, person_masks_fused
 from .pre import cxx_marshalling, fast_base_transform, resize_f32_cv
 
@@ -94,15 +94,20 @@ class MaskEngine:
         frames; 107 against 80 + 9 us at one frame), so the default stays the softmax tensor and the separate class-score pass.
         Under the same conditions (AMOS_MASK_LAZY_COEF=0 turns it off) the pass is lazy about the mask coefficients: the head's output
         convolution leaves their 96 channels out and the post-processing evaluates the mask layer at the displayed detections' priors
-        (net.lazy_coef_enabled, SharedHead.merge_output_layers).  The mode reaches the network as an attribute set around the call."""
+        (net.lazy_coef_enabled, SharedHead.merge_output_layers).  The mode reaches the network as an attribute set around the call.
+        Under the same conditions again (AMOS_MASK_CANDIDATES=0 turns it off) the head writes no class tensor of either form: only a score above
+        the display threshold can be displayed, suppress a displayed box or change a displayed rank, so the head's kernel appends exactly those
+        to per-class lists and top-k and Fast NMS run over the lists (net.candidates_enabled) -- in place of both AMOS_MASK_HEAD_SCORES settings.
+        Inside a graph capture (FrameSession, capture_graph) the lists' memset is recorded with the pass, ahead of the side-stream fork."""
         fused_post = (self.device.type == "cuda" and self.conv_dtype is None and x.dtype == torch.float32 and x.is_cuda
                       and not torch.is_autocast_enabled() and os.environ.get("AMOS_MASK_FUSED_POST", "1") != "0")
         scores_only = fused_post and os.environ.get("AMOS_MASK_HEAD_SCORES", "0") == "1"
         before, self.net.lazy_coef = getattr(self.net, "lazy_coef", False), fused_post and lazy_coef_enabled()
+        before_cand, self.net.candidates = getattr(self.net, "candidates", False), fused_post and candidates_enabled()
         try:
             pred = self._forward(x, scores_only)
         finally:
-            self.net.lazy_coef = before
+            self.net.lazy_coef, self.net.candidates = before, before_cand
         return self._person_masks(pred, width, height)
 
     def _forward(self, x, scores_only=False):
@@ -141,7 +146,7 @@ class MaskEngine:
     def _person_masks(pred, width, height):
         """(masks uint8 [B, height, width], found bool [B]) of a forward's outputs: the fused library call on the GPU, the torch ops elsewhere"""
         fused = person_masks_fused(pred, width, height)
-        if fused is None and ("conf" not in pred or "mask" not in pred):
+        if fused is None and ("conf" not in pred or "mask" not in pred):  # (candidate lists, class scores only, or no coefficient tensor)
             raise RuntimeError("the pass was run for the fused post-processing (class scores only, or no coefficient tensor), which does not apply to its outputs")
         return fused if fused is not None else person_mask_batch(detect_batch(pred), width, height)
 

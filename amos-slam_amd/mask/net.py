@@ -658,7 +658,7 @@ class SharedHead(nn.Module):
         merged = getattr(self, "merged", None)
         return not (merged is None or not x0.is_cuda or x0.dtype != torch.float32 or torch.is_autocast_enabled() or os.environ.get("AMOS_MASK_FUSED_HEAD", "1") == "0")
 
-    def fused_outputs(self, pyramid, n_priors, br=None, out=None, scores=None, lazy=False):
+    def fused_outputs(self, pyramid, n_priors, br=None, out=None, scores=None, lazy=False, cand=None):
         """All levels' outputs, concatenated, softmax / tanh applied: (loc [B, P, 4], conf [B, P, 81], coef [B, P, 32]), or None when the
         fused path does not apply (no merged layer, not float32 channels-last on the GPU).  Per level: the upfeature convolution, the
         merged output convolution WITHOUT its bias, then ONE HIP kernel (amos_mask_head_outputs_device) that adds the bias, takes the
@@ -672,13 +672,17 @@ class SharedHead(nn.Module):
         lazy: the output convolution is the scores-and-boxes layer (256 channels instead of 384), no coefficient tensor is written (out[2] None)
         and the third result is instead the list of the five levels' upfeature tensors (Blocked where the level travels channel-blocked), which
         mask/post.py hands to amos_mask_person_masks_at_priors_device; with br they are held like every tensor that crosses streams, and the
-        caller keeps them alive until that call is enqueued."""
+        caller keeps them alive until that call is enqueued.
+        cand: the candidate lists' buffer (alloc_candidates: allocated and its counters zeroed on the caller's stream, before any side stream
+        started) -> neither conf nor scores are written (out[1] None); every class score above the display threshold is appended to the list of
+        its (frame, class) by the same kernel (amos_mask_head_candidates_device), and mask/post.py runs top-k and Fast NMS over the lists."""
         x0 = pyramid[0]
         if not self.fused_applies(x0):
             return None
         merged = self.scores_boxes if lazy else self.merged
         ups = [None] * len(pyramid)
-        from .. import mask_head_outputs_scores
+        from .. import mask_head_candidates, mask_head_outputs_scores
+        from .post import SCORE_THRESHOLD
         b, dev = x0.shape[0], x0.device
         n_anchor = self.bbox_layer.out_channels // 4
         if out is None:
@@ -704,6 +708,11 @@ class SharedHead(nn.Module):
             if not raw.is_contiguous(memory_format=torch.channels_last):
                 raw = raw.contiguous(memory_format=torch.channels_last)
             cells = raw.shape[2] * raw.shape[3]
+            if cand is not None:
+                mask_head_candidates(torch.cuda.current_stream(dev).cuda_stream, raw.data_ptr(), merged.bias.data_ptr(), loc.data_ptr(),
+                                     coef.data_ptr() if coef is not None else None, cand.data_ptr(), SCORE_THRESHOLD, b, cells, raw.shape[1], n_anchor,
+                                     NUM_CLASSES, MASK_DIM, n_priors, offs[i])
+                return
             mask_head_outputs_scores(torch.cuda.current_stream(dev).cuda_stream, raw.data_ptr(), merged.bias.data_ptr(), loc.data_ptr(),
                                      conf.data_ptr() if conf is not None else None, coef.data_ptr() if coef is not None else None,
                                      scores.data_ptr() if scores is not None else None,
@@ -729,6 +738,15 @@ class SharedHead(nn.Module):
 
     def alloc_scores(self, b, n_priors, dev):
         return torch.empty((b, NUM_CLASSES - 1, n_priors), dtype=torch.float32, device=dev)
+
+    def alloc_candidates(self, b, n_priors, dev):
+        """The candidate lists of a pass (amos_mask_candidates_bytes: counters, then one list of n_priors slots per frame and class, of which
+        only the live entries are ever touched), the counters zeroed by a memset on the current stream: every level's launch must be ordered
+        behind this call."""
+        from .. import mask_candidates_bytes, mask_candidates_reset
+        cand = torch.empty(mask_candidates_bytes(b, n_priors, NUM_CLASSES), dtype=torch.uint8, device=dev)
+        mask_candidates_reset(torch.cuda.current_stream(dev).cuda_stream, cand.data_ptr(), b, NUM_CLASSES)
+        return cand
 
     def forward(self, x):
         b = x.shape[0]
@@ -776,8 +794,17 @@ def lazy_coef_enabled():
     return os.environ.get("AMOS_MASK_LAZY_COEF", "1") != "0"
 
 
-def _outputs(loc, conf, cls, coef, priors, proto, head=None):
+def candidates_enabled():
+    """AMOS_MASK_CANDIDATES=0: the detector's own passes write the softmax tensor (or, with AMOS_MASK_HEAD_SCORES=1, the dense class scores)
+    and select over dense score rows, as before (A/B runs, tests); default: the head writes per-class lists of the scores above the display
+    threshold and the post-processing selects over those (SharedHead.fused_outputs(cand=...)): the same masks, bit for bit."""
+    return os.environ.get("AMOS_MASK_CANDIDATES", "1") != "0"
+
+
+def _outputs(loc, conf, cls, coef, priors, proto, head=None, cand=None):
     out = {"loc": loc, "priors": priors, "proto": proto}
+    if cand is not None:
+        out["candidates"] = (cand, NUM_CLASSES)  # (the lists, classes incl. background)
     if head is None:
         out["mask"] = coef
     else:  # a lazy pass: what the mask layer would be evaluated from, instead of its values
@@ -842,10 +869,15 @@ class YolactR50(nn.Module):
         transposed class scores, written by the head's output kernel (fused_outputs); mask/post.py takes either.
         With the attribute `lazy_coef` set (MaskEngine._masks_of sets it around its call; not an argument: forward keeps its signature), where
         the fused head applies: no "mask" either, but "upfeature" (the head's five upfeature tensors) and "mask_layer", from which the fused
-        post-processing evaluates the coefficients of the displayed detections alone (SharedHead.fused_outputs(lazy=True))."""
+        post-processing evaluates the coefficients of the displayed detections alone (SharedHead.fused_outputs(lazy=True)).
+        With the attribute `candidates` set (likewise), where the fused head applies: neither "conf" nor "cls" whatever scores_only says, but
+        "candidates" -- per (frame, class) lists of the scores above the display threshold (SharedHead.fused_outputs(cand=...))."""
         feats = self.backbone(x)[1:]
         head = self.prediction_layers[0]
         lazy = bool(getattr(self, "lazy_coef", False)) and len(feats) == 3 and head.lazy_applies(feats[0])
+        want_cand = bool(getattr(self, "candidates", False)) and len(feats) == 3 and head.fused_applies(feats[0])
+        if want_cand:
+            scores_only = False  # (the lists take the place of both forms of the class output)
         pn = self.proto_net  # conv, relu, conv, relu, conv, relu, upsample, relu, conv, relu, conv (+ the final ReLU)
 
         def prototypes(p3):
@@ -871,22 +903,24 @@ class YolactR50(nn.Module):
             for _ in range(2):  # the two extra levels: 3 x 3, stride 2, padding 1
                 sizes.append(((sizes[-1][0] - 1) // 2 + 1, (sizes[-1][1] - 1) // 2 + 1))
             n_priors = sum(h * w for h, w in sizes) * (head.bbox_layer.out_channels // 4)
-            out = head.alloc_outputs(x.shape[0], n_priors, x.device, conf=not scores_only, coef=not lazy)  # before any side stream starts
+            out = head.alloc_outputs(x.shape[0], n_priors, x.device, conf=not (scores_only or want_cand), coef=not lazy)  # before any side stream starts
             cls = head.alloc_scores(x.shape[0], n_priors, x.device) if scores_only else None
+            cand = head.alloc_candidates(x.shape[0], n_priors, x.device) if want_cand else None  # (its memset: on this stream, before the fork)
             pyramid = self.fpn(feats, br, chain)
             priors = priors_of(pyramid)
-            loc, conf, coef = head.fused_outputs(pyramid, priors.shape[0], br, out, cls, lazy)
+            loc, conf, coef = head.fused_outputs(pyramid, priors.shape[0], br, out, cls, lazy, cand)
             proto = prototypes(pyramid[0])
             br.join()  # (a lazy pass: the upfeature tensors made on side streams are read on this one from here on, and live on in the result)
-            return _outputs(loc, conf, cls, coef, priors, proto, head if lazy else None)
+            return _outputs(loc, conf, cls, coef, priors, proto, head if lazy else None, cand)
         pyramid = self.fpn(feats, None, chain)
         proto = prototypes(pyramid[0])
         priors = priors_of(pyramid)
         if head.fused_applies(pyramid[0]):
-            out = head.alloc_outputs(x.shape[0], priors.shape[0], x.device, conf=not scores_only, coef=not lazy)
+            out = head.alloc_outputs(x.shape[0], priors.shape[0], x.device, conf=not (scores_only or want_cand), coef=not lazy)
             cls = head.alloc_scores(x.shape[0], priors.shape[0], x.device) if scores_only else None
-            loc, conf, coef = head.fused_outputs(pyramid, priors.shape[0], None, out, cls, lazy)
-            return _outputs(loc, conf, cls, coef, priors, proto, head if lazy else None)
+            cand = head.alloc_candidates(x.shape[0], priors.shape[0], x.device) if want_cand else None
+            loc, conf, coef = head.fused_outputs(pyramid, priors.shape[0], None, out, cls, lazy, cand)
+            return _outputs(loc, conf, cls, coef, priors, proto, head if lazy else None, cand)
         locs, confs, coefs = zip(*(head(p) for p in pyramid))
         return {"loc": torch.cat(locs, 1), "conf": F.softmax(torch.cat(confs, 1), -1), "mask": torch.cat(coefs, 1),
                 "priors": priors, "proto": proto}

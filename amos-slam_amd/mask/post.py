@@ -98,7 +98,9 @@ def person_masks_fused(pred, w, h):
     GPU): the caller then takes the torch path.
     A lazy pass (YolactR50.forward with lazy_coef: no "mask", but "upfeature" and "mask_layer") goes to amos_mask_person_masks_at_priors_device:
     the mask layer is evaluated at the displayed detections' priors, after the selection, from the head's upfeature tensors -- direct float32
-    sums where the full pass has the Winograd or library convolution's, so the coefficients agree to float32 rounding of a 2 304-term sum."""
+    sums where the full pass has the Winograd or library convolution's, so the coefficients agree to float32 rounding of a 2 304-term sum.
+    A pass with "candidates" (YolactR50.forward with `candidates`: per-class lists of the scores above SCORE_THRESHOLD instead of "conf" or "cls")
+    goes to the _candidates entries: top-k and Fast NMS over the lists, the same masks and `found` bit for bit."""
     ups = pred.get("upfeature")
     loc, coef, priors, proto = pred["loc"], pred.get("mask"), pred["priors"], pred["proto"]
     if ups is not None:
@@ -106,8 +108,9 @@ def person_masks_fused(pred, w, h):
         coef = layer.weight  # (stands in for the dtype checks below)
     cls = pred.get("cls")          # Detect's class scores [B, classes, P] from the head's own kernel (YolactR50.forward(scores_only=True)) ...
     conf = pred.get("conf")        # ... or the softmax tensor [B, P, 1 + classes]
-    scores = cls if cls is not None else conf
-    if scores is None or not (loc.is_cuda and all(t.dtype == torch.float32 for t in (loc, scores, coef, priors, proto))) or proto.dim() != 4:
+    cand, cand_c1 = pred.get("candidates", (None, None))   # ... or the lists of the scores above SCORE_THRESHOLD (uint8 buffer, classes incl. background)
+    scores = cand if cand is not None else cls if cls is not None else conf
+    if scores is None or not (loc.is_cuda and all(t.dtype == torch.float32 for t in (loc, coef, priors, proto) + (() if cand is not None else (scores,)))) or proto.dim() != 4:
         return None
     import os
     if os.environ.get("AMOS_MASK_FUSED_POST", "1") == "0":   # A/B runs and the tests that compare the two paths
@@ -116,7 +119,7 @@ def person_masks_fused(pred, w, h):
     loc, scores, priors, proto = (t.contiguous() for t in (loc, scores, priors, proto))
     B, P = loc.shape[:2]
     ph, pw, D = proto.shape[1:]
-    c1 = cls.shape[1] + 1 if cls is not None else conf.shape[2]
+    c1 = cand_c1 if cand is not None else cls.shape[1] + 1 if cls is not None else conf.shape[2]
     if P < 200 or (c1 - 1) * 200 * 4 > 64 * 1024 or D % 4 != 0:
         return None
     nbytes = mask_post_workspace_bytes(B, P, c1, D, ph, pw)
@@ -137,12 +140,13 @@ def person_masks_fused(pred, w, h):
         data = [u.data if f else u for u, f in zip(ups, blocked)]  # held until the call below is enqueued
         if not all(d.is_contiguous() if f else d.is_contiguous(memory_format=torch.channels_last) for d, f in zip(data, blocked)):
             raise RuntimeError("person_masks_fused: an upfeature tensor is neither channels-last nor channel-blocked")
-        mask_person_masks_at_priors(stream, loc.data_ptr(), scores.data_ptr(), cls is not None, [d.data_ptr() for d in data], [tuple(u.shape[2:]) for u in ups], blocked,
+        mask_person_masks_at_priors(stream, loc.data_ptr(), scores.data_ptr(), "candidates" if cand is not None else cls is not None, [d.data_ptr() for d in data], [tuple(u.shape[2:]) for u in ups], blocked,
                                     layer.in_channels, anchors, weight.data_ptr(), layer.bias.data_ptr(), priors.data_ptr(), proto.data_ptr(), B, P, c1, D, ph, pw,
                                     h, w, ws.data_ptr(), nbytes, out.data_ptr(), found.data_ptr())
         return out, found.bool()
     coef = coef.contiguous()
-    (mask_person_masks_scores if cls is not None else mask_person_masks)(
+    from .. import mask_person_masks_candidates
+    (mask_person_masks_candidates if cand is not None else mask_person_masks_scores if cls is not None else mask_person_masks)(
         stream, loc.data_ptr(), scores.data_ptr(), coef.data_ptr(), priors.data_ptr(), proto.data_ptr(),
         B, P, c1, D, ph, pw, h, w, ws.data_ptr(), nbytes, out.data_ptr(), found.data_ptr())
     return out, found.bool()

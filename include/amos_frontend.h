@@ -956,6 +956,41 @@ int amos_mask_person_masks_scores_at_priors_device(void *stream, const float *d_
                                                    int n_classes_with_background, int mask_dim, int proto_h, int proto_w, int out_h, int out_w,
                                                    void *d_workspace, size_t workspace_bytes, uint8_t *d_masks, uint8_t *d_found);
 
+/* ---- candidate lists: the detector's tail from the scores that can be displayed alone.  Only detections with score > AMOS_MASK_SCORE_THRESHOLD
+ * are displayed, Fast NMS suppresses a box only through higher-scored boxes of its class, and a score at or under the threshold sorts behind
+ * every score above it (per class and across classes, ties by index): such a score can neither be displayed nor change what is.  So the head
+ * writes, instead of a softmax or class-score tensor, one list per (frame, class) of the (score, prior) pairs above the threshold, and top-k and
+ * Fast NMS run over those lists.  Masks and `found` equal the dense entries' bit for bit.
+ * d_candidates: amos_mask_candidates_bytes(batch, n_priors, n_classes_with_background) bytes (16-byte aligned): batch x classes int32 counters
+ * (padded to 256 bytes), then batch x classes lists of n_priors 8-byte entries (score key << 32 | ~prior; only the first `count` of a list are
+ * ever touched).  amos_mask_candidates_reset_device zeroes the counters (one hipMemsetAsync); it goes on a stream every level's
+ * amos_mask_head_candidates_device launch is ordered behind.  The order of a list's entries depends on the run; nothing computed from it does. */
+size_t amos_mask_candidates_bytes(int batch, int n_priors, int n_classes_with_background);
+int amos_mask_candidates_reset_device(void *stream, void *d_candidates, int batch, int n_classes_with_background);
+/* amos_mask_head_outputs_device's kernel for one level with the lists as its class output: d_loc (and d_coef unless NULL) as there, the same
+ * softmax quotients, and every class c >= 1 of prior p with softmax > threshold appended to list (frame, c - 1).  One global atomic per
+ * work-group and list that gains entries.  threshold: AMOS_MASK_SCORE_THRESHOLD for the entries below (any value in [0, that] gives their
+ * result).  n_classes_with_background <= 257. */
+int amos_mask_head_candidates_device(void *stream, const float *d_raw, const float *d_bias, float *d_loc, float *d_coef, void *d_candidates, float threshold,
+                                     int batch, int cells, int channels_padded, int anchors, int n_classes_with_background, int mask_dim,
+                                     int n_priors_total, int prior_offset);
+/* Top-k of `rows` lists of unique 8-byte entries (key << 32 | ~index, key = the order-preserving integer image of a float32 score): d_counts
+ * int32 [rows], list r at d_entries + r x capacity.  d_values / d_indices [rows][k]: score descending, equal scores lowest index first; slots
+ * past a list's count hold score -1 and index 0.  Independent of the order of the entries.  1 <= k <= 256. */
+int amos_mask_topk_lists_device(void *stream, const int *d_counts, const unsigned long long *d_entries, int capacity, float *d_values,
+                                long long *d_indices, int rows, int k);
+/* amos_mask_person_masks_device / amos_mask_person_masks_at_priors_device from the lists amos_mask_head_candidates_device wrote. */
+int amos_mask_person_masks_candidates_device(void *stream, const float *d_loc, const void *d_candidates, const float *d_coef, const float *d_priors,
+                                             const float *d_proto, int batch, int n_priors, int n_classes_with_background, int mask_dim, int proto_h,
+                                             int proto_w, int out_h, int out_w, void *d_workspace, size_t workspace_bytes, uint8_t *d_masks,
+                                             uint8_t *d_found);
+int amos_mask_person_masks_candidates_at_priors_device(void *stream, const float *d_loc, const void *d_candidates, const float *const *d_levels,
+                                                       const int *level_h, const int *level_w, const int *level_blocked, const int *level_offsets,
+                                                       int n_levels, int cin, int anchors, const float *d_mask_weight, const float *d_mask_bias,
+                                                       const float *d_priors, const float *d_proto, int batch, int n_priors,
+                                                       int n_classes_with_background, int mask_dim, int proto_h, int proto_w, int out_h, int out_w,
+                                                       void *d_workspace, size_t workspace_bytes, uint8_t *d_masks, uint8_t *d_found);
+
 
 /* ---------------------------------------------------------------- SLIC superpixels (8f-2) ---- */
 
