@@ -98,6 +98,8 @@ PROTOTYPES = {
     "amos_match_triangulation_batch_device": (_i, (_v, _v, _v, _v, _v, _i, _i, _i)),
     "amos_match_bow_kf": (_i, (_v, _v, _v, _f, _i, _v, _v)),
     "amos_match_triangulation": (_i, (_v, _v, _v, _i, _v, _v, _v, _i, _i, _i, _v, _v)),
+    "amos_match_fuse_batch_device": (_i, (_v, _v)),
+    "amos_match_fuse": (_i, (_v, _v, _i, _v, _i, _i, _v, _v, _v, _v, _v, _v, _i, _v, _v, _i, _i, _i, _v, _v, _v, _v, _v)),
     "amos_mask_pre_create": (_i, (_i, _v, _i, _i, _i, _v)),
     "amos_mask_pre_destroy": (None, (_v,)),
     "amos_mask_pre_stream": (_v, (_v,)),
@@ -1003,6 +1005,41 @@ assert KF_GEOMETRY_DTYPE.itemsize == 44
 KF_STATUS_BAD_INDEX, KF_STATUS_BAD_OCTAVE = 1, 2  # amos_bow_search_stats.status of the keyframe pair searches
 
 
+FUSE_LOCAL, FUSE_SIM3 = 0, 1
+FUSE_CAMERA_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("Ow", "<f4", (3,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"),
+                              ("cy", "<f4"), ("mbf", "<f4"), ("th", "<f4")])  # amos_fuse_camera
+FUSE_STATS_DTYPE = np.dtype([("n_in_view", "<i4"), ("n_accepted", "<i4")])  # amos_fuse_stats
+# amos_window_query (include/amos_host_types.h)
+WINDOW_QUERY_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("ur", "<f4"), ("level", "<i4"), ("src", "<i4"), ("desc", "u1", (32,))])
+
+
+class FuseCamera(C.Structure):
+    """amos_fuse_camera (include/amos_frontend.h): 84 bytes; FUSE_CAMERA_DTYPE is the same record for numpy."""
+    _fields_ = [("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("Ow", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
+                ("cy", C.c_float), ("mbf", C.c_float), ("th", C.c_float)]
+
+
+FUSE_CAMERA_BYTES = 84  # the header's static_assert (amos_fuse.hip)
+assert (C.sizeof(FuseCamera), FUSE_CAMERA_DTYPE.itemsize, FUSE_STATS_DTYPE.itemsize, WINDOW_QUERY_DTYPE.itemsize) == (FUSE_CAMERA_BYTES, 84, 8, 52)
+
+
+class FuseSearch(C.Structure):
+    """amos_fuse_search (include/amos_frontend.h)."""
+    _fields_ = [("d_kps", C.c_void_p), ("d_desc", C.c_void_p), ("d_counts", C.c_void_p), ("d_cell_start", C.c_void_p), ("d_items", C.c_void_p),
+                ("d_u_right", C.c_void_p), ("scale_factors", C.c_void_p), ("inv_level_sigma2", C.c_void_p), ("d_points", C.c_void_p),
+                ("pair_frame", C.c_void_p), ("point_first", C.c_void_p), ("point_count", C.c_void_p), ("out_off", C.c_void_p),
+                ("cameras", C.c_void_p), ("d_skip", C.c_void_p), ("d_query", C.c_void_p), ("d_in_view", C.c_void_p), ("d_best_idx", C.c_void_p),
+                ("d_best_dist", C.c_void_p), ("d_stats", C.c_void_p), ("n_frames", C.c_int32), ("n_pairs", C.c_int32), ("n_points", C.c_int32),
+                ("capacity", C.c_int32), ("n_levels", C.c_int32), ("mode", C.c_int32), ("max_dist", C.c_int32), ("min_x", C.c_float),
+                ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float)]
+
+
+class FrameView(C.Structure):
+    """amos_frame_view (include/amos_host_types.h)."""
+    _fields_ = [("n", C.c_int32), ("keys_un", C.c_void_p), ("descriptors", C.c_void_p), ("u_right", C.c_void_p), ("min_x", C.c_float),
+                ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float)]
+
+
 class BowView(C.Structure):
     """amos_bow_view (include/amos_host_types.h)."""
     _fields_ = [("n", C.c_int32), ("keys", C.c_void_p), ("descriptors", C.c_void_p), ("has_point", C.c_void_p), ("u_right", C.c_void_p),
@@ -1274,6 +1311,47 @@ class OrbMatcher(_Handle):
         _check(self.L.amos_match_triangulation(self.h, C.byref(v1), ptrs, len(views), _p(geo), _p(sf), _p(sg), len(sf), int(bool(only_stereo)),
                                                int(bool(check_orientation)), _p(match12), _p(stats)), "amos_match_triangulation")
         return match12, stats
+
+    def fuse_batch_device(self, d_kps, d_desc, d_counts, d_cell_start, d_items, d_points, n_points, n_frames, pair_frame, point_first, point_count,
+                          out_off, cameras, capacity, scale_factors, inv_level_sigma2, d_query, d_in_view, d_best_idx, d_best_dist, d_stats,
+                          mode=FUSE_LOCAL, max_dist=50, bounds=(0.0, 640.0, 0.0, 480.0), d_u_right=None, d_skip=None):
+        """ORBmatcher::Fuse (ORBmatcher.cc:1020-1177; FUSE_SIM3: :1179-1312) without its write-back for (keyframe slot, point range, camera)
+        pairs of resident keyframes: the pre-filter and the search of every point in one launch.  pair_frame, point_first, point_count, out_off:
+        host ints, one per pair; cameras: host FUSE_CAMERA_DTYPE records.  Asynchronous on the matcher's stream."""
+        sf = np.ascontiguousarray(scale_factors, np.float32)
+        s2 = None if inv_level_sigma2 is None else np.ascontiguousarray(inv_level_sigma2, np.float32)
+        pf, p0, pc, oo = (np.ascontiguousarray(a, np.int32) for a in (pair_frame, point_first, point_count, out_off))
+        cams = np.ascontiguousarray(cameras, FUSE_CAMERA_DTYPE).reshape(-1)
+        if not (len(pf) == len(p0) == len(pc) == len(oo) == len(cams)) or (s2 is not None and len(s2) != len(sf)):
+            raise ValueError("one entry per pair in pair_frame, point_first, point_count, out_off and cameras; one per level in the tables")
+        s = FuseSearch(d_kps, d_desc, d_counts, d_cell_start, d_items, d_u_right, sf.ctypes.data, _p(s2), d_points, _p(pf), _p(p0), _p(pc), _p(oo),
+                       _p(cams), d_skip, d_query, d_in_view, d_best_idx, d_best_dist, d_stats, n_frames, len(cams), n_points, capacity, len(sf), mode,
+                       max_dist, *bounds)
+        _check(self.L.amos_match_fuse_batch_device(self.h, C.byref(s)), "amos_match_fuse_batch_device")
+
+    def fuse(self, kfs, points, pair_frame, point_first, point_count, out_off, cameras, scale_factors, inv_level_sigma2, n_out, skip=None,
+             mode=FUSE_LOCAL, max_dist=50, bounds=(0.0, 640.0, 0.0, 480.0)):
+        """The same from host arrays (amos_match_fuse): kfs is a list of dicts with keys_un, desc and optionally u_right.  Returns (query,
+        in_view, best_idx, best_dist, stats); entries no pair owns keep query 0, in_view 0, best_idx -1, best_dist 256."""
+        keep, views = [], (FrameView * max(len(kfs), 1))()
+        for v, k in zip(views, kfs):
+            kp, d = np.ascontiguousarray(k["keys_un"], KP_DTYPE), np.ascontiguousarray(k["desc"], np.uint8).reshape(-1, 32)
+            ur = None if k.get("u_right") is None else np.ascontiguousarray(k["u_right"], np.float32)
+            keep.append((kp, d, ur))
+            v.n, v.keys_un, v.descriptors, v.u_right = len(kp), kp.ctypes.data, d.ctypes.data, None if ur is None else ur.ctypes.data
+            v.min_x, v.max_x, v.min_y, v.max_y = bounds
+        points = np.ascontiguousarray(points, MAP_POINT_DTYPE)
+        sf = np.ascontiguousarray(scale_factors, np.float32)
+        s2 = None if inv_level_sigma2 is None else np.ascontiguousarray(inv_level_sigma2, np.float32)
+        pf, p0, pc, oo = (np.ascontiguousarray(a, np.int32) for a in (pair_frame, point_first, point_count, out_off))
+        cams = np.ascontiguousarray(cameras, FUSE_CAMERA_DTYPE).reshape(-1)
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8)
+        query, in_view = np.zeros(n_out, WINDOW_QUERY_DTYPE), np.zeros(n_out, np.uint8)
+        best_idx, best_dist, stats = np.full(n_out, -1, np.int32), np.full(n_out, 256, np.int32), np.zeros(len(cams), FUSE_STATS_DTYPE)
+        _check(self.L.amos_match_fuse(self.h, views, len(kfs), _p(points), len(points), len(cams), _p(pf), _p(p0), _p(pc), _p(oo), _p(cams), _p(sk),
+                                      n_out, _p(sf), _p(s2), len(sf), mode, max_dist, _p(query), _p(in_view), _p(best_idx), _p(best_dist),
+                                      _p(stats)), "amos_match_fuse")
+        return query, in_view, best_idx, best_dist, stats
 
     def sync(self):
         _check(self.L.amos_match_sync(self.h), "amos_match_sync")

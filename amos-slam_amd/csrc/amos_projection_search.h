@@ -79,14 +79,15 @@ __device__ __forceinline__ amos_best2 best2_from_keys(unsigned best, unsigned se
 // reference walks the cells x-major, then y, then insertion order = ascending CSR position, and its strict-< updates keep the FIRST of
 // equal distances: a min-reduction over keys (dist << 16 | CSR position) gives the same best two whatever the evaluation order.  All lanes
 // of a group call it; q is read only where `active`, the group's first lane writes *out (if not null); keep(idx) is the search's own filter.
+// lanes_window_keys leaves the two keys in every lane of the group (amos_fuse.hip keeps no record in memory).
 template <class Keep>
-__device__ __forceinline__ void lanes_window_best2(const ProjArgs &a, const FrameView &fv, const WindowQuery &q, bool active, int sub, int initDist,
-                                                   Keep keep, amos_best2 *out)
+__device__ __forceinline__ void lanes_window_keys(const ProjArgs &a, const FrameView &fv, const WindowQuery &q, bool active, int sub, int initDist,
+                                                  Keep keep, unsigned &best, unsigned &second)
 {
     CellRange c;
     c.x0 = 0; c.x1 = -1; c.y0 = c.y1 = 0;  // idle lanes walk no column and keep the group shuffles convergent
     if (active) c = cell_range(q.u, q.v, q.r, a.minX, a.minY, a.wInv, a.hInv);
-    unsigned best = 0xffffffffu, second = 0xffffffffu;
+    best = second = 0xffffffffu;
     for (int ix = c.x0 + sub; ix <= c.x1; ix += kWindowLanes) {
         int b, e;  // cells (ix, y0..y1) are consecutive in the CSR: one item range per column
         column_items(fv.cs, c, ix, b, e);
@@ -101,6 +102,13 @@ __device__ __forceinline__ void lanes_window_best2(const ProjArgs &a, const Fram
         const unsigned ob = __shfl_xor(best, off, kWindowLanes), os = __shfl_xor(second, off, kWindowLanes);
         top2_merge(best, second, ob, os);
     }
+}
+template <class Keep>
+__device__ __forceinline__ void lanes_window_best2(const ProjArgs &a, const FrameView &fv, const WindowQuery &q, bool active, int sub, int initDist,
+                                                   Keep keep, amos_best2 *out)
+{
+    unsigned best, second;
+    lanes_window_keys(a, fv, q, active, sub, initDist, keep, best, second);
     if (out && sub == 0) *out = best2_from_keys(best, second, fv.it, initDist);
 }
 

@@ -703,6 +703,83 @@ int amos_match_triangulation(amos_match *m, const struct amos_bow_view *k1, cons
                              const amos_kf_geometry *geometry, const float *scale_factors, const float *level_sigma2, int n_levels,
                              int only_stereo, int check_orientation, int32_t *match12, amos_bow_search_stats *stats);
 
+/* ---------------------------------------------------------------- fuse search ---------------- */
+
+/* ORBmatcher::Fuse for a batch of PAIRS of resident keyframes: pair p is (keyframe pair_frame[p], the points point_first[p] ..
+ * point_first[p] + point_count[p] - 1 of d_points, the camera cameras[p]).  For every (pair, point) the pre-filter of ORBmatcher.cc:1042-1083
+ * and the search of :1085-1148, in ONE launch; nothing of the write-back (:1150-1170: Replace / AddObservation) is done here.
+ *
+ * Pre-filter (PARITY UNPINNED like the local map search above, whose arithmetic this is): float32, every operation rounded, nothing fused, except
+ *   p3Dc = Rcw * P + tcw      one gemm per row: ((R0 P0 + R1 P1) + R2 P2) + t in double, one rounding to float; p3Dc.z < 0.0f is out
+ *   invz = 1.0f / z           the reference writes `1/p3Dc.at<float>(2)`: a float division.  (float) (1.0 / (double) z) is the same value for
+ *                             every z: a quotient of two floats rounded to 53 bits and then to 24 is the correctly rounded float quotient
+ *   x = X * invz;  u = fx * x + cx;  v alike
+ *   KeyFrame::IsInImage: u >= min_x && u < max_x && v >= min_y && v < max_y; a projection that is not finite fails it (z == 0 included)
+ *   ur = u - mbf * invz       (AMOS_FUSE_LOCAL; 0 in AMOS_FUSE_SIM3)
+ *   PO = P - Ow;  dist3D = (float) sqrt(((double) PO0^2 + (double) PO1^2) + (double) PO2^2)
+ *   dist3D < 0.8f * min_distance || dist3D > 1.2f * max_distance is out
+ *   (((double) PO0 Pn0 + (double) PO1 Pn1) + (double) PO2 Pn2) < 0.5 * (double) dist3D is out: a comparison in double, no division
+ *   level = number of m in [0, n_levels) with max_distance / dist3D > scale_factors[m], at most n_levels - 1 (the table form of
+ *   MapPoint::PredictScale of the local map search: it differs from the logf form only for a ratio within rounding of a table entry)
+ * Search: radius th * scale_factors[level]; KeyFrame::GetFeaturesInArea (KeyFrame.cc:752-797: Frame's cell arithmetic, no level check) with
+ * |kp.x - u| < r && |kp.y - v| < r; levels level - 1 .. level; in AMOS_FUSE_LOCAL the chi-square gate in float32, unfused: a feature with
+ * u_right >= 0 is rejected when (double) (((ex ex + ey ey) + er er) * inv_level_sigma2[kpLevel]) > 7.8, any other when
+ * (double) ((ex ex + ey ey) * inv_level_sigma2[kpLevel]) > 5.99 (ex = u - kp.x, ey = v - kp.y, er = ur - u_right); the nearest descriptor by
+ * strict < in the order x-major cells, then y, then insertion; accepted when bestDist <= max_dist (TH_LOW for both reference callers).
+ * AMOS_FUSE_SIM3 is Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (:1179-1312): no chi-square gate; the caller passes the unscaled Rcw, tcw
+ * and Ow = -R^T t. */
+#define AMOS_FUSE_LOCAL 0
+#define AMOS_FUSE_SIM3 1
+typedef struct amos_fuse_camera {      /* per pair: 84 bytes */
+    float Rcw[9], tcw[3], Ow[3];       /* KeyFrame::GetRotation (row-major), GetTranslation, GetCameraCenter */
+    float fx, fy, cx, cy, mbf;
+    float th;
+} amos_fuse_camera;
+typedef struct amos_fuse_stats {       /* per pair: 8 bytes */
+    int32_t n_in_view;                 /* points that passed the pre-filter */
+    int32_t n_accepted;                /* points with an accepted feature */
+} amos_fuse_stats;
+struct amos_window_query;              /* include/amos_host_types.h */
+struct amos_frame_view;
+typedef struct amos_fuse_search {
+    const amos_keypoint *d_kps;        /* [frames][capacity]: mvKeysUn */
+    const uint8_t *d_desc;             /* [frames][capacity][32] */
+    const int32_t *d_counts;           /* [frames] */
+    const int32_t *d_cell_start;       /* [frames][64*48+1]       (amos_frame_grid_build_batch_device) */
+    const int32_t *d_items;            /* [frames][capacity] */
+    const float *d_u_right;            /* [frames][capacity] or NULL (monocular: every feature takes the 5.99 branch) */
+    const float *scale_factors;        /* host, n_levels entries */
+    const float *inv_level_sigma2;     /* host, n_levels entries; read in AMOS_FUSE_LOCAL */
+    const amos_map_point *d_points;    /* n_points; bit 0 of flags: skip (NULL or isBad()) */
+    const int32_t *pair_frame;         /* host, n_pairs: in [0, n_frames) */
+    const int32_t *point_first, *point_count; /* host, n_pairs: ranges of different pairs may coincide (one list against many keyframes) */
+    const int32_t *out_off;            /* host, n_pairs, ascending, out_off[p + 1] >= out_off[p] + point_count[p]: point i of pair p -> out_off[p] + i */
+    const amos_fuse_camera *cameras;   /* host, n_pairs */
+    const uint8_t *d_skip;             /* indexed like the outputs: 1 = skipped for this keyframe (IsInKeyFrame, spAlreadyFound); or NULL */
+    struct amos_window_query *d_query; /* out: u, v, ur, level (0 where the point is not in view), src = i, the point's descriptor */
+    uint8_t *d_in_view;                /* out: 1 where the point passed the pre-filter */
+    int32_t *d_best_idx;               /* out: the accepted feature, or -1 */
+    int32_t *d_best_dist;              /* out: the nearest candidate's distance, accepted or not; 256 where the window had none */
+    amos_fuse_stats *d_stats;          /* out, [n_pairs] */
+    int32_t n_frames, n_pairs, n_points, capacity, n_levels;
+    int32_t mode, max_dist;
+    float min_x, max_x, min_y, max_y;  /* KeyFrame::mnMinX .. mnMaxY */
+} amos_fuse_search;
+/* Asynchronous on the matcher's stream; every host array is consumed before the call returns.  capacity <= 65536.  AMOS_ERR_INVALID, with a
+ * text, for a NULL argument (inv_level_sigma2 in AMOS_FUSE_LOCAL), a pair_frame outside n_frames, a point range outside n_points, an out_off
+ * out of order, a capacity, n_levels or mode out of range or empty image bounds. */
+int amos_match_fuse_batch_device(amos_match *m, const amos_fuse_search *s);
+/* The host form for a C++ drop-in (amos-slam_amd/host/KeyFrameFuse.h): n_kfs keyframe views with the same image bounds, n_points points and
+ * n_pairs pairs from host arrays, synchronous: ONE upload (every keyframe and the point list staged once, Frame::PosInGrid on the way),
+ * AssignFeaturesToGrid for all keyframes, the launch, ONE download.  skip (or NULL), query, in_view, best_idx and best_dist hold n_out
+ * entries, indexed out_off[p] + i; entries no pair owns are left alone.  A keyframe without features and a pair without points are valid
+ * (no feature is accepted); n_pairs == 0 returns at once. */
+int amos_match_fuse(amos_match *m, const struct amos_frame_view *kfs, int n_kfs, const amos_map_point *points, int n_points, int n_pairs,
+                    const int32_t *pair_frame, const int32_t *point_first, const int32_t *point_count, const int32_t *out_off,
+                    const amos_fuse_camera *cameras, const uint8_t *skip, int n_out, const float *scale_factors, const float *inv_level_sigma2,
+                    int n_levels, int mode, int max_dist, struct amos_window_query *query, uint8_t *in_view, int32_t *best_idx, int32_t *best_dist,
+                    amos_fuse_stats *stats);
+
 /* ---------------------------------------------------------------- mask pre-processing (8f-4) - */
 
 /* The pre-processing chain of the mask pass on the device, from the raw BGR frame to the network input:
