@@ -55,6 +55,8 @@ PROTOTYPES = {
     "amos_orb_detect_batch_device": (_i, (_v, _v, _z, _z, _i, _i, _i)),
     "amos_orb_gate_batch_device": (_i, (_v, _v, _z, _z)),
     "amos_orb_gate_labels_batch_device": (_i, (_v, _v, _z, _z, _v, _z, _z, _v, _z, _i, _v, _z, _i, _v)),
+    "amos_orb_gate_mode": (_i, (_i,)),
+    "amos_orb_batch_removed": (_i, (_v, _i, _v, _i, _v)),
     "amos_orb_describe_batch_device": (_i, (_v,)),
     "amos_orb_extract_batch_device_color": (_i, (_v, _v, _z, _z, _i, _i, _i, _i, _i)),
     "amos_frame_rgbd_glue_batch_device": (_i, (_v, _v, _i, _f, _z, _z, _f, _f, _f, _f, _f, _v, _v, _v, _v)),
@@ -104,6 +106,8 @@ PROTOTYPES = {
     "amos_mask_pre_destroy": (None, (_v,)),
     "amos_mask_pre_stream": (_v, (_v,)),
     "amos_mask_preprocess_batch_device": (_i, (_v, _v, _i, _v)),
+    "amos_mask_pre_mode": (_i, (_i,)),
+    "amos_mask_pre_one_pass": (_i, (_v, _v)),
     "amos_orb_detect_color_with_mask_pre_batch_device": (_i, (_v, _v, _v, _z, _z, _i, _i, _i, _i, _i, _v)),
     "amos_mask_bias_act_device": (_i, (_v, _v, _v, _v, _z, _i, _i)),
     "amos_mask_bias_relu_maxpool_device": (_i, (_v, _v, _v, _v, _i, _i, _i, _i)),
@@ -425,6 +429,14 @@ class OrbExtractor(_Handle):
                                                         d_centers, centers_frame_stride, n_centers, d_rm, rm_frame_stride, n_rm, d_status),
                "amos_orb_gate_labels_batch_device")
 
+    def batch_removed(self, frame):
+        """The keypoints the last (batch) gate removed from `frame`, in the reference's order."""
+        total, n = C.c_int32(0), C.c_int(0)
+        _check(self.L.amos_orb_level_layout(self.h, None, None, C.byref(total)), "amos_orb_level_layout")
+        removed = np.zeros(total.value + 1, KP_DTYPE)
+        _check(self.L.amos_orb_batch_removed(self.h, frame, _p(removed), len(removed), C.byref(n)), "amos_orb_batch_removed")
+        return removed[:n.value].copy()
+
     def describe_batch_device(self):
         _check(self.L.amos_orb_describe_batch_device(self.h), "amos_orb_describe_batch_device")
 
@@ -560,7 +572,7 @@ class Slic(_Handle):
 
 
 class MaskPreprocessor(_Handle):
-    """amos_mask_pre_*: BGR frames -> the mask network's [n, 3, 550, 550] input tensor in three HIP kernels
+    """amos_mask_pre_*: BGR frames -> the mask network's [n, 3, 550, 550] input tensor in one HIP kernel (mask_pre_mode 0: three)
     (yolact.cc:220, 385-451; yolact_interface.py:862-866; utils/augmentations.py:616-657)."""
 
     _kind = "mask_pre"
@@ -571,6 +583,17 @@ class MaskPreprocessor(_Handle):
 
     def run(self, d_bgr, n_frames, d_out):
         _check(self.L.amos_mask_preprocess_batch_device(self.h, d_bgr, n_frames, d_out), "amos_mask_preprocess_batch_device")
+
+    def one_pass(self):
+        """(calls on this handle take the one-pass kernel under the current amos_mask_pre_mode, bytes of its source window the frame size needs)"""
+        need = C.c_int(0)
+        return bool(_check(self.L.amos_mask_pre_one_pass(self.h, C.byref(need)), "amos_mask_pre_one_pass")), need.value
+
+
+def mask_pre_mode(mode=-1):
+    """amos_mask_pre_mode: 1 = the pre-processing chain runs as one kernel where the frame size allows it (default), 0 = three kernels; returns the
+    previous mode."""
+    return int(lib().amos_mask_pre_mode(mode))
 
 
 def mask_bias_act(stream_ptr, y_ptr, bias_ptr, residual_ptr, n, channels, relu):
@@ -629,6 +652,11 @@ def mask_stem(stream_ptr, x_ptr, x_strides, packed_ptr, bias_ptr, y_ptr, batch, 
     through its element strides, y channels-last [batch][ph][pw][64] (device pointers)."""
     sb, sc, sy, sx = (int(v) for v in x_strides)
     _check(lib().amos_mask_stem_device(stream_ptr, x_ptr, sb, sc, sy, sx, packed_ptr, bias_ptr, y_ptr, batch, height, width), "amos_mask_stem_device")
+
+
+def orb_gate_mode(mode=-1):
+    """amos_orb_gate_mode: 1 = the batch gates close the masks on bit planes (default), 0 = on grey planes; returns the previous mode."""
+    return int(lib().amos_orb_gate_mode(mode))
 
 
 def mask_bilinear_x2_mode(mode=-1):

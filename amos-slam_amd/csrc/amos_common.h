@@ -188,7 +188,12 @@ struct OrbStereoView {
 };
 // AMOS_ERR_CAPACITY when sadScratchInts exceeds the handle's scratch
 int orb_stereo_view(amos_orb *h, size_t sadScratchInts, OrbStereoView *out);
-int mask_pre_stage_a(amos_mask_pre *p, MaskPreStageA *out);                              // tables and buffers of stage A
+// tables and buffers of stage A; withChain: mid is needed (the three-kernel chain's intermediates are made on first use), else it is NULL or stale
+int mask_pre_stage_a(amos_mask_pre *p, MaskPreStageA *out, bool withChain);
 int mask_pre_finish(amos_mask_pre *p, hipStream_t stream, int n_frames, float *d_out);  // stages B and C on `stream`
+bool mask_pre_one_pass(const amos_mask_pre *p);  // the handle's frame size and amos_mask_pre_mode take k_mask_pre_fused
+// the whole chain in one kernel on `stream`, from interleaved colour frames (bytes 0 .. 2 of `channels` per pixel)
+int mask_pre_run_one_pass(amos_mask_pre *p, hipStream_t stream, const uint8_t *d_color, size_t frame_stride, size_t row_stride, int channels,
+                          int n_frames, float *d_out);
 const char *w24_variant_tag();  // amos_winograd24.hip: " NAME" per timing-experiment switch compiled in, "" for the product build
 }  // namespace amos

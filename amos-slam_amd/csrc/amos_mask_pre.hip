@@ -1,6 +1,6 @@
 // amos_mask_pre.hip -- the mask pass's pre-processing chain on the device: from the raw BGR
-// frame to the network's input tensor in three small kernels, numerically what the reference does in three
-// places:
+// frame to the network's input tensor, numerically what the reference does in three places -- as one kernel that keeps
+// the two intermediate images in LDS (k_mask_pre_fused), or as three small kernels through HBM:
 //   A  yolact::evalImage (yolact.cc:220, 385-451): cv::resize(BGR u8 -> W480 x H640) [sic, swapped], u8 / 255.0
 //      as CHW float, and eval_image's "* 255" (yolact_interface.py:862-864)            -> float HWC 640 x 480
 //   B  eval_image's cv2.resize(float32, (640, 480)) (yolact_interface.py:865)          -> float HWC 480 x 640
@@ -11,7 +11,9 @@
 // PyTorch is not involved: the network consumes d_out directly.
 #include "amos_common.h"
 
+#include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <vector>
 
 namespace amos {
@@ -83,6 +85,163 @@ __global__ __launch_bounds__(256) void k_mask_pre_c(const float *__restrict__ ba
         const float bot = __fadd_rn(__fmul_rn(wl0, p10[c]), __fmul_rn(wl1, p11[c]));
         const float v = __fadd_rn(__fmul_rn(hl0, top), __fmul_rn(hl1, bot));
         o[(size_t)(2 - c) * kNetSize * kNetSize] = __fdiv_rn(__fsub_rn(v, mean[c]), stdv[c]);  // RGB plane order
+    }
+}
+
+
+// The three stages in ONE pass (amos_mask_pre_mode 1, the default): a work-group owns a kPreTile x kPreTile tile of network-input pixels and
+// walks the chain backwards through the tap tables to the windows it needs -- stage C's taps of the tile's first and last row / column
+// give the window of B, the B taps of that window's ends (dFltX / dFltY) the window of A, the A taps of its ends (dFixX / dFixY) the
+// source window; every table is non-decreasing in both taps (checked on the host), so an inner element's taps lie inside.  The source
+// window is staged in LDS, then A's window is computed into LDS once, B's from it, C from that: 0.29 GB per 64 frames (59 MB of frames in,
+// 232 MB out) instead of 1.23 GB through the two 236 MB intermediates.  Every value is made by k_mask_pre_a / _b / _c's operations in
+// their order: the same bits.
+// LDS: B's and A's windows do not depend on the frame size (30 x 39 and 41 x 31 pixels of three floats: 14.0 + 15.3 KB; B's lies over the
+// source window, which is dead by then); the source
+// window does -- 32 x 42 pixels (4 KB) at 640 x 480, 47 x 82 (11.7 KB) at 1280 x 720 -- and gets kPreSrcBytes.  RULE: a frame size takes
+// this kernel iff (most source rows of a tile) x pre_src_pitch(most source columns of a tile) is at most kPreSrcBytes (and the A / B
+// windows are within their arrays); otherwise -- strong downscaling: 70 x 368 = 25.8 KB at 1920 x 1080 -- the three-kernel chain runs.
+// The host evaluates the rule at create time over every tile with the kernel's own window arithmetic (pre_axis_window below).
+// grid = (ceil(550 / 32), ceil(550 / 32), frames), block = 256.
+constexpr int kPreTile = 32, kPreBRows = 30, kPreBCols = 39, kPreARows = 41, kPreACols = 31, kPreSrcBytes = 16 * 1024;
+
+__host__ __device__ inline int pre_src_pitch(int cols) { return (cols * 3 + 3) & ~3; }  // bytes of a staged source row: three per pixel, whole dwords
+
+struct PreTables { const FixTap *fixX, *fixY; const FltTap *fltX, *fltY; const float *lut; };
+
+// stage C's tap of output index o (k_mask_pre_c's expressions): first source index, 0 / 1 step to the second, weights
+__host__ __device__ inline void pre_c_tap(int o, float scale, int inN, int &i0, int &step, float &l0, float &l1)
+{
+#ifdef __HIP_DEVICE_COMPILE__
+    const float r = fmaxf(__fsub_rn(__fmul_rn(scale, __fadd_rn((float)o, 0.5f)), 0.5f), 0.f);
+    i0 = (int)r; step = i0 < inN - 1 ? 1 : 0;
+    l1 = __fsub_rn(r, (float)i0); l0 = __fsub_rn(1.f, l1);
+#else
+    volatile float a = (float)o + 0.5f, b = scale * a, c = b - 0.5f;  // (volatile: one rounding per operation on the host too)
+    const float r = c > 0.f ? c : 0.f;
+    i0 = (int)r; step = i0 < inN - 1 ? 1 : 0;
+    l1 = r - (float)i0; l0 = 1.f - l1;
+#endif
+}
+
+// The windows of one tile along one axis: output indices [o0, o1] -> B's [b0, b1] -> A's [m0, m1] -> source [s0, s1]
+struct PreAxisWindow { int b0, b1, m0, m1, s0, s1; };
+__host__ __device__ inline PreAxisWindow pre_axis_window(int o0, int o1, int backN, float scale, const FltTap *flt, const FixTap *fix)
+{
+    PreAxisWindow w;
+    int i, st;
+    float l0, l1;
+    pre_c_tap(o0, scale, backN, i, st, l0, l1);
+    w.b0 = i;
+    pre_c_tap(o1, scale, backN, i, st, l0, l1);
+    w.b1 = i + st;
+    w.m0 = flt[w.b0].s0; w.m1 = flt[w.b1].s1;
+    w.s0 = fix[w.m0].s0; w.s1 = fix[w.m1].s1;
+    return w;
+}
+
+__global__ __launch_bounds__(256) void k_mask_pre_fused(const uint8_t *__restrict__ src, size_t frameStride, size_t rowStride, int channels,
+                                                       const PreTables t, float *__restrict__ out)
+{
+    __shared__ __align__(16) uint8_t sSrc[kPreSrcBytes];
+    __shared__ float sA[kPreARows * kPreACols * 3];
+    __shared__ float sLut[256];
+    static_assert(kPreBRows * kPreBCols * 3 * sizeof(float) <= kPreSrcBytes, "B's window takes the source window's place");
+    float *sB = reinterpret_cast<float *>(sSrc);  // the source window is dead once A is made (the barrier after stage A): 32.7 KB, five groups per CU
+    const int tid = threadIdx.x, frame = blockIdx.z;
+    const int ox0 = blockIdx.x * kPreTile, oy0 = blockIdx.y * kPreTile;
+    const float sh = (float)kBackH / (float)kNetSize, sw = (float)kBackW / (float)kNetSize;
+    const PreAxisWindow wx = pre_axis_window(ox0, min(ox0 + kPreTile, kNetSize) - 1, kBackW, sw, t.fltX, t.fixX);
+    const PreAxisWindow wy = pre_axis_window(oy0, min(oy0 + kPreTile, kNetSize) - 1, kBackH, sh, t.fltY, t.fixY);
+    const int nSC = wx.s1 - wx.s0 + 1, nSR = wy.s1 - wy.s0 + 1, pitch = pre_src_pitch(nSC);
+    const int nAC = wx.m1 - wx.m0 + 1, nAR = wy.m1 - wy.m0 + 1, nBC = wx.b1 - wx.b0 + 1, nBR = wy.b1 - wy.b0 + 1;
+    // idx / n for the window loops: one multiplication (m = floor((2^32 - 1) / n) + 1 is exact while idx * n < 2^32; idx < 2^13, n < 2^12);
+    // n = 1 has no 32-bit m and is marked by 0
+    auto magic = [](int n) { return n > 1 ? 0xffffffffu / (unsigned)n + 1u : 0u; };
+    auto div = [](int idx, unsigned m) { return m ? (int)__umulhi((unsigned)idx, m) : idx; };
+    sLut[tid] = t.lut[tid];
+    const uint8_t *s0 = src + (size_t)frame * frameStride + (size_t)wy.s0 * rowStride + (size_t)wx.s0 * channels;
+    if (channels == 3) {  // a window row is one run of bytes: four at a time (the tail, which may end the allocation, byte by byte)
+        const int nb = nSC * 3, nd = pitch >> 2;
+        const unsigned m = magic(nd);
+        for (int idx = tid; idx < nSR * nd; idx += 256) {
+            const int r = div(idx, m), j = 4 * (idx - r * nd);
+            const uint8_t *g = s0 + (size_t)r * rowStride + j;
+            unsigned v = 0;
+            if (j + 4 <= nb) __builtin_memcpy(&v, g, 4);  // unaligned global_load_dword
+            else
+                for (int k = 0; j + k < nb; k++) v |= (unsigned)g[k] << (8 * k);
+            *reinterpret_cast<unsigned *>(sSrc + r * pitch + j) = v;
+        }
+    } else {  // four bytes per pixel: one load, the first three kept
+        const unsigned m = magic(nSC);
+        for (int idx = tid; idx < nSR * nSC; idx += 256) {
+            const int r = div(idx, m), c = idx - r * nSC;
+            unsigned v;
+            __builtin_memcpy(&v, s0 + (size_t)r * rowStride + (size_t)c * 4, 4);
+            uint8_t *d = sSrc + r * pitch + 3 * c;
+            d[0] = (uint8_t)v; d[1] = (uint8_t)(v >> 8); d[2] = (uint8_t)(v >> 16);
+        }
+    }
+    __syncthreads();
+    // Stages A, B and C keep one coordinate of a thread fixed over its loop, so that coordinate's taps, offsets and weights are made once:
+    // A: 32 lanes = the window's columns (at most kPreACols = 31), 8 rows per pass
+    static_assert(kPreACols <= 32 && kPreBRows <= 32 && kPreTile == 32, "the thread layouts below");
+    const int lo = tid & 31, hi = tid >> 5;
+    if (lo < nAC) {  // stage A, as k_mask_pre_a
+        const FixTap ax = t.fixX[wx.m0 + lo];
+        const int xa = 3 * (ax.s0 - wx.s0), xb = 3 * (ax.s1 - wx.s0);
+        for (int r = hi; r < nAR; r += 8) {
+            const FixTap ay = t.fixY[wy.m0 + r];
+            const uint8_t *r0 = sSrc + (ay.s0 - wy.s0) * pitch, *r1 = sSrc + (ay.s1 - wy.s0) * pitch;
+            float *o = sA + (r * nAC + lo) * 3;
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                const int h0 = r0[xa + k] * ax.a0 + r0[xb + k] * ax.a1;
+                const int h1 = r1[xa + k] * ax.a0 + r1[xb + k] * ax.a1;
+                const int v = (((ay.a0 * (h0 >> 4)) >> 16) + ((ay.a1 * (h1 >> 4)) >> 16) + 2) >> 2;
+                o[k] = sLut[v];
+            }
+        }
+    }
+    __syncthreads();
+    if (lo < nBR) {  // stage B, as k_mask_pre_b: 32 lanes = the window's rows (at most kPreBRows = 30), 8 columns per pass
+        const FltTap ay = t.fltY[wy.b0 + lo];
+        const float *r0 = sA + (ay.s0 - wy.m0) * nAC * 3, *r1 = sA + (ay.s1 - wy.m0) * nAC * 3;
+        for (int c = hi; c < nBC; c += 8) {
+            const FltTap ax = t.fltX[wx.b0 + c];
+            const int xa = 3 * (ax.s0 - wx.m0), xb = 3 * (ax.s1 - wx.m0);
+            float *o = sB + (lo * nBC + c) * 3;
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                const float h0 = __fadd_rn(__fmul_rn(r0[xa + k], ax.f0), __fmul_rn(r0[xb + k], ax.f1));
+                const float h1 = __fadd_rn(__fmul_rn(r1[xa + k], ax.f0), __fmul_rn(r1[xb + k], ax.f1));
+                o[k] = __fadd_rn(__fmul_rn(h0, ay.f0), __fmul_rn(h1, ay.f1));
+            }
+        }
+    }
+    __syncthreads();
+    const int ox = ox0 + lo;
+    if (ox < kNetSize) {  // stage C, as k_mask_pre_c: 32 lanes = the tile's columns, 8 rows per pass
+        const float mean[3] = {103.94f, 116.78f, 123.68f}, stdv[3] = {57.38f, 57.12f, 58.40f};  // BGR, data/config.py:28-29
+        int w1, w1p;
+        float wl0, wl1;
+        pre_c_tap(ox, sw, kBackW, w1, w1p, wl0, wl1);
+        const float *col = sB + (w1 - wx.b0) * 3;
+        for (int oy = oy0 + hi; oy < min(oy0 + kPreTile, kNetSize); oy += 8) {
+            int h1, h1p;
+            float hl0, hl1;
+            pre_c_tap(oy, sh, kBackH, h1, h1p, hl0, hl1);
+            const float *p00 = col + (h1 - wy.b0) * nBC * 3, *p01 = p00 + w1p * 3, *p10 = p00 + h1p * nBC * 3, *p11 = p10 + w1p * 3;
+            float *o = out + (size_t)frame * 3 * kNetSize * kNetSize + (size_t)oy * kNetSize + ox;
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                const float top = __fadd_rn(__fmul_rn(wl0, p00[k]), __fmul_rn(wl1, p01[k]));
+                const float bot = __fadd_rn(__fmul_rn(wl0, p10[k]), __fmul_rn(wl1, p11[k]));
+                const float v = __fadd_rn(__fmul_rn(hl0, top), __fmul_rn(hl1, bot));
+                o[(size_t)(2 - k) * kNetSize * kNetSize] = __fdiv_rn(__fsub_rn(v, mean[k]), stdv[k]);  // RGB plane order
+            }
+        }
     }
 }
 
@@ -310,9 +469,42 @@ struct amos_mask_pre : StreamHandle {
     int width = 0, height = 0, maxBatch = 0;
     FixTap *dFixX = nullptr, *dFixY = nullptr;
     FltTap *dFltX = nullptr, *dFltY = nullptr;
-    float *dLut = nullptr, *dMid = nullptr, *dBack = nullptr;
+    float *dLut = nullptr;
+    float *dMid = nullptr, *dBack = nullptr;  // the three-kernel chain's intermediates (236 MB each per 64 frames): made on its first use
     int *dFirstX = nullptr, *dFirstY = nullptr;  // inverse of the stage-A tap tables (fused import, amos_orb.hip)
+    bool onePassFits = false;  // the frame size's windows fit k_mask_pre_fused's LDS arrays (the rule stated at the kernel)
+    int srcWindowBytes = 0;    // the largest source window of a tile, rows x columns x 3
 };
+
+// amos_mask_pre_mode: 1 = one pass where the frame size allows it (default), 0 = always the three kernels; AMOS_MASK_PRE_FUSED=0 / 1 in
+// the environment is the initial value, read once.
+static int g_pre_fused = -1;  // -1: environment not read yet
+
+static int pre_fused_mode()
+{
+    if (g_pre_fused < 0) {
+        const char *env = getenv("AMOS_MASK_PRE_FUSED");
+        g_pre_fused = env && env[0] == '0' ? 0 : 1;
+    }
+    return g_pre_fused;
+}
+
+static int pre_chain_buffers(amos_mask_pre *p)
+{
+    if (p->dMid && p->dBack) return AMOS_OK;
+    AMOS_HIP_CHECK(hipSetDevice(p->device));
+    if (!p->dMid) AMOS_HIP_CHECK(hipMalloc((void **)&p->dMid, sizeof(float) * 3 * kMidW * kMidH * (size_t)p->maxBatch));
+    if (!p->dBack) AMOS_HIP_CHECK(hipMalloc((void **)&p->dBack, sizeof(float) * 3 * kBackW * kBackH * (size_t)p->maxBatch));
+    return AMOS_OK;
+}
+
+static void launch_pre_fused(amos_mask_pre *p, hipStream_t stream, const uint8_t *src, size_t frameStride, size_t rowStride, int channels, int n_frames,
+                             float *d_out)
+{
+    const PreTables t{p->dFixX, p->dFixY, p->dFltX, p->dFltY, p->dLut};
+    const int tiles = (kNetSize + kPreTile - 1) / kPreTile;
+    hipLaunchKernelGGL(k_mask_pre_fused, dim3(tiles, tiles, n_frames), dim3(256), 0, stream, src, frameStride, rowStride, channels, t, d_out);
+}
 
 // cv::resize INTER_LINEAR source index and fraction per destination index (double -> float as OpenCV does);
 // the horizontal pass clamps the fraction at both ends, the vertical pass only clips the indices.
@@ -337,10 +529,22 @@ static void axis_taps(int srcN, int dstN, bool clampFraction, std::vector<int> &
 static int round_even(float v) { return (int)std::nearbyintf(v); }
 
 namespace amos {
-int mask_pre_stage_a(amos_mask_pre *p, MaskPreStageA *out)
+int mask_pre_stage_a(amos_mask_pre *p, MaskPreStageA *out, bool withChain)
 {
     if (!p || !out) { set_error("mask pre-processing handle missing"); return AMOS_ERR_INVALID; }
+    if (withChain) {
+        const int rc = pre_chain_buffers(p);
+        if (rc != AMOS_OK) return rc;
+    }
     *out = MaskPreStageA{p->dFixX, p->dFixY, p->dFirstX, p->dFirstY, p->dLut, p->dMid, p->width, p->height, p->maxBatch};
+    return AMOS_OK;
+}
+bool mask_pre_one_pass(const amos_mask_pre *p) { return p && p->onePassFits && pre_fused_mode() == 1; }
+int mask_pre_run_one_pass(amos_mask_pre *p, hipStream_t stream, const uint8_t *d_color, size_t frame_stride, size_t row_stride, int channels, int n_frames,
+                          float *d_out)
+{
+    launch_pre_fused(p, stream, d_color, frame_stride, row_stride, channels, n_frames, d_out);
+    AMOS_HIP_CHECK(hipGetLastError());
     return AMOS_OK;
 }
 int mask_pre_finish(amos_mask_pre *p, hipStream_t stream, int n_frames, float *d_out)
@@ -363,9 +567,12 @@ int amos_mask_pre_create(int device, void *stream, int width, int height, int ma
     if (rc != AMOS_OK) { delete p; return rc; }
     std::vector<int> s0, s1;
     std::vector<float> f;
+    std::vector<FixTap> hFix[2];  // host copies, x then y: the one-pass kernel's windows are worked out from them below
+    std::vector<FltTap> hFlt[2];
     auto fix = [&](int srcN, int dstN, bool clamp, FixTap **dst, int **first) -> hipError_t {
         axis_taps(srcN, dstN, clamp, s0, s1, f);
-        std::vector<FixTap> t(dstN);
+        std::vector<FixTap> &t = hFix[clamp ? 0 : 1];
+        t.resize(dstN);
         for (int d = 0; d < dstN; d++) t[d] = FixTap{s0[d], s1[d], round_even((1.f - f[d]) * 2048.f), round_even(f[d] * 2048.f)};
         // first tap indices are non-decreasing: first[X] = the first destination index whose first tap is >= X
         std::vector<int> inv(srcN + 1);
@@ -381,7 +588,8 @@ int amos_mask_pre_create(int device, void *stream, int width, int height, int ma
     };
     auto flt = [&](int srcN, int dstN, bool clamp, FltTap **dst) -> hipError_t {
         axis_taps(srcN, dstN, clamp, s0, s1, f);
-        std::vector<FltTap> t(dstN);
+        std::vector<FltTap> &t = hFlt[clamp ? 0 : 1];
+        t.resize(dstN);
         for (int d = 0; d < dstN; d++) t[d] = FltTap{s0[d], s1[d], 1.0f - f[d], f[d]};
         hipError_t e = hipMalloc((void **)dst, sizeof(FltTap) * dstN);
         if (e != hipSuccess) return e;
@@ -395,12 +603,29 @@ int amos_mask_pre_create(int device, void *stream, int width, int height, int ma
     if (e == hipSuccess) e = flt(kMidH, kBackH, false, &p->dFltY);
     if (e == hipSuccess) e = hipMalloc((void **)&p->dLut, sizeof(lut));
     if (e == hipSuccess) e = hipMemcpy(p->dLut, lut, sizeof(lut), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->dMid, sizeof(float) * 3 * kMidW * kMidH * (size_t)max_batch);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->dBack, sizeof(float) * 3 * kBackW * kBackH * (size_t)max_batch);
     if (e != hipSuccess) {
         set_error("amos_mask_pre_create: %s", hipGetErrorString(e));
         amos_mask_pre_destroy(p);
         return AMOS_ERR_DEVICE;
+    }
+    {   // k_mask_pre_fused's rule for this frame size: tables non-decreasing, every tile's windows inside the LDS arrays
+        bool fits = true;
+        auto rising = [&](auto &t) {
+            for (size_t d = 1; d < t.size(); d++) fits = fits && t[d].s0 >= t[d - 1].s0 && t[d].s1 >= t[d - 1].s1 && t[d].s1 >= t[d].s0;
+        };
+        rising(hFix[0]); rising(hFix[1]); rising(hFlt[0]); rising(hFlt[1]);
+        const float sh = (float)kBackH / (float)kNetSize, sw = (float)kBackW / (float)kNetSize;
+        int srcRows = 0, srcCols = 0;
+        for (int o0 = 0; fits && o0 < kNetSize; o0 += kPreTile) {
+            const int o1 = std::min(o0 + kPreTile, kNetSize) - 1;
+            const PreAxisWindow wx = pre_axis_window(o0, o1, kBackW, sw, hFlt[0].data(), hFix[0].data());
+            const PreAxisWindow wy = pre_axis_window(o0, o1, kBackH, sh, hFlt[1].data(), hFix[1].data());
+            fits = wx.b1 - wx.b0 < kPreBCols && wy.b1 - wy.b0 < kPreBRows && wx.m1 - wx.m0 < kPreACols && wy.m1 - wy.m0 < kPreARows;
+            srcCols = std::max(srcCols, wx.s1 - wx.s0 + 1);
+            srcRows = std::max(srcRows, wy.s1 - wy.s0 + 1);
+        }
+        p->srcWindowBytes = srcRows * pre_src_pitch(srcCols);  // (most rows and most columns: an upper bound of every tile's product)
+        p->onePassFits = fits && p->srcWindowBytes <= kPreSrcBytes;
     }
     *out = p;
     return AMOS_OK;
@@ -417,11 +642,29 @@ void amos_mask_pre_destroy(amos_mask_pre *p)
 
 void *amos_mask_pre_stream(amos_mask_pre *p) { return p ? (void *)p->stream : nullptr; }
 
+int amos_mask_pre_mode(int mode)
+{
+    const int before = pre_fused_mode();
+    if (mode == 0 || mode == 1) g_pre_fused = mode;
+    return before;
+}
+
+int amos_mask_pre_one_pass(const amos_mask_pre *p, int *source_window_bytes)
+{
+    if (!p) { set_error("amos_mask_pre_one_pass: invalid argument"); return AMOS_ERR_INVALID; }
+    if (source_window_bytes) *source_window_bytes = p->srcWindowBytes;
+    return mask_pre_one_pass(p) ? 1 : 0;
+}
+
 int amos_mask_preprocess_batch_device(amos_mask_pre *p, const uint8_t *d_bgr, int n_frames, float *d_out)
 {
     if (!p || !d_bgr || !d_out || n_frames < 1) { set_error("amos_mask_preprocess_batch_device: invalid argument"); return AMOS_ERR_INVALID; }
     if (n_frames > p->maxBatch) { set_error("amos_mask_preprocess_batch_device: %d frames, handle made for %d", n_frames, p->maxBatch); return AMOS_ERR_CAPACITY; }
     AMOS_HIP_CHECK(hipSetDevice(p->device));
+    if (mask_pre_one_pass(p))
+        return mask_pre_run_one_pass(p, p->stream, d_bgr, (size_t)p->width * p->height * 3, (size_t)p->width * 3, 3, n_frames, d_out);
+    const int rc = pre_chain_buffers(p);
+    if (rc != AMOS_OK) return rc;
     hipLaunchKernelGGL(k_mask_pre_a, dim3((kMidW * kMidH + 255) / 256, n_frames), dim3(256), 0, p->stream, d_bgr, p->width, p->height, p->dFixX,
                        p->dFixY, p->dLut, p->dMid);
     hipLaunchKernelGGL(k_mask_pre_b, dim3((kBackW * kBackH + 255) / 256, n_frames), dim3(256), 0, p->stream, p->dMid, p->dFltX, p->dFltY, p->dBack);

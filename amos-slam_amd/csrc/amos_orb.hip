@@ -82,6 +82,8 @@ struct amos_orb : StreamHandle {
     int *dStereoSad = nullptr;  // [B][kpCap] accepted SADs of a stereo match whose caller passes no d_sad
     float *dStereoOut = nullptr;  // [2][kpCap] uRight and depth of amos_frame_stereo_match (host form)
     uint8_t *dMask = nullptr, *dMaskTmp = nullptr, *dMaskClosed = nullptr;
+    unsigned long long *dMaskBits = nullptr, *dMaskBitsDil = nullptr;  // [B][maxH][maskWords] bit planes of the batch gates: packed, dilated
+    int maskWords = 0;  // 64-bit words per bit-plane row at maxW
     uint8_t *hStage = nullptr;  // pinned host staging for fetch_frame: count, one frame's keypoints and descriptors
     uint8_t *hPyrStage = nullptr;  // pinned host staging for one frame's pyramid (level images to host Mats), made on first use
     double *dLabels = nullptr;
@@ -92,6 +94,7 @@ struct amos_orb : StreamHandle {
     std::vector<hipEvent_t> events;  // [maxRecords][kTimingEvents]
     int maxRecords = 0, nRecords = 0;
     bool detected = false, described = false, gated = false;
+    bool gatedBits = false;  // the last gate ran on bit planes: no grey closed plane exists
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -373,7 +376,7 @@ static int set_geometry(amos_orb *h, int W, int Hh)
     AMOS_HIP_CHECK(hipStreamSynchronize(h->stream));  // host vectors above are pageable and reused
     h->curW = W;
     h->curH = Hh;
-    h->detected = h->described = h->gated = false;
+    h->detected = h->described = h->gated = h->gatedBits = false;
     return AMOS_OK;
 }
 
@@ -436,7 +439,7 @@ static int launch_detect(amos_orb *h, const uint8_t *dSrc, size_t frameStride, s
     AMOS_HIP_CHECK(hipGetLastError());
     h->nFrames = nFrames;
     h->detected = true;
-    h->described = h->gated = false;
+    h->described = h->gated = h->gatedBits = false;
     return AMOS_OK;
 }
 
@@ -628,6 +631,7 @@ int amos_orb_create(const amos_orb_params *params, int max_width, int max_height
     const size_t slack = 4096;  // tile loads may run a few bytes past the last row of the last plane
     h->inputPitch = align_up(max_width, 128);
     h->maskPitch = align_up(max_width, 128);
+    h->maskWords = (max_width + 63) / 64;
 #define ALLOC(ptr, count) do { rc = dev_alloc(&(ptr), (count)); if (rc != AMOS_OK) { amos_orb_destroy(h); return rc; } } while (0)
     ALLOC(h->dGeom, 1);
     ALLOC(h->dCells, h->capCells);
@@ -653,6 +657,8 @@ int amos_orb_create(const amos_orb_params *params, int max_width, int max_height
     ALLOC(h->dMask, (size_t)h->maskPitch * max_height);
     ALLOC(h->dMaskTmp, B * (size_t)h->maskPitch * max_height);
     ALLOC(h->dMaskClosed, B * (size_t)h->maskPitch * max_height);
+    ALLOC(h->dMaskBits, B * (size_t)h->maskWords * max_height);
+    ALLOC(h->dMaskBitsDil, B * (size_t)h->maskWords * max_height);
     ALLOC(h->dLabels, (size_t)max_width * max_height);
     ALLOC(h->dNRemoved, B);
     ALLOC(h->dErr, 1);
@@ -708,7 +714,7 @@ void amos_orb_destroy(amos_orb *h)
     h->close();
     void *ptrs[] = {h->dGeom, h->dCells, h->dTaps, h->dPyr, h->dBlur, h->dInput, h->dSlotCount, h->dSlots, h->dPts,
                     h->dNodeOf, h->dQuadOf, h->dCandCount, h->dLvCount, h->dOutCount, h->dLvKps, h->dOutKps, h->dOutDesc,
-                    h->dRemoved, h->dScratchKps, h->dMask, h->dMaskTmp, h->dMaskClosed, h->dLabels, h->dCenterIds, h->dRm,
+                    h->dRemoved, h->dScratchKps, h->dMask, h->dMaskTmp, h->dMaskClosed, h->dMaskBits, h->dMaskBitsDil, h->dLabels, h->dCenterIds, h->dRm,
                     h->dNRemoved, h->dErr, h->dStereoSad, h->dStereoOut};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (h->hStage) (void)hipHostFree(h->hStage);
@@ -880,7 +886,7 @@ int amos_orb_gate(amos_orb *h, const uint8_t *mask, size_t mask_stride, const do
     dim3 grid((g.W + kMorphTileW - 1) / kMorphTileW, (g.H + kMorphTileH - 1) / kMorphTileH);
     hipLaunchKernelGGL(k_morph31<true>, grid, dim3(256), 0, h->stream, h->dMask, (size_t)0, h->maskPitch, h->dMaskTmp, (size_t)0, h->maskPitch, g.W, g.H);
     hipLaunchKernelGGL(k_morph31<false>, grid, dim3(256), 0, h->stream, h->dMaskTmp, (size_t)0, h->maskPitch, h->dMaskClosed, (size_t)0, h->maskPitch, g.W, g.H);
-    hipLaunchKernelGGL(k_gate, dim3(1), dim3(256), 0, h->stream, h->dGeom, h->dLvKps, h->dLvCount, h->dMaskClosed, (size_t)0, h->maskPitch,
+    hipLaunchKernelGGL(k_gate<false>, dim3(1), dim3(256), 0, h->stream, h->dGeom, h->dLvKps, h->dLvCount, h->dMaskClosed, (size_t)0, h->maskPitch,
                        labels ? h->dLabels : nullptr, g.W, h->dCenterIds, n_centers, h->dRm, n_rm, h->dRemoved, h->dNRemoved, h->dErr);
     AMOS_HIP_CHECK(hipGetLastError());
     int nrem = 0, err = 0;
@@ -888,6 +894,7 @@ int amos_orb_gate(amos_orb *h, const uint8_t *mask, size_t mask_stride, const do
     AMOS_HIP_CHECK(hipMemcpyAsync(&err, h->dErr, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     AMOS_HIP_CHECK(hipStreamSynchronize(h->stream));
     h->gated = true;
+    h->gatedBits = false;
     if (err) { set_error("amos_orb_gate: %s", (err & 1) ? "keypoint outside the mask" : "label / cluster id out of range"); return AMOS_ERR_INVALID; }
     *n_removed = nrem;
     if (removed) {
@@ -903,6 +910,7 @@ int amos_orb_gate(amos_orb *h, const uint8_t *mask, size_t mask_stride, const do
 int amos_orb_closed_mask(amos_orb *h, uint8_t *dst, size_t dst_stride)
 {
     if (!h || !dst || !h->gated) { set_error("amos_orb_closed_mask: no gate has run"); return AMOS_ERR_STATE; }
+    if (h->gatedBits) { set_error("amos_orb_closed_mask: the last gate was a batch gate on bit planes (amos_orb_gate_mode 1): there is no grey closed mask"); return AMOS_ERR_STATE; }
     AMOS_HIP_CHECK(hipMemcpy2DAsync(dst, dst_stride, h->dMaskClosed, h->maskPitch, h->geom.W, h->geom.H, hipMemcpyDeviceToHost, h->stream));
     AMOS_HIP_CHECK(hipStreamSynchronize(h->stream));
     return AMOS_OK;
@@ -1019,6 +1027,48 @@ int amos_orb_detect_batch_device(amos_orb *h, const uint8_t *d_gray, size_t fram
     return launch_detect(h, d_gray, frame_stride, row_stride, n_frames);
 }
 
+// The closing of the batch gates, on the handle's stream.  Bit planes (amos_orb_gate_mode 1, the default): pack the masks' non-zero sets,
+// dilate them; k_gate<true> makes the erosion at each keypoint.  Grey planes (mode 0): k_morph31 twice, as amos_orb_gate.
+static int g_gate_bits = -1;  // -1: environment not read yet
+
+static int gate_bits_mode()
+{
+    if (g_gate_bits < 0) {
+        const char *env = getenv("AMOS_GATE_BITS");
+        g_gate_bits = env && env[0] == '0' ? 0 : 1;
+    }
+    return g_gate_bits;
+}
+
+int amos_orb_gate_mode(int mode)
+{
+    const int before = gate_bits_mode();
+    if (mode == 0 || mode == 1) g_gate_bits = mode;
+    return before;
+}
+
+static bool launch_batch_closing(amos_orb *h, const uint8_t *d_masks, size_t mask_frame_stride, size_t mask_row_stride)
+{
+    const Geom &g = h->geom;
+    const bool bits = gate_bits_mode() == 1;
+    if (bits) {
+        const int words = (g.W + 63) / 64;  // <= h->maskWords: set_geometry holds the frame to the handle's maximum
+        const size_t bitsStride = (size_t)h->maskWords * h->maxH;
+        hipLaunchKernelGGL(k_bits_pack, dim3((words + 3) / 4, (g.H + kBitsPackRows - 1) / kBitsPackRows, h->nFrames), dim3(256), 0, h->stream, d_masks,
+                           mask_frame_stride, mask_row_stride, h->dMaskBits, bitsStride, words, g.W, g.H);
+        hipLaunchKernelGGL(k_bits_dilate, dim3((g.H * words + 255) / 256, 1, h->nFrames), dim3(256), 0, h->stream, h->dMaskBits, h->dMaskBitsDil,
+                           bitsStride, words, g.W, g.H);
+    } else {
+        const size_t planeStride = (size_t)h->maskPitch * h->maxH;
+        dim3 grid((g.W + kMorphTileW - 1) / kMorphTileW, (g.H + kMorphTileH - 1) / kMorphTileH, h->nFrames);
+        hipLaunchKernelGGL(k_morph31<true>, grid, dim3(256), 0, h->stream, d_masks, mask_frame_stride, (int)mask_row_stride, h->dMaskTmp, planeStride,
+                           h->maskPitch, g.W, g.H);
+        hipLaunchKernelGGL(k_morph31<false>, grid, dim3(256), 0, h->stream, h->dMaskTmp, planeStride, h->maskPitch, h->dMaskClosed, planeStride,
+                           h->maskPitch, g.W, g.H);
+    }
+    return bits;
+}
+
 int amos_orb_gate_batch_device(amos_orb *h, const uint8_t *d_masks, size_t mask_frame_stride, size_t mask_row_stride)
 {
     if (!h || !d_masks || mask_row_stride < 1) { set_error("amos_orb_gate_batch_device: invalid argument"); return AMOS_ERR_INVALID; }
@@ -1026,16 +1076,18 @@ int amos_orb_gate_batch_device(amos_orb *h, const uint8_t *d_masks, size_t mask_
     AMOS_HIP_CHECK(hipSetDevice(h->device));
     const Geom &g = h->geom;
     const size_t planeStride = (size_t)h->maskPitch * h->maxH;
-    dim3 grid((g.W + kMorphTileW - 1) / kMorphTileW, (g.H + kMorphTileH - 1) / kMorphTileH, h->nFrames);
     AMOS_HIP_CHECK(hipMemsetAsync(h->dErr, 0, sizeof(int), h->stream));
-    hipLaunchKernelGGL(k_morph31<true>, grid, dim3(256), 0, h->stream, d_masks, mask_frame_stride, (int)mask_row_stride, h->dMaskTmp, planeStride,
-                       h->maskPitch, g.W, g.H);
-    hipLaunchKernelGGL(k_morph31<false>, grid, dim3(256), 0, h->stream, h->dMaskTmp, planeStride, h->maskPitch, h->dMaskClosed, planeStride,
-                       h->maskPitch, g.W, g.H);
-    hipLaunchKernelGGL(k_gate, dim3(h->nFrames), dim3(256), 0, h->stream, h->dGeom, h->dLvKps, h->dLvCount, h->dMaskClosed, planeStride, h->maskPitch,
-                       (const double *)nullptr, 0, (const int *)nullptr, 0, (const int *)nullptr, 0, h->dRemoved, h->dNRemoved, h->dErr);
+    const bool bits = launch_batch_closing(h, d_masks, mask_frame_stride, mask_row_stride);
+    if (bits)
+        hipLaunchKernelGGL(k_gate<true>, dim3(h->nFrames), dim3(256), 0, h->stream, h->dGeom, h->dLvKps, h->dLvCount, (const uint8_t *)nullptr, (size_t)0, 0,
+                           (const double *)nullptr, 0, (const int *)nullptr, 0, (const int *)nullptr, 0, h->dRemoved, h->dNRemoved, h->dErr,
+                           GateLabelStrides(), h->dMaskBitsDil, (size_t)h->maskWords * h->maxH, (g.W + 63) / 64);
+    else
+        hipLaunchKernelGGL(k_gate<false>, dim3(h->nFrames), dim3(256), 0, h->stream, h->dGeom, h->dLvKps, h->dLvCount, h->dMaskClosed, planeStride,
+                           h->maskPitch, (const double *)nullptr, 0, (const int *)nullptr, 0, (const int *)nullptr, 0, h->dRemoved, h->dNRemoved, h->dErr);
     AMOS_HIP_CHECK(hipGetLastError());
     h->gated = true;
+    h->gatedBits = bits;
     return AMOS_OK;
 }
 
@@ -1053,12 +1105,8 @@ int amos_orb_gate_labels_batch_device(amos_orb *h, const uint8_t *d_masks, size_
     if (label_row_stride < (size_t)g.W) { set_error("amos_orb_gate_labels_batch_device: label rows shorter than the frame"); return AMOS_ERR_INVALID; }
     AMOS_HIP_CHECK(hipSetDevice(h->device));
     const size_t planeStride = (size_t)h->maskPitch * h->maxH;
-    dim3 grid((g.W + kMorphTileW - 1) / kMorphTileW, (g.H + kMorphTileH - 1) / kMorphTileH, h->nFrames);
     AMOS_HIP_CHECK(hipMemsetAsync(d_status, 0, sizeof(int32_t) * h->nFrames, h->stream));
-    hipLaunchKernelGGL(k_morph31<true>, grid, dim3(256), 0, h->stream, d_masks, mask_frame_stride, (int)mask_row_stride, h->dMaskTmp, planeStride,
-                       h->maskPitch, g.W, g.H);
-    hipLaunchKernelGGL(k_morph31<false>, grid, dim3(256), 0, h->stream, h->dMaskTmp, planeStride, h->maskPitch, h->dMaskClosed, planeStride,
-                       h->maskPitch, g.W, g.H);
+    const bool bits = launch_batch_closing(h, d_masks, mask_frame_stride, mask_row_stride);
     GateLabelStrides ls;
     constexpr int kRecInts = (int)(sizeof(amos_slic_center) / sizeof(int32_t));
     ls.labelFrame = label_frame_stride;
@@ -1067,10 +1115,36 @@ int amos_orb_gate_labels_batch_device(amos_orb *h, const uint8_t *d_masks, size_
     ls.errFrame = 1;
     ls.centerStride = kRecInts;
     const int *ids = (const int *)d_centers + offsetof(amos_slic_center, id) / sizeof(int32_t);
-    hipLaunchKernelGGL(k_gate, dim3(h->nFrames), dim3(256), 0, h->stream, h->dGeom, h->dLvKps, h->dLvCount, h->dMaskClosed, planeStride, h->maskPitch,
-                       d_labels, (int)label_row_stride, ids, n_centers, (const int *)d_rm, n_rm, h->dRemoved, h->dNRemoved, (int *)d_status, ls);
+    if (bits)
+        hipLaunchKernelGGL(k_gate<true>, dim3(h->nFrames), dim3(256), 0, h->stream, h->dGeom, h->dLvKps, h->dLvCount, (const uint8_t *)nullptr, (size_t)0, 0,
+                           d_labels, (int)label_row_stride, ids, n_centers, (const int *)d_rm, n_rm, h->dRemoved, h->dNRemoved, (int *)d_status, ls,
+                           h->dMaskBitsDil, (size_t)h->maskWords * h->maxH, (g.W + 63) / 64);
+    else
+        hipLaunchKernelGGL(k_gate<false>, dim3(h->nFrames), dim3(256), 0, h->stream, h->dGeom, h->dLvKps, h->dLvCount, h->dMaskClosed, planeStride,
+                           h->maskPitch, d_labels, (int)label_row_stride, ids, n_centers, (const int *)d_rm, n_rm, h->dRemoved, h->dNRemoved,
+                           (int *)d_status, ls);
     AMOS_HIP_CHECK(hipGetLastError());
     h->gated = true;
+    h->gatedBits = bits;
+    return AMOS_OK;
+}
+
+int amos_orb_batch_removed(amos_orb *h, int frame, amos_keypoint *removed, int cap, int *n_removed)
+{
+    if (!h || !n_removed || frame < 0 || frame >= h->nFrames) { set_error("amos_orb_batch_removed: invalid argument"); return AMOS_ERR_INVALID; }
+    if (!h->gated) { set_error("amos_orb_batch_removed: no gate has run"); return AMOS_ERR_STATE; }
+    AMOS_HIP_CHECK(hipSetDevice(h->device));
+    int n = 0;
+    AMOS_HIP_CHECK(hipMemcpyAsync(&n, h->dNRemoved + frame, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    AMOS_HIP_CHECK(hipStreamSynchronize(h->stream));
+    *n_removed = n;
+    if (removed) {
+        if (n > cap) { set_error("%d keypoints removed, caller capacity %d", n, cap); return AMOS_ERR_CAPACITY; }
+        if (n > 0) {
+            AMOS_HIP_CHECK(hipMemcpyAsync(removed, h->dRemoved + (size_t)frame * h->geom.kpLevelTotal, sizeof(amos_keypoint) * n, hipMemcpyDeviceToHost, h->stream));
+            AMOS_HIP_CHECK(hipStreamSynchronize(h->stream));
+        }
+    }
     return AMOS_OK;
 }
 
@@ -1106,8 +1180,11 @@ int amos_orb_detect_color_with_mask_pre_batch_device(amos_orb *h, amos_mask_pre 
         return AMOS_ERR_INVALID;
     }
     if (n_frames > h->maxB) { set_error("batch of %d frames exceeds the handle's max_batch %d", n_frames, h->maxB); return AMOS_ERR_CAPACITY; }
+    // One pass (amos_mask_pre_mode 1 and a frame size it takes): the plain colour import, then k_mask_pre_fused reads the colour frames
+    // itself -- a second read of 59 MB per 64 frames against the 236 MB intermediate that k_import_color_mask writes and stage B reads.
+    const bool onePass = mask_pre_one_pass(pre);
     MaskPreStageA a;
-    int rc = mask_pre_stage_a(pre, &a);
+    int rc = mask_pre_stage_a(pre, &a, !onePass);
     if (rc != AMOS_OK) return rc;
     if (a.width != width || a.height != height) { set_error("mask pre-processing handle made for %dx%d frames, got %dx%d", a.width, a.height, width, height); return AMOS_ERR_INVALID; }
     if (n_frames > a.maxBatch) { set_error("mask pre-processing handle made for %d frames, got %d", a.maxBatch, n_frames); return AMOS_ERR_CAPACITY; }
@@ -1115,8 +1192,9 @@ int amos_orb_detect_color_with_mask_pre_batch_device(amos_orb *h, amos_mask_pre 
     AMOS_HIP_CHECK(hipSetDevice(h->device));
     rc = set_geometry(h, width, height);
     if (rc != AMOS_OK) return rc;
-    rc = launch_detect(h, d_color, frame_stride, row_stride, n_frames, channels, rgb_order != 0, &a);
+    rc = launch_detect(h, d_color, frame_stride, row_stride, n_frames, channels, rgb_order != 0, onePass ? nullptr : &a);
     if (rc != AMOS_OK) return rc;
+    if (onePass) return mask_pre_run_one_pass(pre, h->stream, d_color, frame_stride, row_stride, channels, n_frames, d_net_input);
     return mask_pre_finish(pre, h->stream, n_frames, d_net_input);  // stages B and C follow on the same stream
 }
 

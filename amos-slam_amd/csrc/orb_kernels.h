@@ -1633,6 +1633,98 @@ __global__ __launch_bounds__(256) void k_morph31(const uint8_t *__restrict__ src
     }
 }
 
+// ---- the same closing on bit planes, for the batch gates.  k_gate asks one thing of the closed mask: closed[iy][ix] != 0.  A maximum
+// over a window is non-zero iff some element is, a minimum iff all are, so the non-zero set of the grey closing is the binary closing of
+// the non-zero set of the mask with the same border rules (outside the image: 0 for the dilation, non-zero for the erosion).  A plane is
+// [frame][row][words] 64-bit words, bit b of word k = pixel 64 k + b; bits at x >= W are 0 in the packed and the dilated plane.
+//
+// k_bits_pack: grid = (ceil(words / 4), ceil(h / kBitsPackRows), frames), block = 256; a wave makes one word of kBitsPackRows rows, one
+// ballot per row.
+constexpr int kBitsPackRows = 8;
+
+__global__ __launch_bounds__(256) void k_bits_pack(const uint8_t *__restrict__ src, size_t srcFrameStride, size_t srcStride,
+                                                  unsigned long long *__restrict__ dst, size_t dstFrameStride, int words, int w, int h)
+{
+    const int lane = threadIdx.x & 63, word = blockIdx.x * 4 + (threadIdx.x >> 6), y0 = blockIdx.y * kBitsPackRows;
+    if (word >= words) return;  // wave-uniform
+    const int x = word * 64 + lane;
+    src += (size_t)blockIdx.z * srcFrameStride;
+    unsigned long long mine = 0;
+#pragma unroll
+    for (int r = 0; r < kBitsPackRows; r++) {
+        const int y = y0 + r;
+        const int v = (x < w && y < h) ? src[(size_t)y * srcStride + x] : 0;
+        const unsigned long long b = __ballot(v != 0);
+        if (lane == r) mine = b;
+    }
+    if (lane < kBitsPackRows && y0 + lane < h) dst[(size_t)blockIdx.z * dstFrameStride + (size_t)(y0 + lane) * words + word] = mine;
+}
+
+// k_bits_dilate: one thread per output word.  The element rows of one half-width r dilate the OR of their source rows (H_r(a) | H_r(b) =
+// H_r(a | b)), and the widths are nested, so the rows are taken by |dy| = 0 .. 15 (widest first) into ONE accumulator that is widened by
+// the difference of two consecutive half-widths in between: a row of half-width r is widened by r bits in all (13 shift-and-OR steps
+// per word instead of 31 windows).  The accumulator is the word with 32 bits of each neighbour (the reach is 15); what the steps shift in
+// from beyond those 128 bits never gets closer than 17 bits to the word.  Intermediate bits at x >= W may be set and widen back into
+// the image: a bit they reach is within the full half-width of the source bit they came from, so the result is the same.
+// grid = (ceil(h * words / 256), 1, frames), block = 256.
+__global__ __launch_bounds__(256) void k_bits_dilate(const unsigned long long *__restrict__ src, unsigned long long *__restrict__ dst,
+                                                    size_t frameStride, int words, int w, int h)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= h * words) return;
+    const int y = t / words, k = t - y * words;
+    src += (size_t)blockIdx.z * frameStride;
+    unsigned long long lo = 0, hi = 0;  // bits 0 .. 31 of lo: the left neighbour's top half; bits 32 .. 63 of hi: the right neighbour's low half
+    auto take = [&](int yy) {
+        if (yy < 0 || yy >= h) return;  // rows outside the image hold 0
+        const unsigned long long *row = src + (size_t)yy * words;
+        const unsigned long long c = row[k], l = k > 0 ? row[k - 1] : 0ull, r = k < words - 1 ? row[k + 1] : 0ull;
+        lo |= (l >> 32) | (c << 32);
+        hi |= (c >> 32) | (r << 32);
+    };
+    auto widen = [&](int d) {  // by d bits to either side: v | v << s | v >> s widens a set that is already widened by r without gaps while s <= 2 r + 1
+        for (int r = 0; r < d;) {
+            const int s = min(d - r, 2 * r + 1);
+            const unsigned long long ll = lo << s, lh = (hi << s) | (lo >> (64 - s)), rl = (lo >> s) | (hi << (64 - s)), rh = hi >> s;
+            lo |= ll | rl;
+            hi |= lh | rh;
+            r += s;
+        }
+    };
+#pragma unroll
+    for (int a = 0; a <= 15; a++) {
+        if (a > 0 && kMorphDx[a] != kMorphDx[a - 1]) widen(kMorphDx[a - 1] - kMorphDx[a]);
+        take(y - a);
+        if (a > 0) take(y + a);
+    }
+    static_assert(kMorphDx[15] == 0, "the last element row is one pixel wide");
+    unsigned long long out = (lo >> 32) | (hi << 32);
+    const int valid = w - 64 * k;  // bits of this word inside the image
+    if (valid < 64) out &= (1ull << valid) - 1ull;
+    dst[(size_t)blockIdx.z * frameStride + t] = out;
+}
+
+// The erosion of the dilated plane at ONE pixel, for k_gate: the AND over the 31 element rows of "every dilated bit under the row's
+// window is set".  Rows outside the image and columns outside it count as set (the window is clipped to the image instead of padding the
+// plane with ones).  A clipped window is at most 31 bits: it lies in one word or two neighbouring ones.  Branch-free, so the 62 loads
+// of a keypoint are in flight together.
+__device__ __forceinline__ bool bits_closed_at(const unsigned long long *__restrict__ dil, int words, int w, int h, int ix, int iy)
+{
+    bool all = true;
+#pragma unroll
+    for (int dy = -15; dy <= 15; dy++) {
+        const int r = kMorphDx[dy < 0 ? -dy : dy], yy = iy + dy;
+        const bool inside = yy >= 0 && yy < h;
+        const unsigned long long *row = dil + (size_t)(inside ? yy : iy) * words;
+        const int x0 = max(ix - r, 0), x1 = min(ix + r, w - 1), k0 = x0 >> 6, k1 = x1 >> 6;
+        const unsigned long long m0 = ~0ull << (x0 & 63), m1 = ~0ull >> (63 - (x1 & 63));
+        const unsigned long long a = k0 == k1 ? (m0 & m1) : m0, b = k0 == k1 ? (m0 & m1) : m1;
+        const bool ok = ((row[k0] & a) == a) & ((row[k1] & b) == b);
+        all = all & (ok | !inside);
+    }
+    return all;
+}
+
 // Per-frame offsets of the label gate's inputs (elements) and the element stride of the centre ids: the defaults are the single shared
 // label map / id array / rm vector / error word of amos_orb_gate and amos_orb_gate_batch_device; amos_orb_gate_labels_batch_device reads
 // one of each per frame and the ids straight out of amos_slic_center records.
@@ -1642,7 +1734,9 @@ struct GateLabelStrides {
 };
 
 // One work-group per frame walks the levels in order; kept keypoints are compacted in place
-// (order preserved), removed ones appended to `removed` in the reference's order.
+// (order preserved), removed ones appended to `removed` in the reference's order.  kBits: the closed mask is not a grey plane; the
+// keypoint's bit of it is made from the dilated bit plane (bits_closed_at).
+template <bool kBits>
 __global__ __launch_bounds__(256) void k_gate(const Geom *__restrict__ g, amos_keypoint *__restrict__ lvKps,
                                              int *__restrict__ lvCount, const uint8_t *__restrict__ closedBase,
                                              size_t closedFrameStride, int maskStride, const double *__restrict__ labelBase,
@@ -1650,12 +1744,14 @@ __global__ __launch_bounds__(256) void k_gate(const Geom *__restrict__ g, amos_k
                                              const int *__restrict__ centerIdBase, int nCenters,
                                              const int *__restrict__ rmBase, int nRm,
                                              amos_keypoint *__restrict__ removed, int *__restrict__ nRemoved,
-                                             int *__restrict__ errBase, const GateLabelStrides ls = GateLabelStrides())
+                                             int *__restrict__ errBase, const GateLabelStrides ls = GateLabelStrides(),
+                                             const unsigned long long *__restrict__ dilBase = nullptr, size_t dilFrameStride = 0,
+                                             int dilWords = 0)
 {
     __shared__ int wkeep[4], wrem[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int frame = blockIdx.x;
-    const uint8_t *closed = closedBase + (size_t)frame * closedFrameStride;
+    const uint8_t *closed = kBits ? nullptr : closedBase + (size_t)frame * closedFrameStride;
     const double *labels = labelBase ? labelBase + (size_t)frame * ls.labelFrame : nullptr;
     const int *centerIds = centerIdBase ? centerIdBase + (size_t)frame * ls.centerFrame : nullptr;
     const int *rm = rmBase ? rmBase + (size_t)frame * ls.rmFrame : nullptr;
@@ -1686,7 +1782,9 @@ __global__ __launch_bounds__(256) void k_gate(const Geom *__restrict__ g, amos_k
                             else if (rm[id] == 1) drop = true;
                         }
                     }
-                    if (closed[(size_t)iy * maskStride + ix] != 0) drop = true;
+                    if (kBits ? bits_closed_at(dilBase + (size_t)frame * dilFrameStride, dilWords, g->W, g->H, ix, iy)
+                              : closed[(size_t)iy * maskStride + ix] != 0)
+                        drop = true;
                 }
             }
             const unsigned long long bk = __ballot(valid && !drop), br = __ballot(valid && drop);

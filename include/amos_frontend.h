@@ -152,7 +152,8 @@ int amos_orb_gate(amos_orb *h, const uint8_t *mask, size_t mask_stride, const do
                   size_t lstride, const int32_t *center_ids, int n_centers,
                   const int32_t *rm_vector, int n_rm, amos_keypoint *removed, int cap,
                   int *n_removed);
-/* The closed mask of the last amos_orb_gate call (for parity tests). */
+/* The closed mask of the last amos_orb_gate call (for parity tests).  AMOS_ERR_STATE when no gate has run, and when the last gate
+ * was a batch gate on bit planes (amos_orb_gate_mode 1, the default): that gate makes no grey closed mask. */
 int amos_orb_closed_mask(amos_orb *h, uint8_t *dst, size_t dst_stride);
 
 /* a9: 7x7 sigma-2 blur of every level, 256-bit rBRIEF of the current per-level lists, rescale of
@@ -202,6 +203,14 @@ int amos_orb_gate_labels_batch_device(amos_orb *h, const uint8_t *d_masks, size_
                                       const struct amos_slic_center *d_centers, size_t centers_frame_stride, int n_centers,
                                       const int32_t *d_rm, size_t rm_frame_stride, int n_rm, int32_t *d_status);
 int amos_orb_describe_batch_device(amos_orb *h);
+/* How the two batch gates close the masks.  1 (default): on bit planes -- the gate only asks closed(y, x) != 0, and the non-zero set of
+ * the grey closing is the binary closing of the mask's non-zero set; the same keypoints are removed, amos_orb_closed_mask is not
+ * available afterwards.  0: grey planes, as amos_orb_gate.  Other values only query.  Returns the previous mode; the initial value is
+ * AMOS_GATE_BITS=0 / 1 in the environment, read once per process. */
+int amos_orb_gate_mode(int mode);
+/* The keypoints the last gate removed from `frame` of the batch, in the reference's order, to host memory (removed may be NULL: the
+ * count only).  Synchronises the handle's stream.  For parity tests. */
+int amos_orb_batch_removed(amos_orb *h, int frame, amos_keypoint *removed, int cap, int *n_removed);
 
 /* ---- callers either side of the path (SURVEY 8f "next" rows), device resident ----
  * Tracking::GrabImageRGBD's cvtColor(..., CV_{BGR,RGB}[A]2GRAY) (Tracking.cc:308-321) fused into the
@@ -792,6 +801,15 @@ int amos_mask_pre_create(int device, void *stream, int width, int height, int ma
 void amos_mask_pre_destroy(amos_mask_pre *p);
 void *amos_mask_pre_stream(amos_mask_pre *p); /* the hipStream_t the handle issues on */
 int amos_mask_preprocess_batch_device(amos_mask_pre *p, const uint8_t *d_bgr, int n_frames, float *d_out);
+/* How the chain runs (this call and amos_orb_detect_color_with_mask_pre_batch_device).  1 (default): one kernel from the u8 frame to the
+ * tensor, the two intermediate images staying in on-chip memory, for every frame size whose source windows fit there (640 x 480,
+ * 1280 x 720; not 1920 x 1080 -- such sizes take the three kernels whatever the mode).  0: three kernels through two float intermediates
+ * (2 x 3.7 MB per frame of max_batch, allocated on the first such call).  The tensor has the same bits either way.  Other values only
+ * query.  Returns the previous mode; the initial value is AMOS_MASK_PRE_FUSED=0 / 1 in the environment, read once per process. */
+int amos_mask_pre_mode(int mode);
+/* 1 when calls on this handle take the one-pass kernel under the current mode, 0 when they take the three kernels;
+ * source_window_bytes (may be NULL): what the frame size needs of the kernel's 16 KB source window. */
+int amos_mask_pre_one_pass(const amos_mask_pre *p, int *source_window_bytes);
 
 /* SURVEY 8f-4, "one pass over the RGB-D frame": the colour frame is read ONCE for both of its consumers -- the gray
  * conversion into the padded level 0 (Tracking.cc:308-321, then the rest of amos_orb_detect_batch_device) and stage A of

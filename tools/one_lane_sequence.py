@@ -8,7 +8,8 @@ import sys
 trace = max(glob.glob(sys.argv[1] + "/*/*kernel_trace.csv"), key=os.path.getmtime)
 min_us = float(sys.argv[2]) if len(sys.argv) > 2 else 40.0
 rows = sorted(csv.DictReader(open(trace)), key=lambda r: int(r["Start_Timestamp"]))
-idx = [i for i, r in enumerate(rows) if "k_import_color_mask" in r["Kernel_Name"]]
+FIRST = ("k_import_color_mask", "k_pyramid_level0_color")  # a pass's first kernel: the fused import, or the plain one before k_mask_pre_fused
+idx = [i for i, r in enumerate(rows) if any(k in r["Kernel_Name"] for k in FIRST)]
 rs = rows[idx[-2]:idx[-1]]
 t0 = int(rs[0]["Start_Timestamp"])
 for r in rs:
