@@ -87,6 +87,8 @@ PROTOTYPES = {
     "amos_match_local_points": (_i, (_v, _v, _v, _v, _i, _v, _i, _v, _v, _v, _i, _f, _f, _f, _f, _v, _v, _v, _v)),
     "amos_match_motion_model_batch_device": (_i, (_v, _v)),
     "amos_match_motion_model": (_i, (_v, _v, _v, _v, _i, _v, _i, _v, _v, _i, _f, _f, _f, _f, _v, _v, _v, _v)),
+    "amos_match_pose_optimization_batch_device": (_i, (_v, _v)),
+    "amos_match_pose_optimization": (_i, (_v, _v, _v, _i, _v, _v, _v, _i, _v, _v, _i, _i, _v, _v)),
     "amos_bow_create": (_i, (_i, _v, _i, _i, _i, _i, _i, _v, _v, _v, _v, _v)),
     "amos_bow_destroy": (None, (_v,)),
     "amos_bow_sync": (_i, (_v,)),
@@ -1005,6 +1007,36 @@ class MotionSearch(C.Structure):
                 ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float)]
 
 
+class PoseCamera(C.Structure):
+    """amos_pose_camera: 68 bytes; POSE_CAMERA_DTYPE is the same record for numpy."""
+    _fields_ = [("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("mbf", C.c_float)]
+
+
+class PoseResult(C.Structure):
+    """amos_pose_result: 272 bytes; POSE_RESULT_DTYPE is the same record for numpy."""
+    _fields_ = [("Rt", C.c_double * 12), ("Tcw", C.c_float * 12), ("Ow", C.c_float * 3), ("n_edges", C.c_int32), ("n_inliers", C.c_int32),
+                ("n_inliers_with_obs", C.c_int32), ("rounds", C.c_int32), ("status", C.c_int32), ("iterations", C.c_int32 * 4),
+                ("trials", C.c_int32 * 4), ("lambda_", C.c_double * 4), ("chi2", C.c_double * 4)]
+
+
+POSE_STATUS_OCTAVE, POSE_STATUS_MATCH_INDEX = 1, 2  # amos_pose_result.status
+POSE_CAMERA_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"),
+                              ("mbf", "<f4")])
+POSE_RESULT_DTYPE = np.dtype([("Rt", "<f8", (12,)), ("Tcw", "<f4", (12,)), ("Ow", "<f4", (3,)), ("n_edges", "<i4"), ("n_inliers", "<i4"),
+                              ("n_inliers_with_obs", "<i4"), ("rounds", "<i4"), ("status", "<i4"), ("iterations", "<i4", (4,)),
+                              ("trials", "<i4", (4,)), ("lambda", "<f8", (4,)), ("chi2", "<f8", (4,))])
+assert (C.sizeof(PoseCamera), C.sizeof(PoseResult)) == (POSE_CAMERA_DTYPE.itemsize, POSE_RESULT_DTYPE.itemsize) == (68, 272)
+
+
+class PoseOptimization(C.Structure):
+    """amos_pose_optimization (include/amos_frontend.h)."""
+    _fields_ = [("d_kps", C.c_void_p), ("d_u_right", C.c_void_p), ("d_counts", C.c_void_p), ("d_match", C.c_void_p), ("d_points", C.c_void_p),
+                ("point_stride", C.c_int32), ("flags_offset", C.c_int32), ("has_obs_bit", C.c_int32), ("point_off", C.c_void_p),
+                ("cameras", C.c_void_p), ("inv_level_sigma2", C.c_void_p), ("d_outlier", C.c_void_p), ("d_result", C.c_void_p),
+                ("n_frames", C.c_int32), ("capacity", C.c_int32), ("n_levels", C.c_int32), ("clear_outliers", C.c_int32)]
+
+
 BOW_L1_NORM, BOW_TF_IDF = 0, 0  # DBoW2::ScoringType, DBoW2::WeightingType: what a vocabulary handle is built for
 BOW_MAX_CHILDREN, BOW_MAX_CAPACITY, BOW_NO_WORD, BOW_STATUS_EARLY_LEAF = 32, 16384, 0xFFFFFFFF, 1
 BOW_STATS_DTYPE = np.dtype([("n_words", "<i4"), ("n_nodes", "<i4"), ("n_stopped", "<i4"), ("status", "<i4")])
@@ -1258,6 +1290,41 @@ class OrbMatcher(_Handle):
         _check(self.L.amos_match_motion_model(self.h, _p(kps_un), _p(desc), _p(ur), n, _p(points), m, _p(cam), _p(sf), len(sf), *bounds,
                                               _p(query), _p(projected), _p(match), _p(stats)), "amos_match_motion_model")
         return query, projected, match, stats[0]
+
+    def pose_optimization_batch_device(self, d_kps, d_counts, d_match, d_points, point_off, cameras, capacity, inv_level_sigma2, d_outlier,
+                                       d_result, point_stride=12, flags_offset=-1, has_obs_bit=0, clear_outliers=False, d_u_right=None):
+        """Optimizer::PoseOptimization for resident frames (Optimizer.cc:363-605), one launch: d_match / d_points are a search's output and
+        input (point_stride / flags_offset / has_obs_bit say which record: amos_map_point 80 / 32 / 2, amos_last_point 64 / 20 / 2, bare
+        float[3] 12 / -1).  point_off: n_frames + 1 host ints; cameras: host POSE_CAMERA_DTYPE records.  Writes d_outlier and POSE_RESULT_DTYPE
+        records into d_result.  Asynchronous on the matcher's stream."""
+        sig = np.ascontiguousarray(inv_level_sigma2, np.float32)
+        off = np.ascontiguousarray(point_off, np.int32)
+        cams = np.ascontiguousarray(cameras, POSE_CAMERA_DTYPE).reshape(-1)
+        if len(off) != len(cams) + 1:
+            raise ValueError("point_off holds one entry more than cameras")
+        s = PoseOptimization(d_kps, d_u_right, d_counts, d_match, d_points, point_stride, flags_offset, has_obs_bit, off.ctypes.data,
+                             cams.ctypes.data, sig.ctypes.data, d_outlier, d_result, len(cams), capacity, len(sig), int(bool(clear_outliers)))
+        _check(self.L.amos_match_pose_optimization_batch_device(self.h, C.byref(s)), "amos_match_pose_optimization_batch_device")
+
+    def pose_optimization(self, kps_un, match, points_xyz, camera, inv_level_sigma2, outlier=None, has_obs=None, clear_outliers=False,
+                          u_right=None):
+        """The same for ONE frame from host arrays (amos_match_pose_optimization): returns (result, outlier, match); the arguments are
+        not modified.  outlier: what mvbOutlier holds on entry (zeros by default)."""
+        kps_un = np.ascontiguousarray(kps_un, KP_DTYPE)
+        n = len(kps_un)
+        match = np.array(match, np.int32).reshape(-1)
+        pts = np.ascontiguousarray(points_xyz, np.float32).reshape(-1, 3)
+        cam = np.ascontiguousarray(camera, POSE_CAMERA_DTYPE).reshape(1)
+        sig = np.ascontiguousarray(inv_level_sigma2, np.float32)
+        ur = None if u_right is None else np.ascontiguousarray(u_right, np.float32)
+        ho = None if has_obs is None else np.ascontiguousarray(has_obs, np.uint8)
+        outlier = np.zeros(n, np.uint8) if outlier is None else np.array(outlier, np.uint8).reshape(-1)
+        if len(match) != n or len(outlier) != n or (ur is not None and len(ur) != n) or (ho is not None and len(ho) != len(pts)):
+            raise ValueError("match, outlier and u_right hold one entry per keypoint, has_obs one per point")
+        result = np.zeros(1, POSE_RESULT_DTYPE)
+        _check(self.L.amos_match_pose_optimization(self.h, _p(kps_un), _p(ur), n, _p(match), _p(pts), _p(ho), len(pts), _p(cam), _p(sig), len(sig),
+                                                   int(bool(clear_outliers)), _p(outlier), _p(result)), "amos_match_pose_optimization")
+        return result[0], outlier, match
 
     def bow_batch_device(self, d_kps, d_desc, d_counts, d_n_nodes, d_node_ids, d_node_off, d_node_idx, d_pairs_kf, d_pairs_f, n_pairs, capacity,
                          d_match, d_stats, nn_ratio=0.7, check_orientation=True, d_has_point=None):

@@ -534,6 +534,64 @@ int amos_match_motion_model(amos_match *m, const amos_keypoint *kps_un, const ui
                             int n_levels, float min_x, float max_x, float min_y, float max_y, struct amos_proj_query *query,
                             uint8_t *projected, int32_t *match, amos_motion_stats *stats);
 
+/* ---------------------------------------------------------------- pose optimisation ---------- */
+
+/* Optimizer::PoseOptimization(&mCurrentFrame) (Optimizer.cc:363-605) for a batch of resident frames, behind any search that writes
+ * d_match: the motion-only bundle adjustment that follows every search of the tracking thread (Tracking.cc:1764, :1953, :2014 and the calls
+ * inside Relocalization), with g2o's Levenberg-Marquardt, Huber kernel, projection edges and dense LDL^T solve restated in double
+ * (amos-slam_amd/csrc/amos_pose_core.h: PARITY WITH g2o UNPINNED; the header lists the deviations).  ONE launch, one work-group per frame.
+ *
+ * Feature i < d_counts[f] with d_match[i] >= 0 is an edge: monocular when d_u_right is NULL or d_u_right[i] < 0, else stereo; its point is
+ * record point_off[f] + d_match[i] of d_points, its weight inv_level_sigma2[octave].  A feature whose octave lies outside [0, n_levels)
+ * or whose match index lies outside the frame's points is skipped and sets bit 0 / bit 1 of status.  Fewer than 3 edges: the result holds
+ * the input pose, n_inliers = 0, rounds = 0, and d_outlier / d_match are not written.  Otherwise d_outlier[i] is written for every edge
+ * (other features keep what the array held) and the result is the last executed round's pose. */
+typedef struct amos_pose_camera {      /* per frame: 68 bytes */
+    float Rcw[9], tcw[3];              /* the frame's mTcw on entry, rotation row-major */
+    float fx, fy, cx, cy, mbf;
+} amos_pose_camera;
+
+typedef struct amos_pose_result {      /* per frame: 272 bytes */
+    double Rt[12];                     /* the optimised pose in double: R row-major, then t */
+    float Tcw[12], Ow[3];              /* what SetPose / UpdatePoseMatrices store: rows of [R|t] as float; Ow = -Rcw^T tcw, one gemm per row in double, one rounding */
+    int32_t n_edges;                   /* nInitialCorrespondences */
+    int32_t n_inliers;                 /* the return value: nInitialCorrespondences - nBad */
+    int32_t n_inliers_with_obs;        /* inlier edges whose point has the has_obs bit (all of them when flags_offset is -1): nmatchesMap */
+    int32_t rounds;                    /* executed rounds: 0, 1 (fewer than 10 edges) or 4 */
+    int32_t status;                    /* bit 0: an octave outside the table; bit 1: a match index outside the frame's points */
+    int32_t iterations[4], trials[4];  /* per round: calls of the Levenberg solve, and its trial steps in all */
+    double lambda[4], chi2[4];         /* at each round's end: the damping, the active robust chi2 */
+} amos_pose_result;
+
+typedef struct amos_pose_optimization {
+    const amos_keypoint *d_kps;        /* [frames][capacity]: mvKeysUn */
+    const float *d_u_right;            /* [frames][capacity] or NULL: every edge monocular */
+    const int32_t *d_counts;           /* [frames] */
+    int32_t *d_match;                  /* [frames][capacity]: index into the frame's point list or -1 (a search's output; written only with clear_outliers) */
+    const void *d_points;              /* records of point_stride bytes that begin with float pos[3]: amos_map_point, amos_last_point, or a bare float[3] */
+    int32_t point_stride;              /* a multiple of 4, >= 12 */
+    int32_t flags_offset;              /* byte offset of the record's int32 flags (a multiple of 4), or -1: no flags */
+    int32_t has_obs_bit;               /* AMOS_MAP_POINT_HAS_OBS / AMOS_LAST_POINT_HAS_OBS */
+    const int32_t *point_off;          /* host, n_frames + 1 entries, ascending from >= 0: frame f owns points [point_off[f], point_off[f + 1]) */
+    const amos_pose_camera *cameras;   /* host, n_frames entries */
+    const float *inv_level_sigma2;     /* host, n_levels entries (mvInvLevelSigma2) */
+    uint8_t *d_outlier;                /* out, [frames][capacity]: mvbOutlier */
+    amos_pose_result *d_result;        /* out, [frames] */
+    int32_t n_frames, capacity, n_levels;
+    int32_t clear_outliers;            /* 1: the loop of Tracking.cc:1770-1791: d_match[i] = -1 and d_outlier[i] = 0 where an outlier was; 0: d_match is only read (TrackLocalMap) */
+} amos_pose_optimization;
+/* Asynchronous on the matcher's stream (the three host arrays are consumed before the call returns).  AMOS_ERR_INVALID, before the device
+ * is touched, for a NULL handle or argument (d_u_right apart), n_frames < 1, a capacity outside 1 .. 65536, n_levels outside
+ * 1 .. AMOS_MAX_LEVELS, a point_stride / flags_offset that breaks the rules above, a clear_outliers other than 0 / 1, or a point_off that
+ * descends. */
+int amos_match_pose_optimization_batch_device(amos_match *m, const amos_pose_optimization *s);
+/* The host form for a C++ drop-in (amos-slam_amd/host/FramePoseOptimization.h): ONE frame of n features, host arrays in and out,
+ * synchronous: one upload, the launch, one download.  match [n] and outlier [n] are read and written in place; points_xyz [n_points][3];
+ * has_obs [n_points] (Observations() > 0) or NULL: every point counts.  The return value of PoseOptimization is result->n_inliers. */
+int amos_match_pose_optimization(amos_match *m, const amos_keypoint *kps_un, const float *u_right, int n, int32_t *match, const float *points_xyz,
+                                 const uint8_t *has_obs, int n_points, const amos_pose_camera *camera, const float *inv_level_sigma2, int n_levels,
+                                 int clear_outliers, uint8_t *outlier, amos_pose_result *result);
+
 /* ---------------------------------------------------------------- bag of words --------------- */
 
 /* Tracking::TrackReferenceKeyFrame's two steps (Tracking.cc:1736-1794) for resident frames: Frame::ComputeBoW (Frame.cc:1033-1049), which is
