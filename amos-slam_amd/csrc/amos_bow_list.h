@@ -1,6 +1,6 @@
-// amos_bow_list.h -- what the searches over two FeatureVectors share (amos_bow_search.hip: keyframe against frame; amos_kf_search.hip:
-// keyframe against keyframe): one frame's side of the resident CSR with its clamps, the wave-wide search of one node's list, and what a
-// host form asks of an amos_bow_view before its arrays go to the device.
+// amos_bow_list.h -- what the searches over two FeatureVectors (amos_bow_search.hip) are built on: one frame's side of the resident CSR
+// with its clamps, the wave-wide search of one node's list, and what a host form asks of an amos_bow_view before its arrays go to the
+// device.
 #pragma once
 #include "amos_projection_search.h"  // TakenBitmap, best-two keys, the matcher's staging
 
@@ -31,17 +31,14 @@ __device__ __forceinline__ BowSide bow_side(const A &a, int slot)
 template <class A>
 __device__ __forceinline__ int bow_off(const A &a, const BowSide &s, int node) { return min(max(s.off[node], 0), a.capacity); }
 
-// The whole wave searches the list positions [b0, b1) of a node; cand(j, key) says whether position j holds a candidate and gives its
-// key (unique per position, the smaller the better).  All 64 lanes call it converged; best / second come back wave-uniform, 0xffffffff
-// for none.
+// The whole wave searches the list positions [b0, b1) of a node; cand(j) gives the key of position j (unique per position, the smaller
+// the better) or 0xffffffff when it holds no candidate: pushing that changes nothing, so the loop keeps no flag beside the two keys.  All
+// 64 lanes call it converged; best / second come back wave-uniform, 0xffffffff for none.
 template <class Cand>
 __device__ __forceinline__ void wave_list_keys(int b0, int b1, int lane, Cand cand, unsigned &best, unsigned &second)
 {
     best = second = 0xffffffffu;
-    for (int j = b0 + lane; j < b1; j += 64) {
-        unsigned key;
-        if (cand(j, key)) top2_push(best, second, key);
-    }
+    for (int j = b0 + lane; j < b1; j += 64) top2_push(best, second, cand(j));
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         const unsigned ob = __shfl_xor(best, off, 64), os = __shfl_xor(second, off, 64);
@@ -49,27 +46,6 @@ __device__ __forceinline__ void wave_list_keys(int b0, int b1, int lane, Cand ca
     }
     best = __builtin_amdgcn_readfirstlane(best);
     second = __builtin_amdgcn_readfirstlane(second);
-}
-
-// the whole wave searches a node's list again, against the taken features; the record comes back wave-uniform.  (k_bow_accept's own form
-// of the loop above, kept as it was: written over wave_list_keys it costs that kernel 2 VGPRs and 7 SGPRs more.)
-__device__ __forceinline__ amos_best2 wave_list_best2(const BowSide &fr, int b0, int b1, const Desc &q, const TakenBitmap &taken, int lane)
-{
-    unsigned best = 0xffffffffu, second = 0xffffffffu;
-    for (int j = b0 + lane; j < b1; j += 64) {
-        const int idx = fr.idx[j];
-        if ((unsigned)idx >= (unsigned)fr.n || taken.test(idx)) continue;
-        const int d = hamming256(q, load_desc(fr.desc + (size_t)idx * 32));
-        if (d < kInitDist) top2_push(best, second, ((unsigned)d << 16) | (unsigned)(j - b0));
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned ob = __shfl_xor(best, off, 64), os = __shfl_xor(second, off, 64);
-        top2_merge(best, second, ob, os);
-    }
-    best = __builtin_amdgcn_readfirstlane(best);
-    second = __builtin_amdgcn_readfirstlane(second);
-    return best2_from_keys(best, second, fr.idx + b0, kInitDist);
 }
 
 // what a host form asks of a view before its arrays go to the device

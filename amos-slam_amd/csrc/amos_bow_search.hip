@@ -1,10 +1,14 @@
-// amos_bow_search.hip -- ORBmatcher::SearchByBoW(KeyFrame *pKF, Frame &F, vpMapPointMatches) (ORBmatcher.cc:230-382) for a batch of
-// (keyframe, frame) pairs of resident frames whose FeatureVectors are the CSR of amos_bow_transform_batch_device (amos_bow.hip).
+// amos_bow_search.hip -- the three greedy searches over a pair of FeatureVectors (the CSR of amos_bow_transform_batch_device, amos_bow.hip),
+// for a batch of (side 1, side 2) pairs of resident frames: ORBmatcher::SearchByBoW(pKF, F, vpMapPointMatches) (ORBmatcher.cc:230-382: side 1
+// is the keyframe, side 2 the frame), ORBmatcher::SearchByBoW(pKF1, pKF2, vpMatches12) (:656-799) and ORBmatcher::SearchForTriangulation
+// (:810-1009).
 //
-// Launches on the matcher's stream: k_bow_best2 (eight lanes per keyframe feature: the best two frame features of its node, taken or not)
-// and k_bow_accept (one wave per pair: the reference's sequential loop over those records, then the rotation histogram's pruning).  The
-// semantics are defined in include/amos_frontend.h, "bag of words".
-#include "amos_bow_list.h"  // BowSide, the wave's list search, bow_view_ok
+// All are the same two launches on the matcher's stream, built from one prepass and one acceptance template over a policy (the query
+// filter, the candidate filter, the key order, what a taken record means, the distance bound and the ratio test, which side indexes the result):
+// k_list_best2 (eight lanes per list position of side 1: the best two side-2 features of its node under the filters that do not depend on
+// what has been matched) and k_list_accept (one wave per pair: the reference's sequential loop over those records with the taken side-2
+// features as a bitmap in LDS, then the rotation histogram's pruning).  The semantics are defined in include/amos_frontend.h, "bag of words".
+#include "amos_bow_list.h"
 
 #include <vector>
 
@@ -12,89 +16,211 @@ namespace amos {
 
 static_assert(sizeof(amos_bow_search_stats) == 16, "amos_bow_search_stats is 16 bytes (include/amos_frontend.h)");
 
-struct BowSearchArgs {
+struct ListSearchArgs {
     const amos_keypoint *kps;
     const uint8_t *desc;
     const int *counts, *nNodes;
     const uint32_t *nodeIds;
     const int *nodeOff, *nodeIdx;
     const uint8_t *hasPoint;
-    const int *pairsKf, *pairsF;
-    int *match;
+    const float *uRight;
+    const int *pairs1, *pairs2;
+    int *match;  // per pair: indexed by side 1's feature and holding side 2's, or the other way round (the policy's kMatchBySide2)
     amos_bow_search_stats *stats;
-    amos_best2 *best2;  // scratch, per pair and keyframe list position: the prepass record (indices are frame features)
-    int *part;          // scratch, alike: the frame's node (its place in the frame's node list) the query searches, -1: none (its node is
-                        // not shared, or no map point), -2: a feature index outside the keyframe
-    int *accepted;      // scratch, alike: -1, or bin << 16 | frame feature of the query's accepted match
-    int capacity;
+    amos_best2 *best2;  // scratch, per pair and side-1 list position: the prepass record (indices are side-2 features)
+    int *part;          // scratch, alike: -1: no query, -2: a feature index outside side 1, else side 2's node (its place in the node list)
+                        // in the low 20 bits and kPartBadOctave when a candidate's octave was out of range
+    int *accepted;      // scratch, alike: -1, or the bin of the query's accepted match (under kMatchBySide2: bin << 16 | side-2 feature, the
+                        // entry of `match` it wrote; otherwise that entry is the query's own feature)
+    const amos_kf_geometry *geometry;  // triangulation: [pairs]
+    const float *scale, *sigma2;       // triangulation: [nLevels]
+    int capacity, nLevels;
     float nnRatio;
-    int checkOri;
+    int checkOri, onlyStereo;
+};
+constexpr int kPartNodeMask = 0xfffff, kPartBadOctave = 1 << 20;  // (a node's place is below 65536)
+
+// what the acceptance does with a prepass record
+enum Taken { kKeep, kSecond, kAgain, kNone };
+
+// ---- SearchByBoW(pKF, F, vpMapPointMatches): side 1 is the keyframe, side 2 the frame
+struct BowFramePolicy {
+    struct Query {};
+    static constexpr bool kMatchBySide2 = true;  // match[frame feature] = keyframe feature
+    // :264-270: only the keyframe's features need a good map point
+    __device__ static bool query_ok(const ListSearchArgs &a, int slot1, int idx1) { return !a.hasPoint || a.hasPoint[(size_t)slot1 * a.capacity + idx1]; }
+    __device__ static Query query(const ListSearchArgs &, int, const BowSide &, int, int) { return Query{}; }
+    // :278-304 without the "already matched" test: dist < 256 (bestDist1's start); the frame's has_point is never read
+    __device__ static bool candidate(const ListSearchArgs &, const Query &, const Desc &q, const BowSide &s2, int, int idx2, int &dist, int &)
+    {
+        dist = hamming256(q, load_desc(s2.desc + (size_t)idx2 * 32));
+        return dist < kInitDist;
+    }
+    // the first of equal distances
+    __device__ static unsigned key(int dist, int pos) { return ((unsigned)dist << 16) | (unsigned)pos; }
+    __device__ static int pos(unsigned key) { return (int)(key & 0xffffu); }
+    // the second best distance enters the ratio test: the record stands only when neither of its two is taken
+    __device__ static Taken taken(const TakenBitmap &t, int bi, int si) { return t.either(bi, si) ? kAgain : kKeep; }
+    // :306-309: bestDist1 <= TH_LOW, then the ratio test
+    static constexpr int kMaxDist = AMOS_TH_LOW;
+    __device__ static bool ratio_ok(const ListSearchArgs &a, int bd, int sd) { return (float)bd < __fmul_rn(a.nnRatio, (float)sd); }
 };
 
-// ---- the candidate loop of ORBmatcher.cc:278-304 against the frame with nothing matched yet (list order is candidate order: the first of
-// equal distances wins).  grid = (ceil(capacity * 8 / 256), pairs), block = 256.
-__global__ __launch_bounds__(256) void k_bow_best2(const BowSearchArgs a)
+// ---- SearchByBoW(pKF1, pKF2, vpMatches12): the search above between two keyframes, but for
+struct BowKfPolicy : BowFramePolicy {
+    static constexpr bool kMatchBySide2 = false;  // match12[idx1] = idx2
+    // :700-722 without the vbMatched2 test: keyframe 2's feature needs a good map point too
+    __device__ static bool candidate(const ListSearchArgs &a, const Query &pq, const Desc &q, const BowSide &k2, int slot2, int idx2, int &dist, int &bad)
+    {
+        if (a.hasPoint && !a.hasPoint[(size_t)slot2 * a.capacity + idx2]) return false;
+        return BowFramePolicy::candidate(a, pq, q, k2, slot2, idx2, dist, bad);
+    }
+    static constexpr int kMaxDist = AMOS_TH_LOW - 1;  // :724-726: bestDist1 < TH_LOW, strictly; the same ratio test
+};
+
+// ---- SearchForTriangulation
+struct TriangulationPolicy {
+    struct Query {
+        float a, b, c;  // the epipolar line of keyframe 1's feature in keyframe 2 (CheckDistEpipolarLine, :191-193)
+        float ex, ey;
+        bool stereo;
+    };
+    static constexpr bool kMatchBySide2 = false;  // match12[idx1] = idx2
+    __device__ static bool stereo(const ListSearchArgs &a, int slot, int idx) { return a.uRight && a.uRight[(size_t)slot * a.capacity + idx] >= 0; }
+    __device__ static bool query_ok(const ListSearchArgs &a, int slot1, int idx1)
+    {
+        if (a.hasPoint && a.hasPoint[(size_t)slot1 * a.capacity + idx1]) return false;  // :856-858
+        return !a.onlyStereo || stereo(a, slot1, idx1);                                  // :860-864
+    }
+    __device__ static Query query(const ListSearchArgs &a, int pair, const BowSide &k1, int slot1, int idx1)
+    {
+        const amos_kf_geometry g = a.geometry[pair];
+        const float x = k1.kps[idx1].x, y = k1.kps[idx1].y;
+        Query q;
+        q.a = __fadd_rn(__fadd_rn(__fmul_rn(x, g.f12[0]), __fmul_rn(y, g.f12[3])), g.f12[6]);
+        q.b = __fadd_rn(__fadd_rn(__fmul_rn(x, g.f12[1]), __fmul_rn(y, g.f12[4])), g.f12[7]);
+        q.c = __fadd_rn(__fadd_rn(__fmul_rn(x, g.f12[2]), __fmul_rn(y, g.f12[5])), g.f12[8]);
+        q.ex = g.ex; q.ey = g.ey;
+        q.stereo = stereo(a, slot1, idx1);
+        return q;
+    }
+    // :875-915 without the vbMatched2 test and the running bound: no map point, stereo under onlyStereo, dist <= TH_LOW, then the geometry
+    __device__ static bool candidate(const ListSearchArgs &a, const Query &q, const Desc &d1, const BowSide &k2, int slot2, int idx2, int &dist, int &bad)
+    {
+        if (a.hasPoint && a.hasPoint[(size_t)slot2 * a.capacity + idx2]) return false;
+        const bool stereo2 = stereo(a, slot2, idx2);
+        if (a.onlyStereo && !stereo2) return false;
+        dist = hamming256(d1, load_desc(k2.desc + (size_t)idx2 * 32));
+        if (dist > AMOS_TH_LOW) return false;
+        const amos_keypoint kp2 = k2.kps[idx2];
+        if ((unsigned)kp2.octave >= (unsigned)a.nLevels) { bad = 1; return false; }
+        if (!q.stereo && !stereo2) {  // :899-905
+            const float distex = __fsub_rn(q.ex, kp2.x), distey = __fsub_rn(q.ey, kp2.y);
+            if (__fadd_rn(__fmul_rn(distex, distex), __fmul_rn(distey, distey)) < __fmul_rn(100.0f, a.scale[kp2.octave])) return false;
+        }
+        const float num = __fadd_rn(__fadd_rn(__fmul_rn(q.a, kp2.x), __fmul_rn(q.b, kp2.y)), q.c);  // :195-208
+        const float den = __fadd_rn(__fmul_rn(q.a, q.a), __fmul_rn(q.b, q.b));
+        if (den == 0) return false;
+        const float dsqr = __fdiv_rn(__fmul_rn(num, num), den);
+        return (double)dsqr < __dmul_rn(3.84, (double)a.sigma2[kp2.octave]);
+    }
+    // the LAST of equal distances (dist > bestDist skips, an equal distance replaces)
+    __device__ static unsigned key(int dist, int pos) { return ((unsigned)dist << 16) | (unsigned)(0xffff - pos); }
+    __device__ static int pos(unsigned key) { return 0xffff - (int)(key & 0xffffu); }
+    // only the best is the result: a taken best leaves the second (the best of everything else), and only two taken ask for a new search
+    __device__ static Taken taken(const TakenBitmap &t, int bi, int si)
+    {
+        if (!t.test(bi)) return kKeep;
+        if (si < 0) return kNone;
+        return t.test(si) ? kAgain : kSecond;
+    }
+    // no bound (a candidate is within TH_LOW already) and no ratio test: the distances of a record are not even read
+    static constexpr int kMaxDist = INT_MAX;
+    __device__ static bool ratio_ok(const ListSearchArgs &, int, int) { return true; }
+};
+
+// keys -> the record; `it` is the node's list in side 2
+template <class P>
+__device__ __forceinline__ amos_best2 list_record(unsigned best, unsigned second, const int *it)
+{
+    amos_best2 r;
+    r.best_idx = best == 0xffffffffu ? -1 : it[P::pos(best)];
+    r.best_dist = best == 0xffffffffu ? kInitDist : (int)(best >> 16);
+    r.second_idx = second == 0xffffffffu ? -1 : it[P::pos(second)];
+    r.second_dist = second == 0xffffffffu ? kInitDist : (int)(second >> 16);
+    return r;
+}
+
+// ---- the candidate loop against side 2 with nothing matched yet.  grid = (ceil(capacity * 8 / 256), pairs), block = 256.
+template <class P>
+__global__ __launch_bounds__(256) void k_list_best2(const ListSearchArgs a)
 {
     const int t = blockIdx.x * 256 + threadIdx.x, p = blockIdx.y;
-    const int ik = t / kWindowLanes, sub = t % kWindowLanes;
-    const int slotKf = a.pairsKf[p];
-    const BowSide kf = bow_side(a, slotKf), fr = bow_side(a, a.pairsF[p]);
-    const bool active = ik < bow_off(a, kf, kf.nNodes);
+    const int i1 = t / kWindowLanes, sub = t % kWindowLanes;
+    const int slot1 = a.pairs1[p], slot2 = a.pairs2[p];
+    const BowSide s1 = bow_side(a, slot1), s2 = bow_side(a, slot2);
+    const bool active = i1 < bow_off(a, s1, s1.nNodes);
     int part = -1, b0 = 0, b1 = 0;
     Desc q = {};
+    typename P::Query pq = {};
     if (active) {
-        int lo = 0, hi = kf.nNodes - 1;  // the last node whose list starts at or before ik
+        int lo = 0, hi = s1.nNodes - 1;  // the last node whose list starts at or before i1
         while (lo < hi) {
             const int mid = (lo + hi + 1) >> 1;
-            if (bow_off(a, kf, mid) <= ik) lo = mid; else hi = mid - 1;
+            if (bow_off(a, s1, mid) <= i1) lo = mid; else hi = mid - 1;
         }
-        const uint32_t id = kf.ids[lo];
-        int b = 0, e = fr.nNodes;  // the first frame node with an id >= id
+        const uint32_t id = s1.ids[lo];
+        int b = 0, e = s2.nNodes;  // the first node of side 2 with an id >= id
         while (b < e) {
             const int mid = (b + e) >> 1;
-            if (fr.ids[mid] < id) b = mid + 1; else e = mid;
+            if (s2.ids[mid] < id) b = mid + 1; else e = mid;
         }
-        const int realIdxKF = kf.idx[ik];
-        if ((unsigned)realIdxKF >= (unsigned)kf.n) part = -2;
-        else if (b < fr.nNodes && fr.ids[b] == id && (!a.hasPoint || a.hasPoint[(size_t)slotKf * a.capacity + realIdxKF])) {
+        const int idx1 = s1.idx[i1];
+        if ((unsigned)idx1 >= (unsigned)s1.n) part = -2;
+        else if (b < s2.nNodes && s2.ids[b] == id && P::query_ok(a, slot1, idx1)) {
             part = b;
-            b0 = bow_off(a, fr, b);
-            b1 = max(bow_off(a, fr, b + 1), b0);
-            q = load_desc(kf.desc + (size_t)realIdxKF * 32);
+            b0 = bow_off(a, s2, b);
+            b1 = max(bow_off(a, s2, b + 1), b0);
+            q = load_desc(s1.desc + (size_t)idx1 * 32);
+            pq = P::query(a, p, s1, slot1, idx1);
         }
     }
     unsigned best = 0xffffffffu, second = 0xffffffffu;
+    int bad = 0;
     for (int j = b0 + sub; j < b1; j += kWindowLanes) {
-        const int idx = fr.idx[j];
-        if ((unsigned)idx >= (unsigned)fr.n) continue;
-        const int d = hamming256(q, load_desc(fr.desc + (size_t)idx * 32));
-        if (d < kInitDist) top2_push(best, second, ((unsigned)d << 16) | (unsigned)(j - b0));
+        const int idx2 = s2.idx[j];
+        if ((unsigned)idx2 >= (unsigned)s2.n) continue;
+        int d = 0;
+        if (P::candidate(a, pq, q, s2, slot2, idx2, d, bad)) top2_push(best, second, P::key(d, j - b0));
     }
 #pragma unroll
     for (int off = kWindowLanes / 2; off > 0; off >>= 1) {
         const unsigned ob = __shfl_xor(best, off, kWindowLanes), os = __shfl_xor(second, off, kWindowLanes);
         top2_merge(best, second, ob, os);
+        bad |= __shfl_xor(bad, off, kWindowLanes);
     }
     if (active && sub == 0) {
-        const size_t o = (size_t)p * a.capacity + ik;
-        a.best2[o] = best2_from_keys(best, second, fr.idx + b0, kInitDist);
-        a.part[o] = part;
+        const size_t o = (size_t)p * a.capacity + i1;
+        a.best2[o] = list_record<P>(best, second, s2.idx + b0);
+        a.part[o] = part >= 0 && bad ? part | kPartBadOctave : part;
     }
 }
 
-// ---- the sequential loop of ORBmatcher.cc:254-345 and the pruning of :348-361.  One wave per pair walks the keyframe's list in order with
-// a bitmap of the matched frame features in LDS.  The prepass record stands when neither of its two is matched; otherwise the whole wave
-// searches the node's list again against the bitmap.  Every accepted match is one histogram entry (its frame feature and bin are kept per
-// query in a.accepted); after the loop every entry of a losing bin sets its frame feature to -1 and lowers the count.
+// ---- the sequential loop and the pruning.  One wave per pair walks side 1's list in order with a bitmap of the matched side-2 features
+// in LDS.  P::taken says what a prepass record is worth by now; where it asks for it, the whole wave searches the node's list again
+// against the bitmap.  Every accepted match is one histogram entry (its bin is kept per query in a.accepted); after the loop every entry
+// of a losing bin sets the entry of `match` that its query wrote to -1 and lowers the count.
 // Everything the branches read is wave-uniform (read from one lane, or from LDS behind a barrier), so the barriers are reached by all lanes.
-__global__ __launch_bounds__(64) void k_bow_accept(const BowSearchArgs a)
+template <class P>
+__global__ __launch_bounds__(64) void k_list_accept(const ListSearchArgs a)
 {
     __shared__ TakenBitmap taken;
     __shared__ int hist[AMOS_HISTO_LENGTH];
     const int p = blockIdx.x, lane = threadIdx.x;
     const int cap = a.capacity;
-    const BowSide kf = bow_side(a, a.pairsKf[p]), fr = bow_side(a, a.pairsF[p]);
-    const int mKf = bow_off(a, kf, kf.nNodes);
+    const int slot1 = a.pairs1[p], slot2 = a.pairs2[p];
+    const BowSide s1 = bow_side(a, slot1), s2 = bow_side(a, slot2);
+    const int m1 = bow_off(a, s1, s1.nNodes);
     const bool checkOri = a.checkOri != 0;
     int *match = a.match + (size_t)p * cap;
     const size_t so = (size_t)p * cap;
@@ -102,22 +228,21 @@ __global__ __launch_bounds__(64) void k_bow_accept(const BowSearchArgs a)
     if (lane < AMOS_HISTO_LENGTH) hist[lane] = 0;
     for (int i = lane; i < cap; i += 64) match[i] = -1;
     __syncthreads();
-    const float factor = AMOS_HISTO_LENGTH / 360.0f;
     int nQueries = 0, nMatches = 0, nResearched = 0, bad = 0;
-    for (int base = 0; base < mKf; base += 64) {
-        const int ik = base + lane;
-        const bool valid = ik < mKf;
-        const int part = valid ? a.part[so + ik] : -1;
-        bad |= part == -2;
-        amos_best2 rec = best2_from_keys(0xffffffffu, 0xffffffffu, nullptr, kInitDist);  // none
-        int realIdx = 0;    // this lane's keyframe feature and its angle: read here, side by side, not one by one inside the sequential loop
+    for (int base = 0; base < m1; base += 64) {
+        const int i1 = base + lane;
+        const bool valid = i1 < m1;
+        const int part = valid ? a.part[so + i1] : -1;
+        bad |= (part == -2 ? 1 : 0) | (part >= 0 && (part & kPartBadOctave) ? 2 : 0);
+        amos_best2 rec = list_record<P>(0xffffffffu, 0xffffffffu, nullptr);  // none
+        int realIdx = 0;  // this lane's side-1 feature and its angle: read here, side by side, not one by one inside the sequential loop
         float angle = 0.f;
         if (part >= 0) {
-            rec = a.best2[so + ik];
-            realIdx = kf.idx[ik];  // inside the keyframe: k_bow_best2
-            angle = kf.kps[realIdx].angle;
+            rec = a.best2[so + i1];
+            realIdx = s1.idx[i1];  // inside side 1: k_list_best2
+            angle = s1.kps[realIdx].angle;
         }
-        int acc = -1;  // this lane's query: bin << 16 | frame feature once it is accepted
+        int acc = -1;  // this lane's query: its entry of a.accepted once it is accepted
         unsigned long long todo = __ballot(part >= 0);
         nQueries += __popcll(todo);
         while (todo) {
@@ -126,72 +251,200 @@ __global__ __launch_bounds__(64) void k_bow_accept(const BowSearchArgs a)
             int bi = __builtin_amdgcn_readlane(rec.best_idx, k), bd = __builtin_amdgcn_readlane(rec.best_dist, k);
             const int si = __builtin_amdgcn_readlane(rec.second_idx, k);
             int sd = __builtin_amdgcn_readlane(rec.second_dist, k);
-            if (bi < 0) continue;  // no candidate below 256 in the whole list: none now
-            const int realIdxKF = __builtin_amdgcn_readlane(realIdx, k);
-            if (taken.either(bi, si)) {
+            if (bi < 0) continue;  // no candidate in the whole list: none now
+            const int idx1 = __builtin_amdgcn_readlane(realIdx, k);
+            const Taken tk = P::taken(taken, bi, si);
+            if (tk == kNone) continue;
+            if (tk == kSecond) { bi = si; bd = sd; }
+            if (tk == kAgain) {
                 nResearched++;
-                const int b = __builtin_amdgcn_readlane(part, k);
-                const int b0 = bow_off(a, fr, b), b1 = max(bow_off(a, fr, b + 1), b0);
-                const amos_best2 r = wave_list_best2(fr, b0, b1, load_desc(kf.desc + (size_t)realIdxKF * 32), taken, lane);
+                const int b = __builtin_amdgcn_readlane(part, k) & kPartNodeMask;
+                const int b0 = bow_off(a, s2, b), b1 = max(bow_off(a, s2, b + 1), b0);
+                const Desc q = load_desc(s1.desc + (size_t)idx1 * 32);
+                const typename P::Query pq = P::query(a, p, s1, slot1, idx1);
+                unsigned best, second;
+                wave_list_keys(b0, b1, lane, [&](int j) {
+                    const int idx2 = s2.idx[j];
+                    if ((unsigned)idx2 >= (unsigned)s2.n || taken.test(idx2)) return 0xffffffffu;
+                    int d = 0, ignored = 0;
+                    return P::candidate(a, pq, q, s2, slot2, idx2, d, ignored) ? P::key(d, j - b0) : 0xffffffffu;
+                }, best, second);
+                const amos_best2 r = list_record<P>(best, second, s2.idx + b0);
                 if (r.best_idx < 0) continue;
                 bi = r.best_idx; bd = r.best_dist; sd = r.second_dist;
             }
-            if (bd > AMOS_TH_LOW || !((float)bd < __fmul_rn(a.nnRatio, (float)sd))) continue;  // :306-309
+            if (bd > P::kMaxDist) continue;  // (on its own: a scalar comparison ends most queries)
+            if (!P::ratio_ok(a, bd, sd)) continue;
             nMatches++;
             int bin = 0;
-            if (checkOri) {  // :314-323
-                float rot = __fsub_rn(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(angle), k)), fr.kps[bi].angle);
-                if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-                bin = (int)roundf(__fmul_rn(rot, factor));
-                if (bin == AMOS_HISTO_LENGTH) bin = 0;
-                bin = min(max(bin, 0), AMOS_HISTO_LENGTH - 1);  // (the reference asserts it; an angle that is not finite lands in bin 0)
-            }
-            if (lane == k) acc = (bin << 16) | bi;
+            if (checkOri) bin = rotation_bin(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(angle), k)), s2.kps[bi].angle);
+            if (lane == k) acc = P::kMatchBySide2 ? (bin << 16) | bi : bin;
             if (lane == 0) {
-                match[bi] = realIdxKF;
+                match[P::kMatchBySide2 ? bi : idx1] = P::kMatchBySide2 ? idx1 : bi;  // (either entry is written once)
                 taken.set(bi);
                 if (checkOri) hist[bin]++;
             }
             __syncthreads();  // the bit is visible to every lane before the next query reads the bitmap
         }
-        if (valid) a.accepted[so + ik] = acc;
+        if (valid) a.accepted[so + i1] = acc;
     }
     __threadfence_block();
     __syncthreads();  // lane 0's writes to match and hist are over before the pruning reads and overwrites
     if (checkOri) {
-        // ORBmatcher::ComputeThreeMaxima (ORBmatcher.cc:1866-1908): strict comparisons, the earlier bin wins a tie
-        int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-        for (int i = 0; i < AMOS_HISTO_LENGTH; i++) {
-            const int s = hist[i];
-            if (s > max1) {
-                max3 = max2; max2 = max1; max1 = s;
-                ind3 = ind2; ind2 = ind1; ind1 = i;
-            } else if (s > max2) {
-                max3 = max2; max2 = s;
-                ind3 = ind2; ind2 = i;
-            } else if (s > max3) {
-                max3 = s; ind3 = i;
-            }
-        }
-        if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-        else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) ind3 = -1;
+        int ind1, ind2, ind3;
+        three_maxima(hist, ind1, ind2, ind3);
         int pruned = 0;
-        for (int base = 0; base < mKf; base += 64) {
-            const int ik = base + lane;
-            const int acc = ik < mKf ? a.accepted[so + ik] : -1;
-            const int bin = acc >> 16;
+        for (int base = 0; base < m1; base += 64) {
+            const int i1 = base + lane;
+            const int acc = i1 < m1 ? a.accepted[so + i1] : -1;
+            const int bin = P::kMatchBySide2 ? acc >> 16 : acc;
             const bool lose = acc >= 0 && bin != ind1 && bin != ind2 && bin != ind3;
-            if (lose) match[acc & 0xffff] = -1;
+            if (lose) match[P::kMatchBySide2 ? acc & 0xffff : s1.idx[i1]] = -1;  // (an accepted query's feature index lies inside side 1)
             pruned += __popcll(__ballot(lose));
         }
         nMatches -= pruned;
     }
-    const unsigned long long anyBad = __ballot(bad != 0);
+    const unsigned long long bad0 = __ballot(bad & 1), bad1 = __ballot(bad & 2);
     if (lane == 0) {
         amos_bow_search_stats s;
-        s.n_queries = nQueries; s.n_matches = nMatches; s.n_researched = nResearched; s.status = anyBad ? 1 : 0;
+        s.n_queries = nQueries; s.n_matches = nMatches; s.n_researched = nResearched; s.status = (bad0 ? 1 : 0) | (bad1 ? 2 : 0);
         a.stats[p] = s;
     }
+}
+
+// what the two public structs name differently
+static void fill_pair_args(ListSearchArgs &a, const amos_bow_search &s) { a.pairs1 = s.d_pairs_kf; a.pairs2 = s.d_pairs_f; a.match = s.d_match; a.uRight = nullptr; }
+static void fill_pair_args(ListSearchArgs &a, const amos_kf_pair_search &s) { a.pairs1 = s.d_pairs_1; a.pairs2 = s.d_pairs_2; a.match = s.d_match12; a.uRight = s.d_u_right; }
+
+// S: amos_bow_search or amos_kf_pair_search
+template <class S>
+static void fill_list_args(ListSearchArgs &a, const S &s)
+{
+    a.kps = s.d_kps; a.desc = s.d_desc; a.counts = s.d_counts; a.nNodes = s.d_n_nodes; a.nodeIds = s.d_node_ids; a.nodeOff = s.d_node_off;
+    a.nodeIdx = s.d_node_idx; a.hasPoint = s.d_has_point; a.stats = s.d_stats; a.capacity = s.capacity;
+    fill_pair_args(a, s);
+}
+
+// The check every batch entry makes (own: the entry's own arguments are there), the scratch of a call and the two launches; `a` comes with
+// the entry's own parameters.
+template <class P, class S>
+static int launch_pair_search(const char *name, amos_match *m, const S *s, bool own, ListSearchArgs &a)
+{
+    if (m && s) fill_list_args(a, *s);
+    if (!m || !s || !own || !a.kps || !a.desc || !a.counts || !a.nNodes || !a.nodeIds || !a.nodeOff || !a.nodeIdx || !a.pairs1 || !a.pairs2 ||
+        !a.match || !a.stats || s->n_pairs < 1 || s->capacity < 1 || s->capacity > 65536) {
+        set_error("%s: invalid argument", name);
+        return AMOS_ERR_INVALID;
+    }
+    AMOS_HIP_CHECK(hipSetDevice(m->device));
+    const size_t total = (size_t)s->n_pairs * s->capacity;
+    const size_t bytesBest = align64(sizeof(amos_best2) * total), bytesInt = align64(sizeof(int) * total);
+    int rc = grow(&m->dLocal, &m->capLocal, bytesBest + 2 * bytesInt);
+    if (rc != AMOS_OK) return rc;
+    a.best2 = (amos_best2 *)m->dLocal; a.part = (int *)(m->dLocal + bytesBest); a.accepted = (int *)(m->dLocal + bytesBest + bytesInt);
+    hipLaunchKernelGGL(k_list_best2<P>, dim3(((size_t)s->capacity * kWindowLanes + 255) / 256, s->n_pairs), dim3(256), 0, m->stream, a);
+    hipLaunchKernelGGL(k_list_accept<P>, dim3(s->n_pairs), dim3(64), 0, m->stream, a);
+    AMOS_HIP_CHECK(hipGetLastError());
+    return AMOS_OK;
+}
+
+// ---- the host forms: nv views as frame slots of one capacity, nPairs pairs of them, one upload, one batch call, one download
+
+static size_t staged_view_bytes(int nv, size_t cap) { return (size_t)nv * (cap * (sizeof(amos_keypoint) + 32 + 4 + 4 + 4 + 1 + 4) + 4 + 64 * 10) + 1024; }
+static size_t pair_match_bytes(size_t cap, int nPairs) { return align64(sizeof(int32_t) * cap * nPairs); }
+static size_t pair_out_bytes(size_t cap, int nPairs) { return pair_match_bytes(cap, nPairs) + align64(sizeof(amos_bow_search_stats) * nPairs); }
+
+// The staging arena for the views, `ownBytes` of the form's own inputs and the download; dOut for match [nPairs][cap] and stats [nPairs].
+static int host_pairs_begin(amos_match *m, int nv, size_t cap, int nPairs, size_t ownBytes)
+{
+    AMOS_HIP_CHECK(hipSetDevice(m->device));
+    int rc = stage_begin(m, staged_view_bytes(nv, cap) + ownBytes + pair_out_bytes(cap, nPairs));
+    if (rc != AMOS_OK) return rc;
+    return grow_out(m, pair_out_bytes(cap, nPairs));
+}
+
+// The views staged for ONE upload: a view's arrays at the front of its slot, zeros behind; has_point and u_right are staged when any
+// view has them (a view without gets `hpNone` / -1).  Fills s but for its pairs; the pairs' results lie in dOut.
+static void stage_views(amos_match *m, const amos_bow_view *const *views, int nv, size_t cap, int nPairs, uint8_t hpNone, bool wantRight,
+                        amos_kf_pair_search &s)
+{
+    auto all = [&](size_t per, size_t elem, auto src, auto count) {
+        const size_t o = stage_take(m, nv * per * elem);
+        std::memset(m->hStage + o, 0, nv * per * elem);
+        for (int v = 0; v < nv; v++) {
+            const void *p = src(*views[v]);
+            const size_t c = count(*views[v]);
+            if (p && c) std::memcpy(m->hStage + o + v * per * elem, p, c * elem);
+        }
+        return o;
+    };
+    auto nFeat = [](const amos_bow_view &v) { return (size_t)v.n; };
+    auto nNode = [](const amos_bow_view &v) { return (size_t)v.n_nodes; };
+    s.d_kps = (const amos_keypoint *)(m->dArena + all(cap, sizeof(amos_keypoint), [](const amos_bow_view &v) { return (const void *)v.keys; }, nFeat));
+    s.d_desc = m->dArena + all(cap, 32, [](const amos_bow_view &v) { return (const void *)v.descriptors; }, nFeat);
+    s.d_node_ids = (const uint32_t *)(m->dArena + all(cap, 4, [](const amos_bow_view &v) { return (const void *)v.node_ids; }, nNode));
+    s.d_node_off = (const int32_t *)(m->dArena + all(cap + 1, 4, [](const amos_bow_view &v) { return (const void *)v.node_off; },
+                                                     [](const amos_bow_view &v) { return v.n_nodes ? (size_t)v.n_nodes + 1 : 0; }));
+    s.d_node_idx = (const int32_t *)(m->dArena + all(cap, 4, [](const amos_bow_view &v) { return (const void *)v.node_idx; },
+                                                     [](const amos_bow_view &v) { return v.n_nodes ? (size_t)v.node_off[v.n_nodes] : 0; }));
+    bool anyPoint = false, anyRight = false;
+    for (int v = 0; v < nv; v++) { anyPoint |= views[v]->has_point != nullptr; anyRight |= views[v]->u_right != nullptr; }
+    s.d_has_point = nullptr;
+    if (anyPoint) {
+        const size_t o = all(cap, 1, [](const amos_bow_view &v) { return (const void *)v.has_point; }, nFeat);
+        for (int v = 0; v < nv; v++) if (!views[v]->has_point) std::memset(m->hStage + o + v * cap, hpNone, cap);
+        s.d_has_point = m->dArena + o;
+    }
+    s.d_u_right = nullptr;
+    if (wantRight && anyRight) {
+        const size_t o = all(cap, 4, [](const amos_bow_view &v) { return (const void *)v.u_right; }, nFeat);
+        float *h = (float *)(m->hStage + o);
+        for (int v = 0; v < nv; v++) if (!views[v]->u_right) std::fill(h + v * cap, h + (v + 1) * cap, -1.0f);
+        s.d_u_right = (const float *)(m->dArena + o);
+    }
+    std::vector<int32_t> counts(nv), nodes(nv);
+    for (int v = 0; v < nv; v++) { counts[v] = views[v]->n; nodes[v] = views[v]->n_nodes; }
+    s.d_counts = stage_input<int32_t>(m, counts.data(), sizeof(int32_t) * nv);
+    s.d_n_nodes = stage_input<int32_t>(m, nodes.data(), sizeof(int32_t) * nv);
+    s.d_match12 = (int32_t *)m->dOut;
+    s.d_stats = (amos_bow_search_stats *)((uint8_t *)m->dOut + pair_match_bytes(cap, nPairs));
+    s.n_pairs = nPairs; s.capacity = (int32_t)cap;
+}
+
+// One download of the pairs' results through the staging buffer: the first n entries of every pair's row of `match`, and the stats.
+static int download_pairs(amos_match *m, size_t cap, int nPairs, int n, int32_t *match, amos_bow_search_stats *stats)
+{
+    const size_t bytes = pair_out_bytes(cap, nPairs);
+    const uint8_t *h = m->hStage + stage_take(m, bytes);
+    AMOS_HIP_CHECK(hipMemcpyAsync((void *)h, m->dOut, bytes, hipMemcpyDeviceToHost, m->stream));
+    AMOS_HIP_CHECK(hipStreamSynchronize(m->stream));
+    for (int v = 0; v < nPairs && n; v++) std::memcpy(match + (size_t)v * n, h + sizeof(int32_t) * cap * v, sizeof(int32_t) * (size_t)n);
+    std::memcpy(stats, h + pair_match_bytes(cap, nPairs), sizeof(amos_bow_search_stats) * nPairs);
+    return AMOS_OK;
+}
+
+// The two-view forms: slot 0 against slot 1; n entries of the result go to `match`.
+template <class P>
+static int host_two_views(const char *name, amos_match *m, const amos_bow_view *v1, const amos_bow_view *v2, float nn_ratio, int check_orientation,
+                          int n, int32_t *match, amos_bow_search_stats *stats)
+{
+    if (!m || !stats || !bow_view_ok(v1) || !bow_view_ok(v2) || (n > 0 && !match)) {
+        set_error("%s: invalid argument (a NULL pointer, or a view whose node ids, offsets or feature indices are out of order or range)", name);
+        return AMOS_ERR_INVALID;
+    }
+    const size_t cap = (size_t)std::max(std::max(v1->n, v2->n), 1);
+    int rc = host_pairs_begin(m, 2, cap, 1, 0);
+    if (rc != AMOS_OK) return rc;
+    const amos_bow_view *views[2] = {v1, v2};
+    amos_kf_pair_search s;
+    stage_views(m, views, 2, cap, 1, 1, false, s);
+    const int32_t slots[2] = {0, 1};
+    s.d_pairs_1 = stage_input<int32_t>(m, slots, sizeof(slots));
+    s.d_pairs_2 = s.d_pairs_1 + 1;
+    ListSearchArgs a = {};
+    a.nnRatio = nn_ratio; a.checkOri = check_orientation;
+    if ((rc = stage_flush(m)) != AMOS_OK || (rc = launch_pair_search<P>(name, m, &s, true, a)) != AMOS_OK) return rc;
+    return download_pairs(m, cap, 1, n, match, stats);
 }
 
 }  // namespace amos
@@ -202,81 +455,73 @@ extern "C" {
 
 int amos_match_bow_batch_device(amos_match *m, const amos_bow_search *s)
 {
-    if (!m || !s || !s->d_kps || !s->d_desc || !s->d_counts || !s->d_n_nodes || !s->d_node_ids || !s->d_node_off || !s->d_node_idx ||
-        !s->d_pairs_kf || !s->d_pairs_f || !s->d_match || !s->d_stats || s->n_pairs < 1 || s->capacity < 1 || s->capacity > 65536) {
-        set_error("amos_match_bow_batch_device: invalid argument");
-        return AMOS_ERR_INVALID;
-    }
-    AMOS_HIP_CHECK(hipSetDevice(m->device));
-    const size_t total = (size_t)s->n_pairs * s->capacity;
-    const size_t bytesBest = align64(sizeof(amos_best2) * total), bytesInt = align64(sizeof(int) * total);
-    int rc = grow(&m->dLocal, &m->capLocal, bytesBest + 2 * bytesInt);
-    if (rc != AMOS_OK) return rc;
-    BowSearchArgs a;
-    a.kps = s->d_kps; a.desc = s->d_desc; a.counts = s->d_counts; a.nNodes = s->d_n_nodes; a.nodeIds = s->d_node_ids; a.nodeOff = s->d_node_off;
-    a.nodeIdx = s->d_node_idx; a.hasPoint = s->d_has_point; a.pairsKf = s->d_pairs_kf; a.pairsF = s->d_pairs_f;
-    a.match = s->d_match; a.stats = s->d_stats;
-    a.best2 = (amos_best2 *)m->dLocal; a.part = (int *)(m->dLocal + bytesBest); a.accepted = (int *)(m->dLocal + bytesBest + bytesInt);
-    a.capacity = s->capacity; a.nnRatio = s->nn_ratio; a.checkOri = s->check_orientation;
-    hipLaunchKernelGGL(k_bow_best2, dim3(((size_t)s->capacity * kWindowLanes + 255) / 256, s->n_pairs), dim3(256), 0, m->stream, a);
-    hipLaunchKernelGGL(k_bow_accept, dim3(s->n_pairs), dim3(64), 0, m->stream, a);
-    AMOS_HIP_CHECK(hipGetLastError());
-    return AMOS_OK;
+    ListSearchArgs a = {};
+    if (s) { a.nnRatio = s->nn_ratio; a.checkOri = s->check_orientation; }
+    return launch_pair_search<BowFramePolicy>("amos_match_bow_batch_device", m, s, true, a);
+}
+
+int amos_match_bow_kf_batch_device(amos_match *m, const amos_kf_pair_search *s, float nn_ratio, int check_orientation)
+{
+    ListSearchArgs a = {};
+    a.nnRatio = nn_ratio; a.checkOri = check_orientation;
+    return launch_pair_search<BowKfPolicy>("amos_match_bow_kf_batch_device", m, s, true, a);
+}
+
+int amos_match_triangulation_batch_device(amos_match *m, const amos_kf_pair_search *s, const amos_kf_geometry *d_geometry,
+                                          const float *d_scale_factors, const float *d_level_sigma2, int n_levels, int only_stereo,
+                                          int check_orientation)
+{
+    ListSearchArgs a = {};
+    a.geometry = d_geometry; a.scale = d_scale_factors; a.sigma2 = d_level_sigma2; a.nLevels = n_levels;
+    a.onlyStereo = only_stereo; a.checkOri = check_orientation;
+    const bool own = d_geometry && d_scale_factors && d_level_sigma2 && n_levels >= 1 && n_levels <= AMOS_MAX_LEVELS;
+    return launch_pair_search<TriangulationPolicy>("amos_match_triangulation_batch_device", m, s, own, a);
 }
 
 int amos_match_bow(amos_match *m, const amos_bow_view *kf, const amos_bow_view *f, float nn_ratio, int check_orientation, int32_t *matches_f,
                    amos_bow_search_stats *stats)
 {
-    if (!m || !stats || !bow_view_ok(kf) || !bow_view_ok(f) || (f->n > 0 && !matches_f)) {
-        set_error("amos_match_bow: invalid argument (a NULL pointer, or a view whose node ids, offsets or feature indices are out of order or range)");
+    return host_two_views<BowFramePolicy>("amos_match_bow", m, kf, f, nn_ratio, check_orientation, f ? f->n : 0, matches_f, stats);
+}
+
+int amos_match_bow_kf(amos_match *m, const amos_bow_view *k1, const amos_bow_view *k2, float nn_ratio, int check_orientation, int32_t *match12,
+                      amos_bow_search_stats *stats)
+{
+    return host_two_views<BowKfPolicy>("amos_match_bow_kf", m, k1, k2, nn_ratio, check_orientation, k1 ? k1->n : 0, match12, stats);
+}
+
+int amos_match_triangulation(amos_match *m, const amos_bow_view *k1, const amos_bow_view *const *k2s, int n2, const amos_kf_geometry *geometry,
+                             const float *scale_factors, const float *level_sigma2, int n_levels, int only_stereo, int check_orientation,
+                             int32_t *match12, amos_bow_search_stats *stats)
+{
+    bool ok = m && stats && k2s && n2 >= 1 && geometry && scale_factors && level_sigma2 && n_levels >= 1 && n_levels <= AMOS_MAX_LEVELS &&
+              bow_view_ok(k1) && (k1->n == 0 || match12);
+    for (int v = 0; ok && v < n2; v++) ok = bow_view_ok(k2s[v]);
+    if (!ok) {
+        set_error("amos_match_triangulation: invalid argument (a NULL pointer, n2 or n_levels out of range, or a view whose node ids, offsets or "
+                  "feature indices are out of order or range)");
         return AMOS_ERR_INVALID;
     }
-    AMOS_HIP_CHECK(hipSetDevice(m->device));
-    const size_t cap = (size_t)std::max(std::max(kf->n, f->n), 1);
-    const size_t bytesMatch = align64(sizeof(int32_t) * cap), bytesOut = bytesMatch + align64(sizeof(amos_bow_search_stats));
-    const size_t perSlot = cap * (sizeof(amos_keypoint) + 32 + 4 + 4 + 4 + 1) + 4 + 64 * 8;
-    int rc = stage_begin(m, 2 * perSlot + 1024 + bytesOut);
+    size_t cap = (size_t)std::max(k1->n, 1);
+    for (int v = 0; v < n2; v++) cap = std::max(cap, (size_t)k2s[v]->n);
+    const int nv = n2 + 1;
+    int rc = host_pairs_begin(m, nv, cap, n2, (size_t)n2 * (sizeof(amos_kf_geometry) + 8) + 2 * 64 * (AMOS_MAX_LEVELS / 16 + 1) + 256);
     if (rc != AMOS_OK) return rc;
-    rc = grow_out(m, bytesOut);
-    if (rc != AMOS_OK) return rc;
-    const amos_bow_view *views[2] = {kf, f};
-    // an array of both slots, [2][per]: the views' parts at the front of each slot, zeros behind
-    auto both = [&](size_t per, size_t elem, auto src, auto count) {
-        const size_t o = stage_take(m, 2 * per * elem);
-        std::memset(m->hStage + o, 0, 2 * per * elem);
-        for (int v = 0; v < 2; v++) {
-            const void *p = src(*views[v]);
-            const size_t c = count(*views[v]);
-            if (p && c) std::memcpy(m->hStage + o + v * per * elem, p, c * elem);
-        }
-        return m->dArena + o;
-    };
-    auto nFeat = [](const amos_bow_view &v) { return (size_t)v.n; };
-    auto nNode = [](const amos_bow_view &v) { return (size_t)v.n_nodes; };
-    amos_bow_search s;
-    s.d_kps = (const amos_keypoint *)both(cap, sizeof(amos_keypoint), [](const amos_bow_view &v) { return (const void *)v.keys; }, nFeat);
-    s.d_desc = both(cap, 32, [](const amos_bow_view &v) { return (const void *)v.descriptors; }, nFeat);
-    s.d_node_ids = (const uint32_t *)both(cap, 4, [](const amos_bow_view &v) { return (const void *)v.node_ids; }, nNode);
-    s.d_node_off = (const int32_t *)both(cap + 1, 4, [](const amos_bow_view &v) { return (const void *)v.node_off; },
-                                         [](const amos_bow_view &v) { return v.n_nodes ? (size_t)v.n_nodes + 1 : 0; });
-    s.d_node_idx = (const int32_t *)both(cap, 4, [](const amos_bow_view &v) { return (const void *)v.node_idx; },
-                                         [](const amos_bow_view &v) { return v.n_nodes ? (size_t)v.node_off[v.n_nodes] : 0; });
-    s.d_has_point = kf->has_point ? both(cap, 1, [](const amos_bow_view &v) { return (const void *)v.has_point; }, nFeat) : nullptr;
-    const int32_t counts[2] = {kf->n, f->n}, nodes[2] = {kf->n_nodes, f->n_nodes}, slots[2] = {0, 1};
-    s.d_counts = stage_input<int32_t>(m, counts, sizeof(counts));
-    s.d_n_nodes = stage_input<int32_t>(m, nodes, sizeof(nodes));
-    s.d_pairs_kf = stage_input<int32_t>(m, slots, sizeof(slots));
-    s.d_pairs_f = s.d_pairs_kf + 1;
-    uint8_t *out = (uint8_t *)m->dOut;
-    s.d_match = (int32_t *)out; s.d_stats = (amos_bow_search_stats *)(out + bytesMatch);
-    s.n_pairs = 1; s.capacity = (int32_t)cap; s.nn_ratio = nn_ratio; s.check_orientation = check_orientation;
-    if ((rc = stage_flush(m)) != AMOS_OK || (rc = amos_match_bow_batch_device(m, &s)) != AMOS_OK) return rc;
-    const uint8_t *h = m->hStage + stage_take(m, bytesOut);
-    AMOS_HIP_CHECK(hipMemcpyAsync((void *)h, out, bytesOut, hipMemcpyDeviceToHost, m->stream));
-    AMOS_HIP_CHECK(hipStreamSynchronize(m->stream));
-    if (f->n) std::memcpy(matches_f, h, sizeof(int32_t) * (size_t)f->n);
-    std::memcpy(stats, h + bytesMatch, sizeof(*stats));
-    return AMOS_OK;
+    std::vector<const amos_bow_view *> views(nv);
+    views[0] = k1;  // keyframe 1 is slot 0, staged once for all pairs
+    for (int v = 0; v < n2; v++) views[v + 1] = k2s[v];
+    amos_kf_pair_search s;
+    stage_views(m, views.data(), nv, cap, n2, 0, true, s);
+    std::vector<int32_t> slots(2 * (size_t)n2, 0);
+    for (int v = 0; v < n2; v++) slots[n2 + v] = v + 1;
+    s.d_pairs_1 = stage_input<int32_t>(m, slots.data(), sizeof(int32_t) * 2 * n2);
+    s.d_pairs_2 = s.d_pairs_1 + n2;
+    const amos_kf_geometry *dGeo = stage_input<amos_kf_geometry>(m, geometry, sizeof(amos_kf_geometry) * n2);
+    const float *dScale = stage_input<float>(m, scale_factors, sizeof(float) * n_levels);
+    const float *dSigma = stage_input<float>(m, level_sigma2, sizeof(float) * n_levels);
+    if ((rc = stage_flush(m)) != AMOS_OK ||
+        (rc = amos_match_triangulation_batch_device(m, &s, dGeo, dScale, dSigma, n_levels, only_stereo, check_orientation)) != AMOS_OK) return rc;
+    return download_pairs(m, cap, n2, k1->n, match12, stats);
 }
 
 }  // extern "C"

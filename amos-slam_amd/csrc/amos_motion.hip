@@ -136,7 +136,6 @@ __global__ __launch_bounds__(64) void k_motion_accept(const MotionArgs a)
     if (lane < AMOS_HISTO_LENGTH) hist[lane] = 0;
     for (int i = lane; i < cap; i += 64) match[i] = -1;
     __syncthreads();
-    const float factor = AMOS_HISTO_LENGTH / 360.0f;
     int nProjected = 0, nMatches = 0, nResearched = 0, bad = 0;
     for (int base = off0; base < off1; base += 64) {
         const int p = base + lane;
@@ -175,14 +174,7 @@ __global__ __launch_bounds__(64) void k_motion_accept(const MotionArgs a)
             if (bd > AMOS_TH_HIGH) continue;
             nMatches++;
             int bin = 0;
-            if (checkOri) {  // :1683-1698
-                const float angleLast = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(angle), k));
-                float rot = __fsub_rn(angleLast, fv.tk[bi].angle);
-                if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-                bin = (int)roundf(__fmul_rn(rot, factor));
-                if (bin == AMOS_HISTO_LENGTH) bin = 0;
-                bin = min(max(bin, 0), AMOS_HISTO_LENGTH - 1);  // (the reference asserts it; an angle that is not finite lands in bin 0)
-            }
+            if (checkOri) bin = rotation_bin(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(angle), k)), fv.tk[bi].angle);  // :1683-1698
             if (lane == k) acc = (bin << 16) | bi;
             if (lane == 0) {
                 match[bi] = base + k - off0;
@@ -196,22 +188,8 @@ __global__ __launch_bounds__(64) void k_motion_accept(const MotionArgs a)
     __threadfence_block();
     __syncthreads();  // lane 0's writes to match and hist are over before the pruning reads and overwrites
     if (checkOri) {
-        // ORBmatcher::ComputeThreeMaxima (ORBmatcher.cc:1866-1908): strict comparisons, the earlier bin wins a tie
-        int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-        for (int i = 0; i < AMOS_HISTO_LENGTH; i++) {
-            const int s = hist[i];
-            if (s > max1) {
-                max3 = max2; max2 = max1; max1 = s;
-                ind3 = ind2; ind2 = ind1; ind1 = i;
-            } else if (s > max2) {
-                max3 = max2; max2 = s;
-                ind3 = ind2; ind2 = i;
-            } else if (s > max3) {
-                max3 = s; ind3 = i;
-            }
-        }
-        if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-        else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) ind3 = -1;
+        int ind1, ind2, ind3;
+        three_maxima(hist, ind1, ind2, ind3);
         int pruned = 0;
         for (int base = off0; base < off1; base += 64) {
             const int p = base + lane;

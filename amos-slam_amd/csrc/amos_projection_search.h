@@ -121,6 +121,37 @@ struct TakenBitmap {
     __device__ __forceinline__ void set(int i) { w[i >> 5] |= 1u << (i & 31); }
 };
 
+// The rotation histogram of a greedy loop.  The bin of an accepted match (ORBmatcher.cc:314-323, :1683-1698): float32, every operation
+// rounded in source order.  (The reference asserts the range; an angle that is not finite lands in bin 0.)
+__device__ __forceinline__ int rotation_bin(float angle1, float angle2)
+{
+    float rot = __fsub_rn(angle1, angle2);
+    if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
+    int bin = (int)roundf(__fmul_rn(rot, AMOS_HISTO_LENGTH / 360.0f));
+    if (bin == AMOS_HISTO_LENGTH) bin = 0;
+    return min(max(bin, 0), AMOS_HISTO_LENGTH - 1);
+}
+// ORBmatcher::ComputeThreeMaxima (ORBmatcher.cc:1866-1908) over the bins' counts: strict comparisons, the earlier bin wins a tie; -1: none
+__device__ __forceinline__ void three_maxima(const int *hist, int &ind1, int &ind2, int &ind3)
+{
+    int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;  // (locals, not the references: those would be kept in memory)
+    for (int i = 0; i < AMOS_HISTO_LENGTH; i++) {
+        const int s = hist[i];
+        if (s > max1) {
+            max3 = max2; max2 = max1; max1 = s;
+            i3 = i2; i2 = i1; i1 = i;
+        } else if (s > max2) {
+            max3 = max2; max2 = s;
+            i3 = i2; i2 = i;
+        } else if (s > max3) {
+            max3 = s; i3 = i;
+        }
+    }
+    if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { i2 = -1; i3 = -1; }
+    else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) i3 = -1;
+    ind1 = i1; ind2 = i2; ind3 = i3;
+}
+
 // the whole wave searches a query's window again, against the bitmap; the record comes back wave-uniform
 __device__ __forceinline__ amos_best2 wave_research(const ProjArgs &a, const FrameView &fv, const WindowQuery &q, const TakenBitmap &taken, int lane)
 {
