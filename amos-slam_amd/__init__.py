@@ -87,6 +87,8 @@ PROTOTYPES = {
     "amos_match_local_points": (_i, (_v, _v, _v, _v, _i, _v, _i, _v, _v, _v, _i, _f, _f, _f, _f, _v, _v, _v, _v)),
     "amos_match_motion_model_batch_device": (_i, (_v, _v)),
     "amos_match_motion_model": (_i, (_v, _v, _v, _v, _i, _v, _i, _v, _v, _i, _f, _f, _f, _f, _v, _v, _v, _v)),
+    "amos_match_reloc_batch_device": (_i, (_v, _v)),
+    "amos_match_reloc": (_i, (_v, _v, _v, _i, _v, _i, _v, _v, _v, _i, _f, _f, _f, _f, _v, _v, _v, _v)),
     "amos_match_pose_optimization_batch_device": (_i, (_v, _v)),
     "amos_match_pose_optimization": (_i, (_v, _v, _v, _i, _v, _v, _v, _i, _v, _v, _i, _i, _v, _v)),
     "amos_bow_create": (_i, (_i, _v, _i, _i, _i, _i, _i, _v, _v, _v, _v, _v)),
@@ -1007,6 +1009,49 @@ class MotionSearch(C.Structure):
                 ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float)]
 
 
+class RelocPoint(C.Structure):
+    """amos_reloc_point (include/amos_frontend.h): 64 bytes; RELOC_POINT_DTYPE is the same record for numpy."""
+    _fields_ = [("pos", C.c_float * 3), ("angle", C.c_float), ("min_distance", C.c_float), ("max_distance", C.c_float), ("flags", C.c_int32),
+                ("desc", C.c_uint8 * 32), ("pad", C.c_uint8 * 4)]
+
+
+class RelocCamera(C.Structure):
+    """amos_reloc_camera: 84 bytes; RELOC_CAMERA_DTYPE is the same record for numpy."""
+    _fields_ = [("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("th", C.c_float), ("orb_dist", C.c_int32), ("check_orientation", C.c_int32), ("found_from_match", C.c_int32),
+                ("enabled", C.c_int32)]
+
+
+class RelocStats(C.Structure):
+    """amos_reloc_stats: 32 bytes; RELOC_STATS_DTYPE is the same record for numpy."""
+    _fields_ = [("n_candidates", C.c_int32), ("n_projected", C.c_int32), ("n_matches", C.c_int32), ("n_researched", C.c_int32),
+                ("n_found", C.c_int32), ("n_occupied", C.c_int32), ("status", C.c_int32), ("skipped", C.c_int32)]
+
+
+RELOC_POINT_SKIP, RELOC_POINT_HAS_OBS = 1, 2
+RELOC_POINT_DTYPE = np.dtype([("pos", "<f4", (3,)), ("angle", "<f4"), ("min_distance", "<f4"), ("max_distance", "<f4"), ("flags", "<i4"),
+                              ("desc", "u1", (32,)), ("pad", "u1", (4,))])
+RELOC_CAMERA_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"),
+                               ("th", "<f4"), ("orb_dist", "<i4"), ("check_orientation", "<i4"), ("found_from_match", "<i4"),
+                               ("enabled", "<i4")])
+RELOC_STATS_DTYPE = np.dtype([("n_candidates", "<i4"), ("n_projected", "<i4"), ("n_matches", "<i4"), ("n_researched", "<i4"),
+                              ("n_found", "<i4"), ("n_occupied", "<i4"), ("status", "<i4"), ("skipped", "<i4")])
+# amos_kf_query (include/amos_host_types.h)
+KF_QUERY_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("level", "<i4"), ("angle", "<f4"), ("desc", "u1", (32,))])
+assert (C.sizeof(RelocPoint), C.sizeof(RelocCamera), C.sizeof(RelocStats)) == (RELOC_POINT_DTYPE.itemsize, RELOC_CAMERA_DTYPE.itemsize,
+                                                                              RELOC_STATS_DTYPE.itemsize) == (64, 84, 32)
+
+
+class RelocSearch(C.Structure):
+    """amos_reloc_search (include/amos_frontend.h)."""
+    _fields_ = [("d_kps", C.c_void_p), ("d_desc", C.c_void_p), ("d_counts", C.c_void_p), ("d_cell_start", C.c_void_p), ("d_items", C.c_void_p),
+                ("d_points", C.c_void_p), ("frame_of_pair", C.c_void_p), ("point_off", C.c_void_p), ("cameras", C.c_void_p),
+                ("d_found", C.c_void_p), ("d_pose", C.c_void_p), ("scale_factors", C.c_void_p), ("d_query", C.c_void_p),
+                ("d_projected", C.c_void_p), ("d_match", C.c_void_p), ("d_stats", C.c_void_p), ("n_frames", C.c_int32), ("n_pairs", C.c_int32),
+                ("capacity", C.c_int32), ("n_levels", C.c_int32), ("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float),
+                ("max_y", C.c_float)]
+
+
 class PoseCamera(C.Structure):
     """amos_pose_camera: 68 bytes; POSE_CAMERA_DTYPE is the same record for numpy."""
     _fields_ = [("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
@@ -1289,6 +1334,41 @@ class OrbMatcher(_Handle):
         match, stats = np.full(n, -1, np.int32), np.zeros(1, MOTION_STATS_DTYPE)
         _check(self.L.amos_match_motion_model(self.h, _p(kps_un), _p(desc), _p(ur), n, _p(points), m, _p(cam), _p(sf), len(sf), *bounds,
                                               _p(query), _p(projected), _p(match), _p(stats)), "amos_match_motion_model")
+        return query, projected, match, stats[0]
+
+    def reloc_batch_device(self, d_kps, d_desc, d_counts, d_cell_start, d_items, n_frames, d_points, frame_of_pair, point_off, cameras, capacity,
+                           scale_factors, d_query, d_projected, d_match, d_stats, bounds=(0.0, 640.0, 0.0, 480.0), d_found=None, d_pose=None):
+        """Relocalization's SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (ORBmatcher.cc:1731-1863) for pairs (frame,
+        candidate keyframe) on resident frames.  frame_of_pair: n_pairs host ints; point_off: n_pairs + 1 host ints; cameras: host
+        RELOC_CAMERA_DTYPE records, one per pair; d_match [pairs][capacity] is read and written; d_pose: POSE_RESULT_DTYPE records on the
+        device, one per pair, or None (the cameras' poses).  Asynchronous on the matcher's stream."""
+        sf = np.ascontiguousarray(scale_factors, np.float32)
+        off = np.ascontiguousarray(point_off, np.int32)
+        fop = np.ascontiguousarray(frame_of_pair, np.int32)
+        cams = np.ascontiguousarray(cameras, RELOC_CAMERA_DTYPE).reshape(-1)
+        if len(off) != len(cams) + 1 or len(fop) != len(cams):
+            raise ValueError("point_off holds one entry more than cameras, frame_of_pair as many")
+        s = RelocSearch(d_kps, d_desc, d_counts, d_cell_start, d_items, d_points, fop.ctypes.data, off.ctypes.data, cams.ctypes.data, d_found,
+                        d_pose, sf.ctypes.data, d_query, d_projected, d_match, d_stats, n_frames, len(cams), capacity, len(sf), *bounds)
+        _check(self.L.amos_match_reloc_batch_device(self.h, C.byref(s)), "amos_match_reloc_batch_device")
+
+    def reloc(self, kps_un, desc, points, camera, scale_factors, match, found=None, bounds=(0.0, 640.0, 0.0, 480.0)):
+        """The same for ONE pair from host arrays (amos_match_reloc): match [n] is the frame's matches on entry (not modified); returns
+        (query, projected, match, stats)."""
+        kps_un = np.ascontiguousarray(kps_un, KP_DTYPE)
+        desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        points = np.ascontiguousarray(points, RELOC_POINT_DTYPE)
+        cam = np.ascontiguousarray(camera, RELOC_CAMERA_DTYPE).reshape(1)
+        sf = np.ascontiguousarray(scale_factors, np.float32)
+        match = np.ascontiguousarray(match, np.int32).copy()
+        fd = None if found is None else np.ascontiguousarray(found, np.uint8)
+        n, m = len(kps_un), len(points)
+        if len(desc) != n or len(match) != n or (fd is not None and len(fd) != m):
+            raise ValueError("desc and match hold one entry per keypoint, found one per point")
+        query, projected = np.zeros(m, KF_QUERY_DTYPE), np.zeros(m, np.uint8)
+        stats = np.zeros(1, RELOC_STATS_DTYPE)
+        _check(self.L.amos_match_reloc(self.h, _p(kps_un), _p(desc), n, _p(points), m, _p(fd), _p(cam), _p(sf), len(sf), *bounds, _p(query),
+                                       _p(projected), _p(match), _p(stats)), "amos_match_reloc")
         return query, projected, match, stats[0]
 
     def pose_optimization_batch_device(self, d_kps, d_counts, d_match, d_points, point_off, cameras, capacity, inv_level_sigma2, d_outlier,

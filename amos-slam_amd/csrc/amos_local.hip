@@ -71,13 +71,10 @@ __global__ __launch_bounds__(256) void k_local_frustum(const LocalArgs a)
                                                  __dmul_rn((double)PO2, (double)mp.normal[2]));
                     const float viewCos = (float)__ddiv_rn(dot, (double)dist);
                     if (!(viewCos < c.view_cos_limit)) {
-                        const float ratio = __fdiv_rn(mp.max_distance, dist);
-                        int level = 0;
-                        for (int m = 0; m < a.nLevels; m++) level += ratio > a.scale[m] ? 1 : 0;
                         q.proj_x = u; q.proj_y = v;
                         q.proj_xr = __fsub_rn(u, __fmul_rn(c.mbf, invz));
                         q.view_cos = viewCos;
-                        q.level = min(level, a.nLevels - 1);
+                        q.level = predict_scale_level(a, mp.max_distance, dist);
                         flags = 1;
                     }
                 }

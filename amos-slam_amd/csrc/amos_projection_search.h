@@ -48,6 +48,17 @@ __device__ __forceinline__ void level_window(WindowQuery &q, int octave, bool fo
     else { q.lo = octave - 1; q.hi = octave + 1; }
 }
 
+// MapPoint::PredictScale (MapPoint.cc:571-586) without a library logarithm: the number of table entries below the ratio
+// mfMaxDistance / dist, at most nLevels - 1 (a NaN ratio gives 0).  include/amos_frontend.h, "local map search", says where it differs
+// from ceil(logf(ratio) / mfLogScaleFactor).
+__device__ __forceinline__ int predict_scale_level(const ProjArgs &a, float maxDistance, float dist)
+{
+    const float ratio = __fdiv_rn(maxDistance, dist);
+    int level = 0;
+    for (int m = 0; m < a.nLevels; m++) level += ratio > a.scale[m] ? 1 : 0;
+    return min(level, a.nLevels - 1);
+}
+
 // one candidate of a window (CSR position j): its key dist << 16 | j, or none when a gate rejects it: the level window, the box, the right
 // gate (ORBmatcher.cc:132-137, :1662-1669) and the loops' strict dist < initDist.  Occupancy and bitmap filters are the caller's.
 __device__ __forceinline__ bool window_candidate(const WindowQuery &q, const FrameView &fv, int idx, int j, int initDist, unsigned &key)
@@ -167,17 +178,19 @@ __device__ __forceinline__ amos_best2 wave_research(const ProjArgs &a, const Fra
 
 inline size_t align64(size_t n) { return (n + 63) & ~(size_t)63; }
 
-// S: amos_window_search, amos_local_search or amos_motion_search
+// S: amos_window_search, amos_local_search, amos_motion_search, or amos_reloc_search (which has no right coordinates: uRight = null)
 template <class S>
-inline void fill_proj_args(ProjArgs &a, const S &s)
+inline void fill_proj_args(ProjArgs &a, const S &s, const float *uRight)
 {
-    a.kps = s.d_kps; a.desc = s.d_desc; a.counts = s.d_counts; a.cellStart = s.d_cell_start; a.items = s.d_items; a.uRight = s.d_u_right;
+    a.kps = s.d_kps; a.desc = s.d_desc; a.counts = s.d_counts; a.cellStart = s.d_cell_start; a.items = s.d_items; a.uRight = uRight;
     for (int l = 0; l < AMOS_MAX_LEVELS; l++) a.scale[l] = l < s.n_levels ? s.scale_factors[l] : 0.f;
     a.minX = s.min_x; a.maxX = s.max_x; a.minY = s.min_y; a.maxY = s.max_y;
     a.wInv = static_cast<float>(AMOS_FRAME_GRID_COLS) / static_cast<float>(s.max_x - s.min_x);  // Frame.cc:302-303
     a.hInv = static_cast<float>(AMOS_FRAME_GRID_ROWS) / static_cast<float>(s.max_y - s.min_y);
     a.capacity = s.capacity; a.nLevels = s.n_levels;
 }
+template <class S>
+inline void fill_proj_args(ProjArgs &a, const S &s) { fill_proj_args(a, s, s.d_u_right); }
 
 // what the batch entries of the point searches check alike (own: the entry's own pointers are there) -> the most points of a frame, of all
 template <class S>
@@ -219,14 +232,23 @@ inline int upload_frames(amos_match *m, const void *frames, size_t bytes)
     return AMOS_OK;
 }
 
-// The one-frame host forms of the point searches (S: amos_local_search, amos_motion_search): ONE frame of n features and n_points points,
+// The one-frame host forms of the point searches (S: amos_local_search, amos_motion_search, amos_reloc_search): ONE frame of n features and n_points points,
 // host arrays in and out.  Lays out the result buffer (query records, one byte per point, match, stats: the download; then the grid),
 // computes Frame::PosInGrid, stages the frame's arrays and fills the fields of S that both kinds have; own(s, d_flag, zeros) stages the entry's
 // own inputs (ownBytes of them) and fills its own fields; then one upload, AssignFeaturesToGrid, the batch form, one download, the copy-out.
+// match_in (amos_reloc_search: d_match is read too): `match` travels up with the inputs and is copied into the result buffer first.
+// (amos_reloc_search has no d_u_right and counts pairs beside frames: the two setters below are what differs in its layout)
+template <class S>
+inline auto set_u_right(S &s, const float *p) -> decltype((void)s.d_u_right) { s.d_u_right = p; }
+inline void set_u_right(amos_reloc_search &, const float *) {}
+template <class S>
+inline auto set_n_frames(S &s, int) -> decltype((void)s.n_pairs) { s.n_frames = 1; s.n_pairs = 1; }
+template <class S>
+inline void set_n_frames(S &s, long) { s.n_frames = 1; }
 template <class S, class Own>
 inline int one_frame_search(amos_match *m, int (*batch)(amos_match *, const S *), const amos_keypoint *kps_un, const uint8_t *desc,
                             const float *u_right, int n, int n_points, size_t ownBytes, const float *scale_factors, int n_levels, float min_x,
-                            float max_x, float min_y, float max_y, void *query, uint8_t *flag, int32_t *match, void *stats, Own own)
+                            float max_x, float min_y, float max_y, void *query, uint8_t *flag, int32_t *match, void *stats, Own own, bool match_in = false)
 {
     S s;
     const size_t querySize = sizeof(*s.d_query), statsSize = sizeof(*s.d_stats);
@@ -236,7 +258,7 @@ inline int one_frame_search(amos_match *m, int (*batch)(amos_match *, const S *)
     const size_t oFlag = align64(querySize * np1), oMatch = oFlag + align64(np1), oStats = oMatch + align64(sizeof(int32_t) * (size_t)cap),
                  oEnd = oStats + align64(statsSize), oItems = oEnd + align64(sizeof(int32_t) * (kGridCells + 1)),
                  oAll = oItems + align64(sizeof(int32_t) * (size_t)cap);
-    int rc = stage_begin(m, (size_t)cap * (sizeof(amos_keypoint) + 32 + 4 + 4) + 64 + ownBytes + oEnd);
+    int rc = stage_begin(m, (size_t)cap * (sizeof(amos_keypoint) + 32 + 4 + 4) + 64 + ownBytes + oEnd + (match_in ? align64(sizeof(int32_t) * (size_t)cap) : 0));
     if (rc != AMOS_OK) return rc;
     rc = grow_out(m, oAll);
     if (rc != AMOS_OK) return rc;
@@ -253,17 +275,22 @@ inline int one_frame_search(amos_match *m, int (*batch)(amos_match *, const S *)
     uint8_t *out = (uint8_t *)m->dOut;
     s.d_kps = stage_input<amos_keypoint>(m, n ? (const void *)kps_un : zeros.data(), sizeof(amos_keypoint) * (size_t)cap);
     s.d_desc = stage_input<uint8_t>(m, n ? desc : zeros.data(), (size_t)cap * 32);
-    s.d_u_right = u_right && n ? stage_input<float>(m, u_right, sizeof(float) * (size_t)cap) : nullptr;
+    set_u_right(s, u_right && n ? stage_input<float>(m, u_right, sizeof(float) * (size_t)cap) : nullptr);
+    const int32_t freeFeature = -1;  // (cap is 1 when n is 0)
+    const int32_t *dMatchIn = match_in ? stage_input<int32_t>(m, n ? match : &freeFeature, sizeof(int32_t) * (size_t)cap) : nullptr;
     const int32_t *dCell = stage_input<int32_t>(m, cell.data(), sizeof(int32_t) * (size_t)cap);
     s.d_counts = stage_input<int32_t>(m, &count, sizeof(count));
     s.d_cell_start = (int32_t *)(out + oEnd); s.d_items = (int32_t *)(out + oItems);
     s.point_off = off; s.scale_factors = scale_factors;
     s.d_query = (decltype(s.d_query))out; s.d_match = (int32_t *)(out + oMatch); s.d_stats = (decltype(s.d_stats))(out + oStats);
-    s.n_frames = 1; s.capacity = cap; s.n_levels = n_levels;
+    set_n_frames(s, 0);
+    s.capacity = cap; s.n_levels = n_levels;
     s.min_x = min_x; s.max_x = max_x; s.min_y = min_y; s.max_y = max_y;
     own(s, out + oFlag, zeros.data());
     int32_t *dStart = (int32_t *)(out + oEnd), *dItems = (int32_t *)(out + oItems);
-    if ((rc = stage_flush(m)) != AMOS_OK || (rc = amos_frame_grid_build_batch_device(m, dCell, s.d_counts, 1, cap, dStart, dItems)) != AMOS_OK ||
+    if ((rc = stage_flush(m)) != AMOS_OK) return rc;
+    if (dMatchIn) AMOS_HIP_CHECK(hipMemcpyAsync(out + oMatch, dMatchIn, sizeof(int32_t) * (size_t)cap, hipMemcpyDeviceToDevice, m->stream));
+    if ((rc = amos_frame_grid_build_batch_device(m, dCell, s.d_counts, 1, cap, dStart, dItems)) != AMOS_OK ||
         (rc = batch(m, &s)) != AMOS_OK) return rc;
     const uint8_t *h = m->hStage + stage_take(m, oEnd);
     AMOS_HIP_CHECK(hipMemcpyAsync((void *)h, out, oEnd, hipMemcpyDeviceToHost, m->stream));

@@ -592,6 +592,108 @@ int amos_match_pose_optimization(amos_match *m, const amos_keypoint *kps_un, con
                                  const uint8_t *has_obs, int n_points, const amos_pose_camera *camera, const float *inv_level_sigma2, int n_levels,
                                  int clear_outliers, uint8_t *outlier, amos_pose_result *result);
 
+/* ---------------------------------------------------------------- relocalisation search ----- */
+
+/* Step 6 of Tracking::Relocalization's candidate loop (Tracking.cc:2732, :2756): ORBmatcher::SearchByProjection(CurrentFrame, pKF,
+ * sAlreadyFound, th, ORBdist) (ORBmatcher.cc:1731-1863) for a batch of PAIRS, one (current frame, candidate keyframe) combination each.
+ * Several pairs may name the same resident frame (frame_of_pair): its keypoints, descriptors and grid are read, never written.  Every pair
+ * has its own d_match row ([pairs][capacity], read and written), its own point range, camera and stats.  The index of a point in its
+ * pair's list is the keyframe feature index -- what SearchByBoW(pKF, F) writes into d_match -- so the matches of both index one list and
+ * the pose kernel reads it with point_stride = 64, flags_offset = 24, has_obs_bit = AMOS_RELOC_POINT_HAS_OBS.
+ *
+ * Already found (sAlreadyFound.count(pMP)): point j is found when d_found[j] != 0 (d_found may be NULL), and, with found_from_match, also
+ * when some feature i < count has d_match[i] == j on entry (the rebuild of Tracking.cc:2752-2755).  A list that holds one MapPoint* at two
+ * indices must be marked by the caller at both: the library sees indices, not pointers.
+ *
+ * Arithmetic (PARITY UNPINNED, like the other searches): float32, every operation rounded, nothing fused, except
+ *   x3Dc = Rcw * P + tcw     one gemm per row: ((R0 P0 + R1 P1) + R2 P2) + t in double, one rounding to float
+ *   invzc = (float) (1.0 / (double) zc).  There is NO invzc < 0 test: a point behind the camera is projected and searched (:1762-1770)
+ *   u = ((fx * xc) * invzc) + cx;  v alike
+ *   a u or v that is not finite is skipped and sets bit 0 (value 1) of the pair's status (the reference goes on to convert it to int)
+ *   u < min_x || u > max_x || v < min_y || v > max_y is skipped
+ *   PO = P - Ow;  dist3D = (float) sqrt(((double) PO0^2 + (double) PO1^2) + (double) PO2^2)
+ *   dist3D < 0.8f * min_distance || dist3D > 1.2f * max_distance is skipped (both strict)
+ *   level = number of m in [0, n_levels) with max_distance / dist3D > scale_factors[m], at most n_levels - 1: the table-count form of
+ *   MapPoint::PredictScale of the local map search.  The ratio is mfMaxDistance / dist3D (MapPoint.cc:576): the 1.2f of
+ *   GetMaxDistanceInvariance() enters the range test above, not the ratio.
+ * Pose: with d_pose == NULL the camera's Rcw / tcw, and Ow = -Rcw^T tcw on the host, one gemm per row in double, one rounding (as
+ * amos_pose_result.Ow); else pair k reads Tcw and Ow of d_pose[k] on the device, so PoseOptimization -> search -> PoseOptimization runs
+ * without a host step.
+ * Search: radius th * scale_factors[level]; levels level - 1 .. level + 1; no right gate.  A feature with d_match[i] >= 0, on entry or set
+ * by an earlier point of this call, is skipped; best candidate only, the first wins ties; accepted when bestDist <= orb_dist (0 .. 255: the
+ * reference starts from bestDist = 256 with bestIdx2 = -1, a larger value would accept index -1); no ratio test.
+ * Rotation consistency (check_orientation): rotation_bin(point.angle, keysUn[best].angle), one entry per accepted point; after
+ * ComputeThreeMaxima every entry of a losing bin sets its feature to -1 and lowers n_matches.  Only features matched by this call can be
+ * cleared; the matches present on entry are never touched. */
+typedef struct amos_reloc_point {      /* keyframe feature i of the candidate as the search reads it: 64 bytes */
+    float pos[3];                      /* pKF->GetMapPoint(i)->GetWorldPos() */
+    float angle;                       /* pKF->mvKeysUn[i].angle */
+    float min_distance, max_distance;  /* mfMinDistance, mfMaxDistance (raw: the 0.8f / 1.2f factors are applied on the device) */
+    int32_t flags;                     /* bit 0: skip (no point, or isBad()); bit 1: Observations() > 0 (for the pose kernel; the search does not read it) */
+    uint8_t desc[32];                  /* pMP->GetDescriptor() */
+    uint8_t pad[4];
+} amos_reloc_point;
+#define AMOS_RELOC_POINT_SKIP 1
+#define AMOS_RELOC_POINT_HAS_OBS 2
+
+typedef struct amos_reloc_camera {     /* per pair: 84 bytes */
+    float Rcw[9], tcw[3];              /* CurrentFrame.mTcw, rotation row-major (not read when d_pose is given) */
+    float fx, fy, cx, cy;
+    float th;                          /* 10 / 3 in Tracking.cc:2732, :2756: finite and > 0 */
+    int32_t orb_dist;                  /* 100 / 64: 0 .. 255 */
+    int32_t check_orientation;         /* mbCheckOrientation */
+    int32_t found_from_match;          /* 1: a point that d_match names on entry is found */
+    int32_t enabled;                   /* 0: the pair's work-groups return at once; d_match is untouched, the stats are zero with skipped = 1 */
+} amos_reloc_camera;
+
+typedef struct amos_reloc_stats {      /* 32 bytes */
+    int32_t n_candidates;              /* points neither skipped nor found */
+    int32_t n_projected;               /* points that reached GetFeaturesInArea */
+    int32_t n_matches;                 /* the return value: nadditional */
+    int32_t n_researched;              /* points whose best two among the features free on entry were both taken at their turn */
+    int32_t n_found;                   /* points without the skip bit that were found */
+    int32_t n_occupied;                /* features i < count with d_match[i] >= 0 on entry */
+    int32_t status;                    /* bit 0: a projection was not finite */
+    int32_t skipped;                   /* 1: enabled was 0 */
+} amos_reloc_stats;
+
+struct amos_kf_query;                  /* include/amos_host_types.h: u, v, level, angle, descriptor */
+struct amos_pose_result;
+
+typedef struct amos_reloc_search {
+    const amos_keypoint *d_kps;        /* [frames][capacity]: the current frames' undistorted keypoints (mvKeysUn) */
+    const uint8_t *d_desc;             /* [frames][capacity][32] */
+    const int32_t *d_counts;           /* [frames] */
+    const int32_t *d_cell_start;       /* [frames][64*48+1]       (amos_frame_grid_build_batch_device) */
+    const int32_t *d_items;            /* [frames][capacity] */
+    const amos_reloc_point *d_points;  /* pair k owns points [point_off[k], point_off[k + 1]) */
+    const int32_t *frame_of_pair;      /* host, n_pairs entries in [0, n_frames) */
+    const int32_t *point_off;          /* host, n_pairs + 1 entries, ascending from >= 0 */
+    const amos_reloc_camera *cameras;  /* host, n_pairs entries */
+    const uint8_t *d_found;            /* one byte per point, or NULL */
+    const struct amos_pose_result *d_pose; /* [pairs], or NULL: the cameras' poses */
+    const float *scale_factors;        /* host, n_levels entries (mvScaleFactors) */
+    struct amos_kf_query *d_query;     /* out, one per point of an enabled pair: angle and descriptor always, u / v / level where projected (else 0) */
+    uint8_t *d_projected;              /* out, one per point of an enabled pair: 1 where the point reached GetFeaturesInArea */
+    int32_t *d_match;                  /* in / out, [pairs][capacity]: index of the matched point inside the pair's own list, or -1 */
+    amos_reloc_stats *d_stats;         /* out, [pairs] */
+    int32_t n_frames, n_pairs, capacity, n_levels;
+    float min_x, max_x, min_y, max_y;  /* Frame::mnMinX .. mnMaxY */
+} amos_reloc_search;
+/* Asynchronous on the matcher's stream (the three host arrays and the table are consumed before the call returns).  Three launches
+ * (projection, window search, acceptance), and one more ahead of them when a pair has found_from_match.  AMOS_ERR_INVALID, before the device
+ * is touched, for a NULL handle or required pointer, n_pairs < 1, n_frames < 1, a capacity outside 1 .. 65536, n_levels outside
+ * 1 .. AMOS_MAX_LEVELS, a frame_of_pair outside [0, n_frames), a point_off that descends or starts below 0, empty bounds, an orb_dist
+ * outside 0 .. 255 or a th that is not finite or not positive. */
+int amos_match_reloc_batch_device(amos_match *m, const amos_reloc_search *s);
+/* The host form for a C++ drop-in (amos-slam_amd/host/FrameRelocalization.h): ONE pair, host arrays in and out, synchronous: one upload (the
+ * grid cells of Frame::PosInGrid are computed on the way), AssignFeaturesToGrid and the launches on the device, one download.  found
+ * [n_points] or NULL; query, projected [n_points]; match [n] is read and written in place. */
+int amos_match_reloc(amos_match *m, const amos_keypoint *kps_un, const uint8_t *desc, int n, const amos_reloc_point *points, int n_points,
+                     const uint8_t *found, const amos_reloc_camera *camera, const float *scale_factors, int n_levels, float min_x,
+                     float max_x, float min_y, float max_y, struct amos_kf_query *query, uint8_t *projected, int32_t *match /* in/out [n] */,
+                     amos_reloc_stats *stats);
+
 /* ---------------------------------------------------------------- bag of words --------------- */
 
 /* Tracking::TrackReferenceKeyFrame's two steps (Tracking.cc:1736-1794) for resident frames: Frame::ComputeBoW (Frame.cc:1033-1049), which is
