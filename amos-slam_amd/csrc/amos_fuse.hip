@@ -9,7 +9,6 @@
 // of its window; the group's first lane writes the record.  The arithmetic is defined in include/amos_frontend.h, "fuse search".
 #include "amos_common.h"
 #include "amos_projection_search.h"
-#include "amos_scene_flow.h"  // gemm_row
 
 #include "../../include/amos_host_types.h"  // amos_window_query, amos_frame_view
 
@@ -58,26 +57,18 @@ __global__ __launch_bounds__(256) void k_fuse(const FuseArgs a)
         mp = a.points + pr.first + i;
         const bool skipped = (mp->flags & AMOS_MAP_POINT_SKIP) || (a.skip && a.skip[o]);
         if (!skipped) {
-            const float P0 = mp->pos[0], P1 = mp->pos[1], P2 = mp->pos[2];
-            const float PcX = gemm_row(c.Rcw, 0, P0, P1, P2, c.tcw[0]);
-            const float PcY = gemm_row(c.Rcw, 1, P0, P1, P2, c.tcw[1]);
-            const float PcZ = gemm_row(c.Rcw, 2, P0, P1, P2, c.tcw[2]);
+            float PcX, PcY, PcZ;
+            camera_point(c.Rcw, c.tcw, mp->pos, PcX, PcY, PcZ);
             if (!(PcZ < 0.0f)) {
                 const float invz = __fdiv_rn(1.0f, PcZ);
                 const float u = __fadd_rn(__fmul_rn(c.fx, __fmul_rn(PcX, invz)), c.cx);
                 const float v = __fadd_rn(__fmul_rn(c.fy, __fmul_rn(PcY, invz)), c.cy);
                 if (u >= a.minX && u < a.maxX && v >= a.minY && v < a.maxY) {  // KeyFrame::IsInImage: a NaN or an infinity fails it
-                    const float PO0 = __fsub_rn(P0, c.Ow[0]), PO1 = __fsub_rn(P1, c.Ow[1]), PO2 = __fsub_rn(P2, c.Ow[2]);
-                    const double n2 = __dadd_rn(__dadd_rn(__dmul_rn((double)PO0, (double)PO0), __dmul_rn((double)PO1, (double)PO1)),
-                                                __dmul_rn((double)PO2, (double)PO2));
-                    const float dist = (float)__dsqrt_rn(n2);
-                    if (!(dist < __fmul_rn(0.8f, mp->min_distance) || dist > __fmul_rn(1.2f, mp->max_distance))) {
-                        const double dot = __dadd_rn(__dadd_rn(__dmul_rn((double)PO0, (double)mp->normal[0]), __dmul_rn((double)PO1, (double)mp->normal[1])),
-                                                     __dmul_rn((double)PO2, (double)mp->normal[2]));
-                        if (!(dot < __dmul_rn(0.5, (double)dist))) {
-                            const float ratio = __fdiv_rn(mp->max_distance, dist);
-                            for (int m = 0; m < a.nLevels; m++) level += ratio > a.scale[m] ? 1 : 0;
-                            level = min(level, a.nLevels - 1);
+                    float PO[3];
+                    const float dist = point_offset(mp->pos, c.Ow, PO);
+                    if (in_distance_band(dist, mp->min_distance, mp->max_distance)) {
+                        if (!(normal_dot(PO, mp->normal) < __dmul_rn(0.5, (double)dist))) {
+                            level = predict_scale_level(a, mp->max_distance, dist);
                             q.u = u; q.v = v;
                             q.ur = a.chi2 ? __fsub_rn(u, __fmul_rn(c.mbf, invz)) : 0.f;
                             q.lo = level - 1; q.hi = level;
@@ -120,8 +111,7 @@ __global__ __launch_bounds__(256) void k_fuse(const FuseArgs a)
         amos_window_query w;
         w.u = q.u; w.v = q.v; w.ur = q.ur;
         w.level = level; w.src = i;
-#pragma unroll
-        for (int k = 0; k < 8; k++) reinterpret_cast<uint32_t *>(w.desc)[k] = reinterpret_cast<const uint32_t *>(mp->desc)[k];
+        copy_desc(w.desc, mp->desc);
         a.query[o] = w;
         a.inView[o] = inView ? 1 : 0;
         a.bestIdx[o] = bestIdx;
@@ -181,7 +171,7 @@ int amos_match_fuse_batch_device(amos_match *m, const amos_fuse_search *s)
     a.chi2 = s->mode == AMOS_FUSE_LOCAL ? 1 : 0; a.maxDist = s->max_dist;
     AMOS_HIP_CHECK(hipMemsetAsync(s->d_stats, 0, sizeof(amos_fuse_stats) * (size_t)s->n_pairs, m->stream));
     if (maxPoints > 0) {
-        hipLaunchKernelGGL(k_fuse, dim3(((size_t)maxPoints * kWindowLanes + 255) / 256, s->n_pairs), dim3(256), 0, m->stream, a);
+        hipLaunchKernelGGL(k_fuse, window_grid(maxPoints, s->n_pairs), dim3(256), 0, m->stream, a);
         AMOS_HIP_CHECK(hipGetLastError());
     }
     return AMOS_OK;
@@ -221,7 +211,7 @@ int amos_match_fuse(amos_match *m, const amos_frame_view *kfs, int n_kfs, const 
     if (rc != AMOS_OK) return rc;
     rc = grow_out(m, oAll);
     if (rc != AMOS_OK) return rc;
-    // every keyframe at the front of its slot of `cap` features, zeros behind; Frame::PosInGrid (Frame.cc:1007-1030) on the way
+    // every keyframe at the front of its slot of `cap` features, zeros behind; pos_in_grid on the way
     const float wInv = static_cast<float>(AMOS_FRAME_GRID_COLS) / static_cast<float>(kfs[0].max_x - kfs[0].min_x);
     const float hInv = static_cast<float>(AMOS_FRAME_GRID_ROWS) / static_cast<float>(kfs[0].max_y - kfs[0].min_y);
     const size_t hKps = stage_take(m, nk * cap * sizeof(amos_keypoint)), hDesc = stage_take(m, nk * cap * 32), hCell = stage_take(m, nk * cap * 4);
@@ -239,10 +229,7 @@ int amos_match_fuse(amos_match *m, const amos_frame_view *kfs, int n_kfs, const 
         std::memcpy(m->hStage + hKps + k * cap * sizeof(amos_keypoint), v.keys_un, sizeof(amos_keypoint) * (size_t)v.n);
         std::memcpy(m->hStage + hDesc + k * cap * 32, v.descriptors, 32 * (size_t)v.n);
         if (right && v.u_right) std::memcpy(right + k * cap, v.u_right, 4 * (size_t)v.n);
-        for (int i = 0; i < v.n; i++) {
-            const int px = (int)roundf((v.keys_un[i].x - v.min_x) * wInv), py = (int)roundf((v.keys_un[i].y - v.min_y) * hInv);
-            if (px >= 0 && px < AMOS_FRAME_GRID_COLS && py >= 0 && py < AMOS_FRAME_GRID_ROWS) cell[k * cap + i] = px * AMOS_FRAME_GRID_ROWS + py;
-        }
+        for (int i = 0; i < v.n; i++) cell[k * cap + i] = pos_in_grid(v.keys_un[i].x, v.keys_un[i].y, v.min_x, v.min_y, wInv, hInv);
     }
     const std::vector<uint8_t> zeros(sizeof(amos_map_point), 0);
     uint8_t *out = (uint8_t *)m->dOut;

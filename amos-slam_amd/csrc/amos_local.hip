@@ -7,7 +7,6 @@
 // greedy loop over those records).  The arithmetic is defined in include/amos_frontend.h, "local map search".
 #include "amos_common.h"
 #include "amos_projection_search.h"
-#include "amos_scene_flow.h"  // gemm_row
 
 #include "../../include/amos_host_types.h"  // amos_map_query
 
@@ -48,28 +47,20 @@ __global__ __launch_bounds__(256) void k_local_frustum(const LocalArgs a)
     q.proj_x = q.proj_y = q.proj_xr = q.view_cos = 0.f;
     q.level = 0;
     q.has_obs = (mp.flags & AMOS_MAP_POINT_HAS_OBS) ? 1 : 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) reinterpret_cast<uint32_t *>(q.desc)[k] = reinterpret_cast<const uint32_t *>(mp.desc)[k];
+    copy_desc(q.desc, mp.desc);
     int flags = 0;
     if (!(mp.flags & AMOS_MAP_POINT_SKIP)) {
-        const float P0 = mp.pos[0], P1 = mp.pos[1], P2 = mp.pos[2];
-        const float PcX = gemm_row(c.Rcw, 0, P0, P1, P2, c.tcw[0]);
-        const float PcY = gemm_row(c.Rcw, 1, P0, P1, P2, c.tcw[1]);
-        const float PcZ = gemm_row(c.Rcw, 2, P0, P1, P2, c.tcw[2]);
+        float PcX, PcY, PcZ;
+        camera_point(c.Rcw, c.tcw, mp.pos, PcX, PcY, PcZ);
         if (!(PcZ < 0.0f)) {
             const float invz = __fdiv_rn(1.0f, PcZ);
             const float u = __fadd_rn(__fmul_rn(__fmul_rn(c.fx, PcX), invz), c.cx);
             const float v = __fadd_rn(__fmul_rn(__fmul_rn(c.fy, PcY), invz), c.cy);
-            if (!(isfinite(u) && isfinite(v))) flags = 2;
-            else if (!(u < a.minX || u > a.maxX) && !(v < a.minY || v > a.maxY)) {
-                const float PO0 = __fsub_rn(P0, c.Ow[0]), PO1 = __fsub_rn(P1, c.Ow[1]), PO2 = __fsub_rn(P2, c.Ow[2]);
-                const double n2 = __dadd_rn(__dadd_rn(__dmul_rn((double)PO0, (double)PO0), __dmul_rn((double)PO1, (double)PO1)),
-                                            __dmul_rn((double)PO2, (double)PO2));
-                const float dist = (float)__dsqrt_rn(n2);
-                if (!(dist < __fmul_rn(0.8f, mp.min_distance) || dist > __fmul_rn(1.2f, mp.max_distance))) {
-                    const double dot = __dadd_rn(__dadd_rn(__dmul_rn((double)PO0, (double)mp.normal[0]), __dmul_rn((double)PO1, (double)mp.normal[1])),
-                                                 __dmul_rn((double)PO2, (double)mp.normal[2]));
-                    const float viewCos = (float)__ddiv_rn(dot, (double)dist);
+            if (pixel_in_bounds(a, u, v, flags)) {
+                float PO[3];
+                const float dist = point_offset(mp.pos, c.Ow, PO);
+                if (in_distance_band(dist, mp.min_distance, mp.max_distance)) {
+                    const float viewCos = (float)__ddiv_rn(normal_dot(PO, mp.normal), (double)dist);
                     if (!(viewCos < c.view_cos_limit)) {
                         q.proj_x = u; q.proj_y = v;
                         q.proj_xr = __fsub_rn(u, __fmul_rn(c.mbf, invz));
@@ -198,8 +189,8 @@ int amos_match_local_points_batch_device(amos_match *m, const amos_local_search 
     int rc = check_point_search("amos_match_local_points_batch_device", m, s, s && s->d_occupied && s->d_in_view, &maxPoints, &total);
     if (rc != AMOS_OK) return rc;
     AMOS_HIP_CHECK(hipSetDevice(m->device));
-    const size_t bytesFrames = align64(sizeof(LocalFrame) * (size_t)s->n_frames), bytesBest = align64(sizeof(amos_best2) * total);
-    rc = grow(&m->dLocal, &m->capLocal, bytesFrames + bytesBest + align64(total));
+    const PointScratch l = point_scratch(sizeof(LocalFrame) * (size_t)s->n_frames, total, false, 1);
+    rc = grow(&m->dLocal, &m->capLocal, l.bytes);
     if (rc != AMOS_OK) return rc;
     std::vector<LocalFrame> frames((size_t)s->n_frames);
     for (int f = 0; f < s->n_frames; f++) frames[f] = LocalFrame{s->cameras[f], s->point_off[f], s->point_off[f + 1]};
@@ -209,10 +200,10 @@ int amos_match_local_points_batch_device(amos_match *m, const amos_local_search 
     fill_proj_args(a, *s);
     a.points = s->d_points; a.frames = (const LocalFrame *)m->dLocal; a.occupied = s->d_occupied;
     a.query = s->d_query; a.inView = s->d_in_view; a.match = s->d_match; a.stats = s->d_stats;
-    a.best2 = (amos_best2 *)(m->dLocal + bytesFrames); a.flags = m->dLocal + bytesFrames + bytesBest;
+    a.best2 = (amos_best2 *)(m->dLocal + l.best2); a.flags = m->dLocal + l.flags;
     if (maxPoints > 0) {
         hipLaunchKernelGGL(k_local_frustum, dim3((maxPoints + 255) / 256, s->n_frames), dim3(256), 0, m->stream, a);
-        hipLaunchKernelGGL(k_local_window_best2, dim3((maxPoints * kWindowLanes + 255) / 256, s->n_frames), dim3(256), 0, m->stream, a);
+        hipLaunchKernelGGL(k_local_window_best2, window_grid(maxPoints, s->n_frames), dim3(256), 0, m->stream, a);
     }
     hipLaunchKernelGGL(k_local_accept, dim3(s->n_frames), dim3(64), 0, m->stream, a);
     AMOS_HIP_CHECK(hipGetLastError());

@@ -8,7 +8,6 @@
 // of a frame whose first search found enough returns at once.  The arithmetic is defined in include/amos_frontend.h, "motion-model search".
 #include "amos_common.h"
 #include "amos_projection_search.h"
-#include "amos_scene_flow.h"  // gemm_row
 
 #include "../../include/amos_host_types.h"  // amos_proj_query
 
@@ -53,20 +52,16 @@ __global__ __launch_bounds__(256) void k_motion_project(const MotionArgs a)
     q.octave = lp.octave;
     q.angle = lp.angle;
     q.has_obs = (lp.flags & AMOS_LAST_POINT_HAS_OBS) ? 1 : 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) reinterpret_cast<uint32_t *>(q.desc)[k] = reinterpret_cast<const uint32_t *>(lp.desc)[k];
+    copy_desc(q.desc, lp.desc);
     int flags = 0;
     if (!(lp.flags & AMOS_LAST_POINT_SKIP)) {
-        const float P0 = lp.pos[0], P1 = lp.pos[1], P2 = lp.pos[2];
-        const float xc = gemm_row(c.Rcw, 0, P0, P1, P2, c.tcw[0]);
-        const float yc = gemm_row(c.Rcw, 1, P0, P1, P2, c.tcw[1]);
-        const float zc = gemm_row(c.Rcw, 2, P0, P1, P2, c.tcw[2]);
+        float xc, yc, zc;
+        camera_point(c.Rcw, c.tcw, lp.pos, xc, yc, zc);
         const float invzc = (float)__ddiv_rn(1.0, (double)zc);
         if (!(invzc < 0)) {
             const float u = __fadd_rn(__fmul_rn(__fmul_rn(c.fx, xc), invzc), c.cx);
             const float v = __fadd_rn(__fmul_rn(__fmul_rn(c.fy, yc), invzc), c.cy);
-            if (!(isfinite(u) && isfinite(v))) flags = 2;
-            else if (!(u < a.minX || u > a.maxX) && !(v < a.minY || v > a.maxY)) {
+            if (pixel_in_bounds(a, u, v, flags)) {
                 if (lp.octave < 0 || lp.octave >= a.nLevels) flags = 4;
                 else {
                     q.u = u; q.v = v; q.invz = invzc;
@@ -223,9 +218,8 @@ int amos_match_motion_model_batch_device(amos_match *m, const amos_motion_search
     int rc = check_point_search("amos_match_motion_model_batch_device", m, s, s && s->d_projected, &maxPoints, &total);
     if (rc != AMOS_OK) return rc;
     AMOS_HIP_CHECK(hipSetDevice(m->device));
-    const size_t bytesFrames = align64(sizeof(MotionFrame) * (size_t)s->n_frames), bytesBest = align64(sizeof(amos_best2) * total),
-                 bytesAcc = align64(sizeof(int) * total);
-    rc = grow(&m->dLocal, &m->capLocal, bytesFrames + bytesBest + bytesAcc + align64(total));
+    const PointScratch l = point_scratch(sizeof(MotionFrame) * (size_t)s->n_frames, total, true, 1);
+    rc = grow(&m->dLocal, &m->capLocal, l.bytes);
     if (rc != AMOS_OK) return rc;
     std::vector<MotionFrame> frames((size_t)s->n_frames);
     bool retry = false;
@@ -235,7 +229,7 @@ int amos_match_motion_model_batch_device(amos_match *m, const amos_motion_search
         // :1584-1599.  twc = -Rcw^T tcw and tlc = Rlw twc + tlw are one gemm each: double accumulation, one rounding
         const amos_motion_camera &c = fr.cam;
         float twc[3];
-        for (int k = 0; k < 3; k++) twc[k] = (float)(-((double)c.Rcw[k] * c.tcw[0] + (double)c.Rcw[3 + k] * c.tcw[1] + (double)c.Rcw[6 + k] * c.tcw[2]));
+        camera_centre(c.Rcw, c.tcw, twc);
         const float tlcZ = (float)((double)c.Rlw[6] * twc[0] + (double)c.Rlw[7] * twc[1] + (double)c.Rlw[8] * twc[2] + (double)c.tlw[2]);
         const bool bForward = tlcZ > c.mb && !c.mono, bBackward = -tlcZ > c.mb && !c.mono;
         fr.flags = (bForward ? 1 : 0) | (bBackward ? 2 : 0);
@@ -247,14 +241,12 @@ int amos_match_motion_model_batch_device(amos_match *m, const amos_motion_search
     fill_proj_args(a, *s);
     a.points = s->d_points; a.frames = (const MotionFrame *)m->dLocal;
     a.query = s->d_query; a.projected = s->d_projected; a.match = s->d_match; a.stats = s->d_stats;
-    a.best2 = (amos_best2 *)(m->dLocal + bytesFrames); a.accepted = (int *)(m->dLocal + bytesFrames + bytesBest);
-    a.flags = m->dLocal + bytesFrames + bytesBest + bytesAcc;
+    a.best2 = (amos_best2 *)(m->dLocal + l.best2); a.accepted = (int *)(m->dLocal + l.accepted); a.flags = m->dLocal + l.flags;
     a.pass = 1;
     if (maxPoints > 0) hipLaunchKernelGGL(k_motion_project, dim3((maxPoints + 255) / 256, s->n_frames), dim3(256), 0, m->stream, a);
     for (int pass = 1; pass <= (retry ? 2 : 1); pass++) {
         a.pass = pass;
-        if (maxPoints > 0)
-            hipLaunchKernelGGL(k_motion_window_best2, dim3((maxPoints * kWindowLanes + 255) / 256, s->n_frames), dim3(256), 0, m->stream, a);
+        if (maxPoints > 0) hipLaunchKernelGGL(k_motion_window_best2, window_grid(maxPoints, s->n_frames), dim3(256), 0, m->stream, a);
         hipLaunchKernelGGL(k_motion_accept, dim3(s->n_frames), dim3(64), 0, m->stream, a);
     }
     AMOS_HIP_CHECK(hipGetLastError());

@@ -1,9 +1,16 @@
-// amos_projection_search.h -- what the projection-window searches share (k_window_best2 of amos_match.hip, the local-map search of
-// amos_local.hip, the motion-model search of amos_motion.hip): Frame::GetFeaturesInArea (Frame.cc:894-1003) plus the best / second-best
-// Hamming loop over a frame's cell CSR, on the device, and the argument filling, validation and staging of their entries on the host.
-// A search itself keeps how it finds its query, its extra filter and its accept rules.
+// amos_projection_search.h -- what the projection-window searches share: k_window_best2 of amos_match.hip and the four map-point searches
+// (local map: amos_local.hip, motion model: amos_motion.hip, relocalisation: amos_reloc.hip, Fuse: amos_fuse.hip).  On the device:
+//   - Frame::GetFeaturesInArea (Frame.cc:894-1003) plus the best / second-best Hamming loop over a frame's cell CSR (all five);
+//   - the steps of a point's projection that the four spell alike: camera_point, point_offset, normal_dot, in_distance_band, pixel_in_bounds,
+//     copy_desc, predict_scale_level;
+//   - the parts of the greedy acceptance of local, motion and relocalisation: TakenBitmap, wave_research, rotation_bin, three_maxima
+//     (Fuse has no greedy stage).  The sequential loop around them is written out in each accept kernel: three shared forms of it were
+//     measured and each cost the relocalisation kernel 2 to 17 % (profiles/r14_point_searches.txt).
+// On the host: the argument filling, validation, scratch layout and staging of their entries.
+// A search itself keeps how it finds its query and which gates stand between the projection's steps, its extra filter and its accept loop.
 #pragma once
 #include "amos_match_core.h"
+#include "amos_scene_flow.h"  // gemm_row
 
 #include <climits>
 #include <cmath>
@@ -57,6 +64,46 @@ __device__ __forceinline__ int predict_scale_level(const ProjArgs &a, float maxD
     int level = 0;
     for (int m = 0; m < a.nLevels; m++) level += ratio > a.scale[m] ? 1 : 0;
     return min(level, a.nLevels - 1);
+}
+
+// ---- the steps of a point's projection that the point searches (amos_local.hip, amos_motion.hip, amos_reloc.hip, amos_fuse.hip) spell
+// alike.  The gates between them, 1 / z, the order of the pixel's products and Fuse's half-open IsInImage differ on purpose and stay in
+// the kernels (DESIGN.md section 1 lists them).
+
+// Pc = R P + t: one gemm row each, double accumulation, one rounding
+__device__ __forceinline__ void camera_point(const float *R, const float *t, const float *P, float &x, float &y, float &z)
+{
+    x = gemm_row(R, 0, P[0], P[1], P[2], t[0]);
+    y = gemm_row(R, 1, P[0], P[1], P[2], t[1]);
+    z = gemm_row(R, 2, P[0], P[1], P[2], t[2]);
+}
+// PO = P - Ow in float32 -> its length: the squares accumulated in double left to right, one square root, one rounding
+__device__ __forceinline__ float point_offset(const float *P, const float *Ow, float PO[3])
+{
+    PO[0] = __fsub_rn(P[0], Ow[0]); PO[1] = __fsub_rn(P[1], Ow[1]); PO[2] = __fsub_rn(P[2], Ow[2]);
+    const double n2 = __dadd_rn(__dadd_rn(__dmul_rn((double)PO[0], (double)PO[0]), __dmul_rn((double)PO[1], (double)PO[1])),
+                                __dmul_rn((double)PO[2], (double)PO[2]));
+    return (float)__dsqrt_rn(n2);
+}
+// PO . normal in double, left to right, not rounded to float
+__device__ __forceinline__ double normal_dot(const float PO[3], const float *normal)
+{
+    return __dadd_rn(__dadd_rn(__dmul_rn((double)PO[0], (double)normal[0]), __dmul_rn((double)PO[1], (double)normal[1])),
+                     __dmul_rn((double)PO[2], (double)normal[2]));
+}
+// the scale-invariance band of a map point's distance: strict on both sides, a NaN passes
+__device__ __forceinline__ bool in_distance_band(float dist, float minD, float maxD) { return !(dist < __fmul_rn(0.8f, minD) || dist > __fmul_rn(1.2f, maxD)); }
+// the frame searches' pixel gate: inside the inclusive bounds; a pixel that is not finite sets bit 1 of the point's flags instead
+__device__ __forceinline__ bool pixel_in_bounds(const ProjArgs &a, float u, float v, int &flags)
+{
+    if (!(isfinite(u) && isfinite(v))) { flags |= 2; return false; }
+    return !(u < a.minX || u > a.maxX) && !(v < a.minY || v > a.maxY);
+}
+// a point's descriptor into its query record, eight words
+__device__ __forceinline__ void copy_desc(uint8_t *dst, const uint8_t *src)
+{
+#pragma unroll
+    for (int k = 0; k < 8; k++) reinterpret_cast<uint32_t *>(dst)[k] = reinterpret_cast<const uint32_t *>(src)[k];
 }
 
 // one candidate of a window (CSR position j): its key dist << 16 | j, or none when a gate rejects it: the level window, the box, the right
@@ -192,9 +239,11 @@ inline void fill_proj_args(ProjArgs &a, const S &s, const float *uRight)
 template <class S>
 inline void fill_proj_args(ProjArgs &a, const S &s) { fill_proj_args(a, s, s.d_u_right); }
 
-// what the batch entries of the point searches check alike (own: the entry's own pointers are there) -> the most points of a frame, of all
+// What the batch entries of the point searches check alike (own: the entry's own pointers and counts are there).  The point ranges are one
+// per frame, or one per pair (nGroups = &S::n_pairs) with frameOf naming each pair's frame.  -> the most points of a range, of all
 template <class S>
-inline int check_point_search(const char *name, const amos_match *m, const S *s, bool own, int *maxPoints, size_t *total)
+inline int check_point_search(const char *name, const amos_match *m, const S *s, bool own, int *maxPoints, size_t *total,
+                              int32_t S::*nGroups = &S::n_frames, const int32_t *S::*frameOf = nullptr)
 {
     if (!m || !s || !own || !s->d_kps || !s->d_desc || !s->d_counts || !s->d_cell_start || !s->d_items || !s->d_points || !s->point_off ||
         !s->cameras || !s->scale_factors || !s->d_query || !s->d_match || !s->d_stats || s->n_frames < 1 || s->capacity < 1 ||
@@ -204,13 +253,40 @@ inline int check_point_search(const char *name, const amos_match *m, const S *s,
     }
     *maxPoints = 0;
     if (s->point_off[0] < 0) { set_error("%s: point_off[0] < 0", name); return AMOS_ERR_INVALID; }
-    for (int f = 0; f < s->n_frames; f++) {
-        if (s->point_off[f + 1] < s->point_off[f]) { set_error("%s: point_off descends at %d", name, f); return AMOS_ERR_INVALID; }
-        *maxPoints = std::max(*maxPoints, s->point_off[f + 1] - s->point_off[f]);
+    const int groups = s->*nGroups;
+    for (int g = 0; g < groups; g++) {
+        if (frameOf && ((s->*frameOf)[g] < 0 || (s->*frameOf)[g] >= s->n_frames)) { set_error("%s: frame_of_pair[%d] outside the frames", name, g); return AMOS_ERR_INVALID; }
+        if (s->point_off[g + 1] < s->point_off[g]) { set_error("%s: point_off descends at %d", name, g); return AMOS_ERR_INVALID; }
+        *maxPoints = std::max(*maxPoints, s->point_off[g + 1] - s->point_off[g]);
     }
-    *total = (size_t)s->point_off[s->n_frames];
+    *total = (size_t)s->point_off[groups];
     return AMOS_OK;
 }
+
+// The per-call scratch of a point search in dLocal: the frame (or pair) records that upload_frames writes, one amos_best2 per point, then
+// as the search asks one int per point (`accepted`) and one or two planes of one byte per point (flags), each aligned to 64 bytes
+struct PointScratch { size_t best2, accepted, flags, flags2, bytes; };
+inline PointScratch point_scratch(size_t recordBytes, size_t total, bool accepted, int flagPlanes)
+{
+    const size_t best2 = align64(recordBytes), acc = best2 + align64(sizeof(amos_best2) * total), flags = acc + (accepted ? align64(sizeof(int) * total) : 0);
+    return PointScratch{best2, acc, flags, flags + align64(total), flags + (size_t)flagPlanes * align64(total)};
+}
+
+// -Rcw^T tcw (the motion-model search's twc, the relocalisation search's Ow): double accumulation left to right, one rounding
+inline void camera_centre(const float *Rcw, const float *tcw, float *out)
+{
+    for (int k = 0; k < 3; k++) out[k] = (float)-(((double)Rcw[k] * tcw[0] + (double)Rcw[3 + k] * tcw[1]) + (double)Rcw[6 + k] * tcw[2]);
+}
+
+// Frame::PosInGrid (Frame.cc:1007-1030) -> the cell x * rows + y, or -1 outside the grid
+inline int32_t pos_in_grid(float x, float y, float min_x, float min_y, float wInv, float hInv)
+{
+    const int px = (int)roundf((x - min_x) * wInv), py = (int)roundf((y - min_y) * hInv);
+    return px >= 0 && px < AMOS_FRAME_GRID_COLS && py >= 0 && py < AMOS_FRAME_GRID_ROWS ? px * AMOS_FRAME_GRID_ROWS + py : -1;
+}
+
+// the launch grid of a prepass: kWindowLanes lanes per point, 256 threads per block, one row of blocks per frame or pair
+inline dim3 window_grid(int maxPoints, int groups) { return dim3((unsigned)(((size_t)maxPoints * kWindowLanes + 255) / 256), groups); }
 
 // The per-frame parameters of a call to the front of dLocal, through the handle's own pinned buffer: the previous call's copy out of it
 // has to be over before it is written again (an event, not a stream synchronisation: the kernels behind that copy are not waited for).
@@ -262,14 +338,10 @@ inline int one_frame_search(amos_match *m, int (*batch)(amos_match *, const S *)
     if (rc != AMOS_OK) return rc;
     rc = grow_out(m, oAll);
     if (rc != AMOS_OK) return rc;
-    // Frame::PosInGrid (Frame.cc:1007-1030)
     const float wInv = static_cast<float>(AMOS_FRAME_GRID_COLS) / static_cast<float>(max_x - min_x);
     const float hInv = static_cast<float>(AMOS_FRAME_GRID_ROWS) / static_cast<float>(max_y - min_y);
     std::vector<int32_t> cell((size_t)cap, -1);
-    for (int i = 0; i < n; i++) {
-        const int px = (int)roundf((kps_un[i].x - min_x) * wInv), py = (int)roundf((kps_un[i].y - min_y) * hInv);
-        if (px >= 0 && px < AMOS_FRAME_GRID_COLS && py >= 0 && py < AMOS_FRAME_GRID_ROWS) cell[i] = px * AMOS_FRAME_GRID_ROWS + py;
-    }
+    for (int i = 0; i < n; i++) cell[i] = pos_in_grid(kps_un[i].x, kps_un[i].y, min_x, min_y, wInv, hInv);
     const std::vector<uint8_t> zeros(std::max<size_t>((size_t)cap * 32, 256), 0);  // a frame without features or points still hands valid arrays down
     const int32_t count = n, off[2] = {0, n_points};
     uint8_t *out = (uint8_t *)m->dOut;

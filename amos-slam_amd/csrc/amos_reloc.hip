@@ -8,7 +8,6 @@
 // those records, then the rotation histogram's pruning).  The arithmetic is defined in include/amos_frontend.h, "relocalisation search".
 #include "amos_common.h"
 #include "amos_projection_search.h"
-#include "amos_scene_flow.h"  // gemm_row
 
 #include "../../include/amos_host_types.h"  // amos_kf_query
 
@@ -70,8 +69,7 @@ __global__ __launch_bounds__(256) void k_reloc_project(const RelocArgs a)
     q.u = q.v = 0.f;
     q.level = 0;
     q.angle = kp.angle;
-#pragma unroll
-    for (int k = 0; k < 8; k++) reinterpret_cast<uint32_t *>(q.desc)[k] = reinterpret_cast<const uint32_t *>(kp.desc)[k];
+    copy_desc(q.desc, kp.desc);
     int flags = 0;
     if (!(kp.flags & AMOS_RELOC_POINT_SKIP)) {
         const bool found = (a.found && a.found[p] != 0) || (c.found_from_match && a.foundMatch[p] != 0);
@@ -93,20 +91,15 @@ __global__ __launch_bounds__(256) void k_reloc_project(const RelocArgs a)
 #pragma unroll
                 for (int r = 0; r < 3; r++) { t[r] = c.tcw[r]; Ow[r] = pr.Ow[r]; }
             }
-            const float P0 = kp.pos[0], P1 = kp.pos[1], P2 = kp.pos[2];
-            const float xc = gemm_row(R, 0, P0, P1, P2, t[0]);
-            const float yc = gemm_row(R, 1, P0, P1, P2, t[1]);
-            const float zc = gemm_row(R, 2, P0, P1, P2, t[2]);
+            float xc, yc, zc;
+            camera_point(R, t, kp.pos, xc, yc, zc);
             const float invzc = (float)__ddiv_rn(1.0, (double)zc);  // no sign test: :1762-1770
             const float u = __fadd_rn(__fmul_rn(__fmul_rn(c.fx, xc), invzc), c.cx);
             const float v = __fadd_rn(__fmul_rn(__fmul_rn(c.fy, yc), invzc), c.cy);
-            if (!(isfinite(u) && isfinite(v))) flags |= kNotFinite;
-            else if (!(u < a.minX || u > a.maxX) && !(v < a.minY || v > a.maxY)) {
-                const float PO0 = __fsub_rn(P0, Ow[0]), PO1 = __fsub_rn(P1, Ow[1]), PO2 = __fsub_rn(P2, Ow[2]);
-                const double n2 = __dadd_rn(__dadd_rn(__dmul_rn((double)PO0, (double)PO0), __dmul_rn((double)PO1, (double)PO1)),
-                                            __dmul_rn((double)PO2, (double)PO2));
-                const float dist = (float)__dsqrt_rn(n2);
-                if (!(dist < __fmul_rn(0.8f, kp.min_distance) || dist > __fmul_rn(1.2f, kp.max_distance))) {
+            if (pixel_in_bounds(a, u, v, flags)) {
+                float PO[3];
+                const float dist = point_offset(kp.pos, Ow, PO);
+                if (in_distance_band(dist, kp.min_distance, kp.max_distance)) {
                     q.u = u; q.v = v;
                     q.level = predict_scale_level(a, kp.max_distance, dist);
                     flags |= kProjected;
@@ -273,38 +266,28 @@ extern "C" {
 int amos_match_reloc_batch_device(amos_match *m, const amos_reloc_search *s)
 {
     static const char *name = "amos_match_reloc_batch_device";
-    if (!m || !s || !s->d_kps || !s->d_desc || !s->d_counts || !s->d_cell_start || !s->d_items || !s->d_points || !s->frame_of_pair ||
-        !s->point_off || !s->cameras || !s->scale_factors || !s->d_query || !s->d_projected || !s->d_match || !s->d_stats || s->n_frames < 1 ||
-        s->n_pairs < 1 || s->capacity < 1 || s->capacity > 65536 || s->n_levels < 1 || s->n_levels > AMOS_MAX_LEVELS || !(s->max_x > s->min_x) ||
-        !(s->max_y > s->min_y)) {
-        set_error("%s: invalid argument", name);
-        return AMOS_ERR_INVALID;
-    }
-    if (s->point_off[0] < 0) { set_error("%s: point_off[0] < 0", name); return AMOS_ERR_INVALID; }
-    int maxPoints = 0;
+    int maxPoints;
+    size_t total;
+    int rc = check_point_search(name, m, s, s && s->frame_of_pair && s->d_projected && s->n_pairs >= 1, &maxPoints, &total, &amos_reloc_search::n_pairs,
+                                &amos_reloc_search::frame_of_pair);
+    if (rc != AMOS_OK) return rc;
     bool fromMatch = false;
     for (int k = 0; k < s->n_pairs; k++) {
         const amos_reloc_camera &c = s->cameras[k];
-        if (s->frame_of_pair[k] < 0 || s->frame_of_pair[k] >= s->n_frames) { set_error("%s: frame_of_pair[%d] outside the frames", name, k); return AMOS_ERR_INVALID; }
-        if (s->point_off[k + 1] < s->point_off[k]) { set_error("%s: point_off descends at %d", name, k); return AMOS_ERR_INVALID; }
         if (c.orb_dist < 0 || c.orb_dist > 255) { set_error("%s: orb_dist of pair %d outside 0 .. 255", name, k); return AMOS_ERR_INVALID; }
         if (!std::isfinite(c.th) || !(c.th > 0.f)) { set_error("%s: th of pair %d is not finite and positive", name, k); return AMOS_ERR_INVALID; }
-        maxPoints = std::max(maxPoints, s->point_off[k + 1] - s->point_off[k]);
         fromMatch = fromMatch || (c.enabled && c.found_from_match);
     }
-    const size_t total = (size_t)s->point_off[s->n_pairs];
     AMOS_HIP_CHECK(hipSetDevice(m->device));
-    const size_t bytesPairs = align64(sizeof(RelocPair) * (size_t)s->n_pairs), bytesBest = align64(sizeof(amos_best2) * total),
-                 bytesAcc = align64(sizeof(int) * total), bytesFlags = align64(total);
-    int rc = grow(&m->dLocal, &m->capLocal, bytesPairs + bytesBest + bytesAcc + 2 * bytesFlags);
+    const PointScratch l = point_scratch(sizeof(RelocPair) * (size_t)s->n_pairs, total, true, 2);
+    rc = grow(&m->dLocal, &m->capLocal, l.bytes);
     if (rc != AMOS_OK) return rc;
     std::vector<RelocPair> pairs((size_t)s->n_pairs);
     for (int k = 0; k < s->n_pairs; k++) {
         RelocPair &pr = pairs[k];
         pr.cam = s->cameras[k];
         pr.frame = s->frame_of_pair[k]; pr.off0 = s->point_off[k]; pr.off1 = s->point_off[k + 1];
-        const amos_reloc_camera &c = pr.cam;  // Ow = -Rcw^T tcw: double accumulation, one rounding
-        for (int i = 0; i < 3; i++) pr.Ow[i] = (float)-(((double)c.Rcw[i] * c.tcw[0] + (double)c.Rcw[3 + i] * c.tcw[1]) + (double)c.Rcw[6 + i] * c.tcw[2]);
+        camera_centre(pr.cam.Rcw, pr.cam.tcw, pr.Ow);
     }
     rc = upload_frames(m, pairs.data(), sizeof(RelocPair) * pairs.size());
     if (rc != AMOS_OK) return rc;
@@ -312,16 +295,15 @@ int amos_match_reloc_batch_device(amos_match *m, const amos_reloc_search *s)
     fill_proj_args(a, *s, nullptr);
     a.points = s->d_points; a.pairs = (const RelocPair *)m->dLocal; a.found = s->d_found; a.pose = s->d_pose;
     a.query = s->d_query; a.projected = s->d_projected; a.match = s->d_match; a.stats = s->d_stats;
-    a.best2 = (amos_best2 *)(m->dLocal + bytesPairs); a.accepted = (int *)(m->dLocal + bytesPairs + bytesBest);
-    a.flags = m->dLocal + bytesPairs + bytesBest + bytesAcc;
-    a.foundMatch = fromMatch && total > 0 ? a.flags + bytesFlags : nullptr;
+    a.best2 = (amos_best2 *)(m->dLocal + l.best2); a.accepted = (int *)(m->dLocal + l.accepted); a.flags = m->dLocal + l.flags;
+    a.foundMatch = fromMatch && total > 0 ? m->dLocal + l.flags2 : nullptr;
     if (maxPoints > 0) {
         if (a.foundMatch) {
             AMOS_HIP_CHECK(hipMemsetAsync(a.foundMatch, 0, total, m->stream));
             hipLaunchKernelGGL(k_reloc_found, dim3((s->capacity + 255) / 256, s->n_pairs), dim3(256), 0, m->stream, a);
         }
         hipLaunchKernelGGL(k_reloc_project, dim3((maxPoints + 255) / 256, s->n_pairs), dim3(256), 0, m->stream, a);
-        hipLaunchKernelGGL(k_reloc_window_best2, dim3((maxPoints * kWindowLanes + 255) / 256, s->n_pairs), dim3(256), 0, m->stream, a);
+        hipLaunchKernelGGL(k_reloc_window_best2, window_grid(maxPoints, s->n_pairs), dim3(256), 0, m->stream, a);
     }
     hipLaunchKernelGGL(k_reloc_accept, dim3(s->n_pairs), dim3(64), 0, m->stream, a);
     AMOS_HIP_CHECK(hipGetLastError());
