@@ -127,6 +127,8 @@ PROTOTYPES = {
     "amos_mask_conv_chain_supported": (_i, (_i, _i, _i, _i, _i, _i, _i)),
     "amos_mask_conv_chain_device": (_i, (_v, _v, _v, _v, _v, _v, _v, _v, _i, _i, _i, _i, _i, _i, _i)),
     "amos_mask_conv1x1_supported": (_i, (_i, _i, _i)),
+    "amos_mask_conv_upsampled_residual_device": (_i, (_v, _v, _v, _v, _v, _v, _i, _i, _i, _i, _i, _i, _i, _f, _f, _i)),
+    "amos_mask_fpn_fold_mode": (_i, (_i,)),
     "amos_mask_winograd_supported": (_i, (_i, _i)),
     "amos_mask_winograd_weight_floats": (_z, (_i, _i)),
     "amos_mask_winograd_weights_device": (_i, (_v, _v, _v, _i, _i)),
@@ -144,6 +146,8 @@ PROTOTYPES = {
     "amos_mask_nms_column_max_device": (_i, (_v, _v, _v, _i, _i)),
     "amos_mask_class_scores_device": (_i, (_v, _v, _v, _i, _i, _i, _f)),
     "amos_mask_person_mask_device": (_i, (_v, _v, _v, _v, _i, _i, _i, _i, _i, _i)),
+    "amos_mask_person_mask_rects_device": (_i, (_v, _v, _v, _v, _v, _i, _i, _i, _i, _i, _i)),
+    "amos_mask_person_window_mode": (_i, (_i,)),
     "amos_mask_head_outputs_device": (_i, (_v, _v, _v, _v, _v, _v, _i, _i, _i, _i, _i, _i, _i, _i)),
     "amos_mask_head_outputs_scores_device": (_i, (_v, _v, _v, _v, _v, _v, _v, _f, _i, _i, _i, _i, _i, _i, _i, _i)),
     "amos_mask_topk_rows_device": (_i, (_v, _v, _v, _v, _i, _i, _i)),
@@ -157,6 +161,7 @@ PROTOTYPES = {
     "amos_mask_candidates_bytes": (_z, (_i, _i, _i)),
     "amos_mask_candidates_reset_device": (_i, (_v, _v, _i, _i)),
     "amos_mask_head_candidates_device": (_i, (_v, _v, _v, _v, _v, _v, _f, _i, _i, _i, _i, _i, _i, _i, _i)),
+    "amos_mask_head_form_mode": (_i, (_i,)),
     "amos_mask_topk_lists_device": (_i, (_v, _v, _v, _i, _v, _v, _i, _i)),
     "amos_mask_person_masks_candidates_device": (_i, (_v, _v, _v, _v, _v, _v, _i, _i, _i, _i, _i, _i, _i, _i, _v, _z, _v, _v)),
     "amos_mask_person_masks_candidates_at_priors_device": (_i, (_v, _v, _v, _v, _v, _v, _v, _v, _i, _i, _i, _v, _v, _v, _v, _i, _i, _i, _i, _i, _i, _i, _i, _v, _z, _v, _v)),
@@ -754,6 +759,19 @@ def mask_conv_chain(stream_ptr, x_ptr, wd_ptr, bd_ptr, yc_ptr, w3_ptr, b3_ptr, y
            "amos_mask_conv_chain_device")
 
 
+def mask_conv_upsampled_residual(stream_ptr, x_ptr, w_ptr, bias_ptr, up_ptr, y_ptr, batch, in_h, in_w, cin, cout, up_h, up_w, scale_h, scale_w, relu):
+    """amos_mask_conv_upsampled_residual_device: y = act((conv1x1(x, w) + bias) + bilinear(up -> in_h x in_w)) on NHWC float32 tensors in one
+    launch, bit for bit mask_bilinear_nhwc followed by mask_conv with its output as the residual."""
+    _check(lib().amos_mask_conv_upsampled_residual_device(stream_ptr, x_ptr, w_ptr, bias_ptr, up_ptr, y_ptr, batch, in_h, in_w, cin, cout, up_h, up_w,
+                                                          scale_h, scale_w, int(relu)), "amos_mask_conv_upsampled_residual_device")
+
+
+def mask_fpn_fold_mode(mode=-1):
+    """amos_mask_fpn_fold_mode: 1 = the pyramid's top-down resize runs inside the lateral GEMM's epilogue (default), 0 = as a launch of its own;
+    returns the previous mode."""
+    return int(lib().amos_mask_fpn_fold_mode(mode))
+
+
 def mask_conv_workspace_bytes(batch, in_h, in_w, cin, cout, kh, kw, stride, pad):
     """amos_mask_conv_workspace_bytes: scratch mask_conv_ws wants for its split-K plan of this shape; 0 = the plan is an ordinary launch."""
     return int(lib().amos_mask_conv_workspace_bytes(batch, in_h, in_w, cin, cout, kh, kw, stride, pad))
@@ -778,6 +796,19 @@ def mask_class_scores(stream_ptr, conf_ptr, scores_ptr, batch, n_priors, n_class
 
 def mask_person_mask(stream_ptr, masks_ptr, flags_ptr, out_ptr, batch, n_det, mask_h, mask_w, out_h, out_w):
     _check(lib().amos_mask_person_mask_device(stream_ptr, masks_ptr, flags_ptr, out_ptr, batch, n_det, mask_h, mask_w, out_h, out_w), "amos_mask_person_mask_device")
+
+
+def mask_person_mask_rects(stream_ptr, masks_ptr, flags_ptr, rects_ptr, out_ptr, batch, n_det, mask_h, mask_w, out_h, out_w):
+    """amos_mask_person_mask_rects_device: mask_person_mask with the masks' crop rectangles [batch][n_det][4] = (x0, x1, y0, y1); every mask
+    is zero outside its rectangle."""
+    _check(lib().amos_mask_person_mask_rects_device(stream_ptr, masks_ptr, flags_ptr, rects_ptr, out_ptr, batch, n_det, mask_h, mask_w, out_h, out_w),
+           "amos_mask_person_mask_rects_device")
+
+
+def mask_person_window_mode(mode=-1):
+    """amos_mask_person_window_mode: 1 = k_person_mask derives its staging rows and uses the crop rectangles (default), 0 = the earlier form;
+    returns the previous mode."""
+    return int(lib().amos_mask_person_window_mode(mode))
 
 
 def mask_head_outputs(stream_ptr, raw_ptr, bias_ptr, loc_ptr, conf_ptr, coef_ptr, batch, cells, channels_padded, anchors, n_classes_with_background, mask_dim,
@@ -860,6 +891,12 @@ def mask_head_candidates(stream_ptr, raw_ptr, bias_ptr, loc_ptr, coef_ptr, candi
     list of its (frame, class)."""
     _check(lib().amos_mask_head_candidates_device(stream_ptr, raw_ptr, bias_ptr, loc_ptr, coef_ptr, candidates_ptr, threshold, batch, cells, channels_padded,
                                                   anchors, n_classes_with_background, mask_dim, n_priors_total, prior_offset), "amos_mask_head_candidates_device")
+
+
+def mask_head_form_mode(mode=-1):
+    """amos_mask_head_form_mode: 1 = mask_head_candidates' kernel gives a thread one (anchor, class) column (default), 0 = its element loops;
+    returns the previous mode."""
+    return int(lib().amos_mask_head_form_mode(mode))
 
 
 def mask_topk_lists(stream_ptr, counts_ptr, entries_ptr, capacity, values_ptr, indices_ptr, rows, k):

@@ -22,6 +22,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <atomic>
 
 #include "../../include/amos_frontend.h"
 #include "amos_common.h"
@@ -52,6 +53,10 @@ struct ConvGemmArgs {
     // work-group before the main GEMM, over the same output tile; it stays in registers and is the residual of the epilogue
     const float *sx, *sw, *sbias;
     int sK, sStride, sInW, sInH;
+    // kUpRes: `res` is the COARSER tensor [.][upH][upW][N]; the residual of output pixel (oy, ox) is its bilinear sample (align_corners =
+    // false, source index and weights from upScaleH / upScaleW as k_bilinear_nhwc takes them)
+    int upH, upW;
+    float upScaleH, upScaleW;
 };
 
 // kTaps: a kh x kw convolution as an implicit GEMM.  The weight is [cout][kh][kw][cin] (a channels-last Conv2d weight), so the W tile
@@ -60,10 +65,14 @@ struct ConvGemmArgs {
 // kShortcut (1 x 1 only, no split-K): the first block of a ResNet stage as ONE launch -- y = relu((X * W + b) + D) with the projection
 // shortcut D = (X0 * Wd + bd) + 0 computed first over the same tile by the same k loop (the bits amos_mask_conv_device stores for D and then
 // reads back as the residual), so D never goes through memory.
-template <int WM, int WN, int TI, bool kTaps, bool kShortcut = false>  // waves along m and n; a wave's tile is 32 TI x 64
+// kUpRes (1 x 1, stride 1, no split-K): the FPN's lateral convolution with the top-down resize in its epilogue -- y = (X * W + b) + up, where
+// up is what k_bilinear_nhwc<false> would have stored for this pixel and channel (the same four taps, the same weights, the same order of
+// roundings), made from the coarser level by the piece loop instead of being written out and read back.
+template <int WM, int WN, int TI, bool kTaps, bool kShortcut = false, bool kUpRes = false>  // waves along m and n; a wave's tile is 32 TI x 64
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_conv_gemm(const ConvGemmArgs args)  // LDS admits two groups per CU: 256 registers
 {
     static_assert(!(kShortcut && kTaps), "the shortcut form is a pair of 1 x 1 GEMMs");
+    static_assert(!(kUpRes && (kTaps || kShortcut)), "the resize form is a plain 1 x 1 GEMM");
     constexpr int BM = 32 * TI * WM, BN = 64 * WN;
     constexpr int XP = BM / 32, WP = BN / 32;  // 16-byte pieces per thread and stage
     constexpr int kStage = (BM + BN) * kGemmPitch;  // floats of one stage: the X tile, then the W tile
@@ -360,6 +369,51 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
     // costs outside its main loop is the epilogue's write of the 64 KB tile: M 78 400, N 1 024 at k = 32 / 64 / 256 takes 127 / 168 / 384 us --
     // 37 us per stage, 89 % of the pipe, on top of 90 us that no k amortises and the CU's second group does not hide.)
     constexpr int kBatch = 8;  // residual loads in flight per thread
+    if constexpr (kUpRes) {
+        // kBatch pieces at a time: their 4 x kBatch tap loads go out together, then each piece is mixed as k_bilinear_nhwc<false> mixes it
+        // (h0 * (w0 * a + w1 * b) + h1 * (w0 * c + w1 * d), every step rounded) and added as the residual: (acc + bias) + up.
+        const int c4 = a.N / 4;
+        const float4 *up = reinterpret_cast<const float4 *>(a.res) + n0 / 4;
+#pragma unroll
+        for (int p0 = 0; p0 < kPasses; p0 += kBatch) {
+            float4 ta[kBatch], tb[kBatch], tc[kBatch], td[kBatch];
+            float wly[kBatch], wlx[kBatch];
+#pragma unroll
+            for (int q = 0; q < kBatch; q++) {
+                const int m = min(mt * BM + (p0 + q) * kRowsPerPass + orow, a.M - 1);  // rows past the end repeat the last one; they are not stored
+                const int b = m / a.outHW, rem = m - b * a.outHW, oy = rem / a.outW, ox = rem - oy * a.outW;
+                float fy = __fsub_rn(__fmul_rn(a.upScaleH, __fadd_rn((float)oy, 0.5f)), 0.5f), fx = __fsub_rn(__fmul_rn(a.upScaleW, __fadd_rn((float)ox, 0.5f)), 0.5f);
+                fy = fy < 0.f ? 0.f : fy;
+                fx = fx < 0.f ? 0.f : fx;
+                const int y0 = min((int)fy, a.upH - 1), x0 = min((int)fx, a.upW - 1);  // (the minimum only binds for scales that do not belong to the sizes)
+                const int y1 = y0 + (y0 < a.upH - 1 ? 1 : 0), x1 = x0 + (x0 < a.upW - 1 ? 1 : 0);
+                wly[q] = __fsub_rn(fy, (float)y0);
+                wlx[q] = __fsub_rn(fx, (float)x0);
+                const float4 *src = up + (size_t)b * a.upH * a.upW * c4;
+                ta[q] = src[((size_t)y0 * a.upW + x0) * c4];
+                tb[q] = src[((size_t)y0 * a.upW + x1) * c4];
+                tc[q] = src[((size_t)y1 * a.upW + x0) * c4];
+                td[q] = src[((size_t)y1 * a.upW + x1) * c4];
+            }
+#pragma unroll
+            for (int q = 0; q < kBatch; q++) {
+                const int row = (p0 + q) * kRowsPerPass + orow, m = mt * BM + row;
+                if (m >= a.M) continue;
+                const float ly = wly[q], lx = wlx[q], hy = __fsub_rn(1.f, ly), hx = __fsub_rn(1.f, lx);
+                auto mix = [&](float p, float r, float s2, float u) {
+                    return __fadd_rn(__fmul_rn(hy, __fadd_rn(__fmul_rn(hx, p), __fmul_rn(lx, r))), __fmul_rn(ly, __fadd_rn(__fmul_rn(hx, s2), __fmul_rn(lx, u))));
+                };
+                float4 v = *reinterpret_cast<const float4 *>(&smem[row * BN + 4 * oc]);
+                v.x = (v.x + bv.x) + mix(ta[q].x, tb[q].x, tc[q].x, td[q].x);
+                v.y = (v.y + bv.y) + mix(ta[q].y, tb[q].y, tc[q].y, td[q].y);
+                v.z = (v.z + bv.z) + mix(ta[q].z, tb[q].z, tc[q].z, td[q].z);
+                v.w = (v.w + bv.w) + mix(ta[q].w, tb[q].w, tc[q].w, td[q].w);
+                if (a.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+                *reinterpret_cast<float4 *>(a.y + (size_t)m * a.N + n0) = v;
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int p0 = 0; p0 < kPasses; p0 += kBatch) {
         float4 rv[kBatch];
@@ -497,6 +551,7 @@ int amos_mask_conv_ws_device(void *stream, const float *d_x, const float *d_w, c
     a.counters = nullptr;
     a.sx = a.sw = a.sbias = nullptr;
     a.sK = a.sStride = a.sInW = a.sInH = 0;
+    a.upH = a.upW = 0; a.upScaleH = a.upScaleW = 0.f;
     if (d_workspace) {  // split-K when the plan for this shape says so and the caller brought the scratch for it
         const int stages = (cin / kGemmBK) * kh * kw, splits = gemm_splits(M, cout, stages, wide);
         const size_t need = (size_t)kSplitCounterBytes + (size_t)splits * a.mTiles * a.nTiles * BM * BN * sizeof(float);
@@ -552,8 +607,64 @@ int amos_mask_conv_chain_device(void *stream, const float *d_x, const float *d_w
     a.counters = nullptr;
     a.sx = d_x; a.sw = d_wd; a.sbias = d_bd;
     a.sK = cin; a.sStride = stride; a.sInW = in_w; a.sInH = in_h;
+    a.upH = a.upW = 0; a.upScaleH = a.upScaleW = 0.f;
     const dim3 grid((unsigned)(((a.mTiles + 7) / 8) * 8 * a.nTiles)), block(256);
     hipLaunchKernelGGL((k_conv_gemm<2, 2, 2, false, true>), grid, block, 0, (hipStream_t)stream, a);
+    AMOS_HIP_CHECK(hipGetLastError());
+    return AMOS_OK;
+}
+
+// The FPN's lateral 1 x 1 convolution with the top-down resize of the level above as its residual, in one launch (k_conv_gemm<.., false, false,
+// true>): y = act((conv1x1(x, w) + bias) + bilinear(up)), every float what amos_mask_bilinear_nhwc_device followed by amos_mask_conv_device
+// stores.  Tiles as amos_mask_conv_device chooses them (amos_mask_conv_tile_mode); no split-K.
+static std::atomic<int> g_fpn_fold{-2};  // -2: environment not read yet
+static int fpn_fold_mode()
+{
+    if (g_fpn_fold.load() == -2) {
+        const char *env = getenv("AMOS_MASK_FPN_FOLD");
+        g_fpn_fold.store(env && env[0] == '0' ? 0 : 1);
+    }
+    return g_fpn_fold.load();
+}
+
+int amos_mask_fpn_fold_mode(int mode)
+{
+    const int before = fpn_fold_mode();
+    if (mode == 0 || mode == 1) g_fpn_fold.store(mode);
+    return before;
+}
+
+int amos_mask_conv_upsampled_residual_device(void *stream, const float *d_x, const float *d_w, const float *d_bias, const float *d_up, float *d_y, int batch,
+                                             int in_h, int in_w, int cin, int cout, int up_h, int up_w, float scale_h, float scale_w, int relu)
+{
+    if (!d_x || !d_w || !d_up || !d_y || batch < 1 || in_h < 1 || in_w < 1 || up_h < 1 || up_w < 1 || amos_mask_conv_supported(cin, cout, 1, 1, 1, 0) != AMOS_OK ||
+        !(scale_h > 0.f) || !(scale_w > 0.f) || ((uintptr_t)d_x | (uintptr_t)d_w | (uintptr_t)d_y | (uintptr_t)d_bias | (uintptr_t)d_up) % 16 != 0) {
+        set_error("amos_mask_conv_upsampled_residual_device: invalid argument (cin %% 32 == 0, cout %% 64 == 0, positive scales, 16-byte aligned channels-last tensors)");
+        return AMOS_ERR_INVALID;
+    }
+    const long long M = (long long)batch * in_h * in_w;
+    if (M > 0x7fffffffLL / 4 || (long long)batch * in_h * in_w * cin > 0x7fffffffffLL || (long long)batch * up_h * up_w * cout > 0x7fffffffffLL) {
+        set_error("amos_mask_conv_upsampled_residual_device: tensor too large");
+        return AMOS_ERR_INVALID;
+    }
+    ConvGemmArgs a;
+    a.x = d_x; a.w = d_w; a.bias = d_bias; a.res = d_up; a.y = d_y;
+    a.M = (int)M; a.N = cout; a.K = cin;
+    a.outW = in_w; a.outHW = in_h * in_w; a.inW = in_w; a.inH = in_h;
+    a.stride = 1; a.relu = relu; a.kh = a.kw = 1; a.pad = 0;
+    const bool wide = gemm_wide_tiles(M, cout);
+    a.mTiles = (int)((M + 127) / 128);
+    a.nTiles = cout / (wide ? 128 : 64);
+    a.splits = 1;
+    a.stagesPerSplit = 0;
+    a.partial = nullptr;
+    a.counters = nullptr;
+    a.sx = a.sw = a.sbias = nullptr;
+    a.sK = a.sStride = a.sInW = a.sInH = 0;
+    a.upH = up_h; a.upW = up_w; a.upScaleH = scale_h; a.upScaleW = scale_w;
+    const dim3 grid((unsigned)(((a.mTiles + 7) / 8) * 8 * a.nTiles)), block(256);
+    if (wide) hipLaunchKernelGGL((k_conv_gemm<2, 2, 2, false, false, true>), grid, block, 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((k_conv_gemm<4, 1, 1, false, false, true>), grid, block, 0, (hipStream_t)stream, a);
     AMOS_HIP_CHECK(hipGetLastError());
     return AMOS_OK;
 }

@@ -10,7 +10,12 @@
 //                   256 (the reference's `(m * 255).byte()`).  PyTorch: upsample to a [B][15][H][W] float tensor (590 MB at 32 frames),
 //                   compare, and, widen, sum; here the 36 MB of masks are read and the 10 MB result written, unflagged detections skipped.
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
+#include <stdlib.h>
+
+#include <algorithm>
+#include <atomic>
 
 #include "../../include/amos_frontend.h"
 #include "amos_common.h"
@@ -51,15 +56,21 @@ __global__ __launch_bounds__(256) void k_class_scores(const float *__restrict__ 
 }
 
 // grid = (ceil(W / 64), ceil(H / 16), B), block = (64, 4).  The 64 x 16 output pixels of a work-group read a source window of at most
-// kPmCols x kPmRows mask pixels (the masks are upsampled: 138 -> 640 is 0.216 source pixels per output pixel); the window of every flagged
-// detection is staged in LDS by a few coalesced loads, and the four taps of a pixel come from there -- per-thread global gathers (4 per
-// detection and pixel) made this kernel vector-memory-issue bound: 0.39 ms per 64 frames for 20 MB of output.  Windows larger than the
-// staging area (downsampling, or upsampling by less than ~3.7 x) take the gathers as before.  Same arithmetic either way.
-constexpr int kPmCols = 20, kPmRows = 6, kPmDet = 16, kPmTileH = 16;  // a work-group: 64 x 16 output pixels, four rows per thread
-__global__ __launch_bounds__(256) void k_person_mask(const float *__restrict__ masks, const uint8_t *__restrict__ flags, uint8_t *__restrict__ out, int n,
-                                                    int ph, int pw, int H, int W, float scaleH, float scaleW)
+// kPmCols x winRows mask pixels (the masks are upsampled: 138 -> 640 is 0.216 source pixels per output pixel); the window of every
+// detection that counts is staged in LDS by a few coalesced loads, and the four taps of a pixel come from there -- per-thread global gathers
+// (4 per detection and pixel) made this kernel vector-memory-issue bound: 0.39 ms per 64 frames for 20 MB of output.  Windows larger than
+// the staging area (downsampling, or upsampling by less than ~3.7 x along x) take the gathers as before.  Same arithmetic either way.
+// winRows (dynamic LDS: kPmDet x winRows x kPmCols floats) is what the launch derives from the tile height and the scale
+// (person_mask_rows): sixteen output rows at 138 -> 480 touch six or SEVEN source rows, and with six staged a third of the tiles gathered.
+// rects != nullptr: [B][n] (x0, x1, y0, y1), the masks' crop rectangles -- mask (b, i) is ZERO at every pixel outside x0 <= x < x1,
+// y0 <= y < y1 (k_assemble_masks).  A flagged detection whose rectangle, widened by one source pixel, misses the work-group's source window
+// has nothing but zeros under this tile: every pixel's v is 0, which is not above 0.5, so it is neither staged nor evaluated and the
+// counts are what they would have been.
+constexpr int kPmCols = 20, kPmRowsFixed = 6, kPmRowsMax = 16, kPmDet = 16, kPmTileH = 16;  // a work-group: 64 x 16 output pixels, four rows per thread
+__global__ __launch_bounds__(256) void k_person_mask(const float *__restrict__ masks, const uint8_t *__restrict__ flags, const float4 *__restrict__ rects,
+                                                    uint8_t *__restrict__ out, int n, int ph, int pw, int H, int W, float scaleH, float scaleW, int winRows)
 {
-    __shared__ float win[kPmDet][kPmRows][kPmCols];
+    extern __shared__ float win[];  // [kPmDet][winRows][kPmCols]
     __shared__ int sList[kPmDet], sCount;
     const int ox = blockIdx.x * 64 + threadIdx.x, b = blockIdx.z, t = threadIdx.y * 64 + threadIdx.x;
     auto src = [](float scale, int o) {
@@ -70,10 +81,17 @@ __global__ __launch_bounds__(256) void k_person_mask(const float *__restrict__ m
     const int ox0 = blockIdx.x * 64, ox1 = min(ox0 + 63, W - 1), oy0 = blockIdx.y * kPmTileH, oy1 = min(oy0 + kPmTileH - 1, H - 1);
     const int wx0 = (int)src(scaleW, ox0), wx1 = min((int)src(scaleW, ox1) + 1, pw - 1), wy0 = (int)src(scaleH, oy0), wy1 = min((int)src(scaleH, oy1) + 1, ph - 1);
     const int wc = wx1 - wx0 + 1, wr = wy1 - wy0 + 1;
-    const bool staged = wc <= kPmCols && wr <= kPmRows && n <= kPmDet;  // uniform over the work-group
+    const bool staged = wc <= kPmCols && wr <= winRows && n <= kPmDet;  // uniform over the work-group
+    // does detection i count under this tile?  (uniform over the work-group; a NaN in a rectangle compares false: culled, and its mask is zero)
+    auto counts = [&](int i) {
+        if (!flags[b * n + i]) return false;
+        if (!rects) return true;
+        const float4 rc = rects[(size_t)b * n + i];
+        return (float)(wx1 + 1) >= rc.x && (float)(wx0 - 1) < rc.y && (float)(wy1 + 1) >= rc.z && (float)(wy0 - 1) < rc.w;
+    };
     if (staged) {
-        if (t < 64) {  // the flagged detections, in order (wave 0: a ballot and its prefix counts)
-            const bool f = t < n && flags[b * n + t] != 0;
+        if (t < 64) {  // the detections that count, in order (wave 0: a ballot and its prefix counts)
+            const bool f = t < n && counts(t);
             const unsigned long long m = __ballot(f);
             if (f) sList[__popcll(m & ((1ull << t) - 1ull))] = t;
             if (t == 0) sCount = (int)__popcll(m);
@@ -82,7 +100,7 @@ __global__ __launch_bounds__(256) void k_person_mask(const float *__restrict__ m
         const int cnt = sCount, per = wr * wc;
         for (int e = t; e < cnt * per; e += 256) {
             const int d = e / per, rem = e - d * per, r = rem / wc, c = rem - r * wc;
-            win[d][r][c] = masks[((size_t)b * n + sList[d]) * ph * pw + (size_t)(wy0 + r) * pw + wx0 + c];
+            win[(d * winRows + r) * kPmCols + c] = masks[((size_t)b * n + sList[d]) * ph * pw + (size_t)(wy0 + r) * pw + wx0 + c];
         }
         __syncthreads();
     }
@@ -98,15 +116,16 @@ __global__ __launch_bounds__(256) void k_person_mask(const float *__restrict__ m
         const float ly = __fsub_rn(fy, (float)y0), hy = __fsub_rn(1.f, ly);
         unsigned count = 0;
         if (staged) {
-            const int cnt = sCount, ry0 = y0 - wy0, ry1 = y1 - wy0, cx0 = x0 - wx0, cx1 = x1 - wx0;
-            for (int d = 0; d < cnt; d++) {
-                const float p = win[d][ry0][cx0], r = win[d][ry0][cx1], s2 = win[d][ry1][cx0], u = win[d][ry1][cx1];
+            const int cnt = sCount, cx0 = x0 - wx0, cx1 = x1 - wx0;
+            const float *w0 = win + (y0 - wy0) * kPmCols, *w1 = win + (y1 - wy0) * kPmCols;
+            for (int d = 0; d < cnt; d++, w0 += winRows * kPmCols, w1 += winRows * kPmCols) {
+                const float p = w0[cx0], r = w0[cx1], s2 = w1[cx0], u = w1[cx1];
                 const float v = __fadd_rn(__fmul_rn(hy, __fadd_rn(__fmul_rn(hx, p), __fmul_rn(lx, r))), __fmul_rn(ly, __fadd_rn(__fmul_rn(hx, s2), __fmul_rn(lx, u))));
                 count += v > 0.5f ? 1u : 0u;
             }
         } else {
             for (int i = 0; i < n; i++) {
-                if (!flags[b * n + i]) continue;  // uniform over the work-group
+                if (!counts(i)) continue;  // uniform over the work-group
                 const float *m = masks + ((size_t)b * n + i) * ph * pw;
                 const float p = m[y0 * pw + x0], r = m[y0 * pw + x1], s2 = m[y1 * pw + x0], u = m[y1 * pw + x1];
                 const float v = __fadd_rn(__fmul_rn(hy, __fadd_rn(__fmul_rn(hx, p), __fmul_rn(lx, r))), __fmul_rn(ly, __fadd_rn(__fmul_rn(hx, s2), __fmul_rn(lx, u))));
@@ -134,7 +153,12 @@ __global__ __launch_bounds__(256) void k_person_mask(const float *__restrict__ m
 // inside a list depends on the run; the entries are unique, and k_topk_lists sorts them.
 constexpr int kHeadCells = 16;
 __device__ __forceinline__ unsigned topk_key(float f);
-template <bool kCand>
+// kColumns (kCand only; anchors x (1 + C) <= 256, amos_mask_head_form_mode): the kernel is bound by vector instruction issue -- 1 790 per wave at
+// 3 anchors x 81 classes, most of them stepping (cell, offset) pairs and dividing offsets by 1 + C around one exponential or one comparison.
+// Here thread t OWNS column t of the anchors x (1 + C) class values -- its anchor and its class never change -- and walks the cells: an
+// element costs its LDS accesses and its arithmetic.  The same operations on the same values per element, the sums in the same order:
+// the same loc (and coef) bits and the same entries in every list.
+template <bool kCand, bool kColumns = false>
 __global__ __launch_bounds__(256) void k_head_outputs(const float *__restrict__ raw, const float *__restrict__ bias, float *__restrict__ loc, float *__restrict__ conf,
                                                      float *__restrict__ coef, int cells, int cpad, int A, int C1, int D, int P, int pOff,
                                                      float *__restrict__ scores, float thresh, int *__restrict__ candCount,
@@ -190,7 +214,16 @@ __global__ __launch_bounds__(256) void k_head_outputs(const float *__restrict__ 
     }
     __syncthreads();
     const float invC1 = 1.f / (float)C1;
-    AMOS_HEAD_FOREACH(nConf, {
+    static_assert(!kColumns || kCand, "the column form exists for the candidate lists");
+    const int colA = kColumns ? (int)threadIdx.x / C1 : 0, colC = kColumns ? (int)threadIdx.x - colA * C1 : 0;  // kColumns: this thread's anchor and class
+    const bool colMine = kColumns && (int)threadIdx.x < nConf;
+    if constexpr (kColumns) {
+        if (colMine) {
+            float *v = sh + nLoc + threadIdx.x;
+            const float *mx = sMax + colA;
+            for (int cell = 0; cell < nc; cell++, v += cpad, mx += A) *v = expf(__fsub_rn(*v, *mx));
+        }
+    } else AMOS_HEAD_FOREACH(nConf, {
         float *v = sh + cell * cpad + nLoc + r;
         int a = (int)((float)r * invC1);  // r / C1 for r < A * C1 <= a few hundred: the float quotient is off by at most one
         a -= a * C1 > r ? 1 : 0;
@@ -220,7 +253,20 @@ __global__ __launch_bounds__(256) void k_head_outputs(const float *__restrict__ 
         const float pre = thresh * 0.99f;
         unsigned long long mine = 0ull;
         int trip = 0;
-        AMOS_HEAD_FOREACH(nConf, {
+        if constexpr (kColumns) {
+            if (colMine && colC >= 1) {  // (bit `cell` of the mask; all of this thread's entries belong to class row colC - 1: one LDS atomic)
+                const float *v = sh + nLoc + threadIdx.x, *sm = sSum + colA;
+                unsigned passed = 0u;
+                for (int cell = 0; cell < nc; cell++, v += cpad, sm += A) {
+                    const float ev = *v, s = *sm;
+                    if (ev > s * pre && ev / s > thresh) {  // (NaN compares false)
+                        mine |= 1ull << cell;
+                        passed++;
+                    }
+                }
+                if (passed) atomicAdd(&sCnt[colC - 1], passed);
+            }
+        } else AMOS_HEAD_FOREACH(nConf, {
             int a = (int)((float)r * invC1);
             a -= a * C1 > r ? 1 : 0;
             a += (a + 1) * C1 <= r ? 1 : 0;
@@ -246,7 +292,8 @@ __global__ __launch_bounds__(256) void k_head_outputs(const float *__restrict__ 
         while (mine) {
             const int tr = (int)__builtin_ctzll(mine);
             mine &= mine - 1ull;
-            const int e = (int)threadIdx.x + 256 * tr, cell = e / nConf, r = e - cell * nConf, a = r / C1, c = r - a * C1;
+            const int e = (int)threadIdx.x + 256 * tr, cell = kColumns ? tr : e / nConf, r = kColumns ? (int)threadIdx.x : e - cell * nConf;
+            const int a = kColumns ? colA : r / C1, c = kColumns ? colC : r - a * C1;
             const float q = sh[cell * cpad + nLoc + r] / sSum[cell * A + a];  // the quotient conf would hold
             const unsigned slot = sBase[c - 1] + atomicAdd(&sCnt[c - 1], 1u);
             const unsigned prior = (unsigned)(pOff + (c0 + cell) * A + a);
@@ -1194,18 +1241,55 @@ int amos_mask_class_scores_device(void *stream, const float *d_conf, float *d_sc
     return AMOS_OK;
 }
 
+// Form of k_person_mask: 1 (default) = staging rows derived from the scale and, where the caller brings the crop rectangles, only the
+// detections that meet a work-group's source window; 0 = six staging rows and every flagged detection everywhere, the form before.  Same
+// bytes either way.  AMOS_MASK_PERSON_WINDOW=0 / 1 in the environment is the initial value.
+static std::atomic<int> g_person_window{-2};  // -2: environment not read yet
+static int person_window_mode()
+{
+    if (g_person_window.load() == -2) {
+        const char *env = getenv("AMOS_MASK_PERSON_WINDOW");
+        g_person_window.store(env && env[0] == '0' ? 0 : 1);
+    }
+    return g_person_window.load();
+}
+
+// source rows that kPmTileH consecutive output rows can touch: the first and the last are (kPmTileH - 1) * scale apart, each reads the
+// row below it as well
+static int person_mask_rows(float scale_h)
+{
+    const float span = ceilf((float)(kPmTileH - 1) * scale_h);
+    return span >= (float)(kPmRowsMax - 2) ? kPmRowsMax : std::max((int)span + 2, 2);
+}
+
+int amos_mask_person_window_mode(int mode)
+{
+    const int before = person_window_mode();
+    if (mode == 0 || mode == 1) g_person_window.store(mode);
+    return before;
+}
+
 int amos_mask_person_mask_device(void *stream, const float *d_masks, const uint8_t *d_flags, uint8_t *d_out, int batch, int n_det, int mask_h, int mask_w,
                                  int out_h, int out_w)
 {
-    if (!d_masks || !d_flags || !d_out || batch < 0 || n_det < 0 || mask_h < 1 || mask_w < 1 || out_h < 1 || out_w < 1 || batch > 65535 || out_h > 16 * 65535) {
+    return amos_mask_person_mask_rects_device(stream, d_masks, d_flags, nullptr, d_out, batch, n_det, mask_h, mask_w, out_h, out_w);
+}
+
+int amos_mask_person_mask_rects_device(void *stream, const float *d_masks, const uint8_t *d_flags, const float *d_rects, uint8_t *d_out, int batch, int n_det,
+                                       int mask_h, int mask_w, int out_h, int out_w)
+{
+    if (!d_masks || !d_flags || !d_out || batch < 0 || n_det < 0 || mask_h < 1 || mask_w < 1 || out_h < 1 || out_w < 1 || batch > 65535 || out_h > 16 * 65535 ||
+        (uintptr_t)d_rects % 16 != 0) {
         set_error("amos_mask_person_mask_device: invalid argument");
         return AMOS_ERR_INVALID;
     }
     if (batch == 0) return AMOS_OK;
     // PyTorch's area_pixel_compute_scale for a given output size: input / output in float32
     const float sh = (float)mask_h / (float)out_h, sw = (float)mask_w / (float)out_w;
-    hipLaunchKernelGGL(k_person_mask, dim3((out_w + 63) / 64, (out_h + kPmTileH - 1) / kPmTileH, batch), dim3(64, 4), 0, (hipStream_t)stream, d_masks, d_flags, d_out, n_det, mask_h,
-                       mask_w, out_h, out_w, sh, sw);
+    const bool window = person_window_mode() != 0;
+    const int rows = window ? person_mask_rows(sh) : kPmRowsFixed;
+    hipLaunchKernelGGL(k_person_mask, dim3((out_w + 63) / 64, (out_h + kPmTileH - 1) / kPmTileH, batch), dim3(64, 4), (size_t)kPmDet * rows * kPmCols * sizeof(float),
+                       (hipStream_t)stream, d_masks, d_flags, window ? (const float4 *)d_rects : nullptr, d_out, n_det, mask_h, mask_w, out_h, out_w, sh, sw, rows);
     AMOS_HIP_CHECK(hipGetLastError());
     return AMOS_OK;
 }
@@ -1257,6 +1341,25 @@ int amos_mask_candidates_reset_device(void *stream, void *d_candidates, int batc
     return AMOS_OK;
 }
 
+// Form of k_head_outputs<true>: 1 (default) = a thread owns an (anchor, class) column and walks the cells, where anchors x classes fit a
+// work-group; 0 = the element loops of the other forms.  Same loc, same lists.  AMOS_MASK_HEAD_COLUMNS=0 / 1 in the environment is the initial value.
+static std::atomic<int> g_head_form{-2};  // -2: environment not read yet
+static int head_form_mode()
+{
+    if (g_head_form.load() == -2) {
+        const char *env = getenv("AMOS_MASK_HEAD_COLUMNS");
+        g_head_form.store(env && env[0] == '0' ? 0 : 1);
+    }
+    return g_head_form.load();
+}
+
+int amos_mask_head_form_mode(int mode)
+{
+    const int before = head_form_mode();
+    if (mode == 0 || mode == 1) g_head_form.store(mode);
+    return before;
+}
+
 int amos_mask_head_candidates_device(void *stream, const float *d_raw, const float *d_bias, float *d_loc, float *d_coef, void *d_candidates, float threshold,
                                      int batch, int cells, int channels_padded, int anchors, int n_classes_with_background, int mask_dim, int n_priors_total,
                                      int prior_offset)
@@ -1271,10 +1374,15 @@ int amos_mask_head_candidates_device(void *stream, const float *d_raw, const flo
     }
     if (batch == 0) return AMOS_OK;
     uint8_t *cand = (uint8_t *)d_candidates;
-    hipLaunchKernelGGL(k_head_outputs<true>, dim3((cells + kHeadCells - 1) / kHeadCells, batch), dim3(256), (size_t)kHeadCells * channels_padded * sizeof(float),
-                       (hipStream_t)stream, d_raw, d_bias, d_loc, (float *)nullptr, d_coef, cells, channels_padded, anchors, n_classes_with_background, mask_dim,
-                       n_priors_total, prior_offset, (float *)nullptr, threshold, (int *)cand,
-                       (unsigned long long *)(cand + cand_counts_bytes(batch, n_classes_with_background - 1)));
+    const dim3 grid((cells + kHeadCells - 1) / kHeadCells, batch);
+    const size_t lds = (size_t)kHeadCells * channels_padded * sizeof(float);
+    unsigned long long *entries = (unsigned long long *)(cand + cand_counts_bytes(batch, n_classes_with_background - 1));
+    if (head_form_mode() != 0 && anchors * n_classes_with_background <= 256)  // a thread per (anchor, class) column
+        hipLaunchKernelGGL((k_head_outputs<true, true>), grid, dim3(256), lds, (hipStream_t)stream, d_raw, d_bias, d_loc, (float *)nullptr, d_coef, cells, channels_padded,
+                           anchors, n_classes_with_background, mask_dim, n_priors_total, prior_offset, (float *)nullptr, threshold, (int *)cand, entries);
+    else
+        hipLaunchKernelGGL((k_head_outputs<true, false>), grid, dim3(256), lds, (hipStream_t)stream, d_raw, d_bias, d_loc, (float *)nullptr, d_coef, cells, channels_padded,
+                           anchors, n_classes_with_background, mask_dim, n_priors_total, prior_offset, (float *)nullptr, threshold, (int *)cand, entries);
     AMOS_HIP_CHECK(hipGetLastError());
     return AMOS_OK;
 }
@@ -1557,7 +1665,7 @@ static int person_masks(void *stream, const float *d_loc, const float *d_conf, c
     }
     hipLaunchKernelGGL(k_assemble_masks, dim3((proto_h * proto_w + 255) / 256, nd, B), dim3(256), 0, st, d_proto, selCoef, selRect, flags, masks, proto_h, proto_w, D, nd);
     AMOS_HIP_CHECK(hipGetLastError());
-    return amos_mask_person_mask_device(stream, masks, flags, d_masks, B, nd, proto_h, proto_w, out_h, out_w);
+    return amos_mask_person_mask_rects_device(stream, masks, flags, (const float *)selRect, d_masks, B, nd, proto_h, proto_w, out_h, out_w);
 }
 
 }  // extern "C"

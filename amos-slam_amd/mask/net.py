@@ -350,6 +350,40 @@ def bilinear(x, size=None, scale_factor=None, relu=False):
     return F.relu(y) if relu else y
 
 
+def lateral_fold(conv, x, top):
+    """Does the pyramid's lateral convolution `conv` of x take the level above, `top`, as it is and resize it in its own epilogue
+    (amos_mask_conv_upsampled_residual_device: one launch, the resized tensor never written) instead of bilinear + conv_bias_act?  Only where
+    conv_bias_act would run the layer on the project's GEMM -- the fused kernel stores exactly the floats of the two launches.
+    amos_mask_fpn_fold_mode / AMOS_MASK_FPN_FOLD=0 turn it off."""
+    if top is None or not x.is_cuda or conv.bias is None or torch.is_autocast_enabled():
+        return False
+    if conv.kernel_size != (1, 1) or conv.stride != (1, 1) or conv.padding != (0, 0) or top.shape[1] != conv.out_channels or top.shape[0] != x.shape[0]:
+        return False
+    cl = torch.channels_last
+    if not (x.dtype == top.dtype == conv.weight.dtype == torch.float32 and x.is_contiguous(memory_format=cl) and top.is_contiguous(memory_format=cl)):
+        return False
+    if not (conv.weight.is_contiguous(memory_format=cl) or conv.weight.is_contiguous()) or not _gemm_conv(conv, x):
+        return False
+    from .. import mask_fpn_fold_mode
+    return mask_fpn_fold_mode() == 1
+
+
+def lateral_conv(conv, x, top):
+    """The pyramid's lateral step: conv(x) + bias + bilinear(top, size of x); top None: the deepest level, no residual."""
+    if not lateral_fold(conv, x, top):
+        up = bilinear(top, size=x.shape[2:]) if top is not None else None
+        return conv_bias_act(conv, x, False, residual=up)
+    from .. import mask_conv_upsampled_residual
+    b, _, h, w = x.shape
+    uh, uw = top.shape[2:]
+    # PyTorch's area_pixel_compute_scale for a given size, in float32 (as bilinear() takes it)
+    sh, sw = float(torch.tensor(uh, dtype=torch.float32) / h), float(torch.tensor(uw, dtype=torch.float32) / w)
+    y = torch.empty((b, conv.out_channels, h, w), device=x.device, dtype=torch.float32, memory_format=torch.channels_last)
+    mask_conv_upsampled_residual(torch.cuda.current_stream(x.device).cuda_stream, x.data_ptr(), conv.weight.data_ptr(), conv.bias.data_ptr(), top.data_ptr(),
+                                 y.data_ptr(), b, h, w, conv.in_channels, conv.out_channels, uh, uw, sh, sw, False)
+    return y
+
+
 def _fold(conv, bn):
     """conv followed by an inference-mode batch norm == one conv with scaled weights and a bias:
     w' = w * g / sqrt(var + eps),  b' = beta - mean * g / sqrt(var + eps)   (folded in float64, stored float32)."""
@@ -575,9 +609,9 @@ class FeaturePyramid(nn.Module):
         top = None
         for k, lat in enumerate(self.lat_layers):  # deepest level first
             j = n - 1 - k
-            # lateral convolution + bias + the upsampled level above (the residual of the fused epilogue: same order of sums)
-            up = bilinear(top, size=feats[j].shape[2:]) if top is not None else None
-            merged[j] = top = conv_bias_act(lat, feats[j], False, residual=up)
+            # lateral convolution + bias + the upsampled level above (the residual of the fused epilogue: same order of sums; where the
+            # lateral runs on the GEMM the resize happens in that epilogue too, lateral_conv)
+            merged[j] = top = lateral_conv(lat, feats[j], top)
         outs = [None] * n
         if br is not None and n == 3:
             br.hold(*merged)

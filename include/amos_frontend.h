@@ -1050,6 +1050,18 @@ int amos_mask_conv_chain_supported(int batch, int in_h, int in_w, int cin, int p
 int amos_mask_conv_chain_device(void *stream, const float *d_x, const float *d_wd, const float *d_bd, const float *d_yc, const float *d_w3,
                                 const float *d_b3, float *d_y, int batch, int in_h, int in_w, int cin, int planes, int cout, int stride);
 int amos_mask_conv1x1_supported(int cin, int cout, int stride);
+/* The feature pyramid's lateral 1 x 1 convolution with the top-down resize of the level above in its epilogue (one launch):
+ *   y = act((conv1x1(x, w) + bias) + bilinear(up))    x [batch][in_h][in_w][cin], up [batch][up_h][up_w][cout], y [batch][in_h][in_w][cout]
+ * bilinear = amos_mask_bilinear_nhwc_device(up -> in_h x in_w, scale_h, scale_w): the same taps, weights and order of roundings, so every
+ * value of y is the float that call followed by amos_mask_conv_device (d_residual = its output) stores; the resized tensor is never
+ * written.  Tiles as amos_mask_conv_device picks them (amos_mask_conv_tile_mode), no split-K.  d_bias may be NULL.
+ * amos_mask_fpn_fold_mode: 1 = the network's pyramid uses this entry where its lateral runs on the GEMM (default), 0 = resize and
+ * convolution as two launches; returns the mode in force before the call, any other argument only queries.  AMOS_MASK_FPN_FOLD=0 / 1 in
+ * the environment is the initial value. */
+int amos_mask_conv_upsampled_residual_device(void *stream, const float *d_x, const float *d_w, const float *d_bias, const float *d_up,
+                                             float *d_y, int batch, int in_h, int in_w, int cin, int cout, int up_h, int up_w,
+                                             float scale_h, float scale_w, int relu);
+int amos_mask_fpn_fold_mode(int mode);
 
 /* The same convolution for 3 x 3 kernels with stride 1 and pad 1 (the prototype network, the prediction head, the FPN's prediction layers
  * and the bottlenecks' conv2 of yolact.py / backbone.py: 70 % of the network's multiply-accumulates) as Winograd F(2 x 2, 3 x 3) on the
@@ -1128,6 +1140,16 @@ int amos_mask_class_scores_device(void *stream, const float *d_conf, float *d_sc
  * the reference's `(m * 255).byte()`.  Same source index and weights as PyTorch's upsample_bilinear2d. */
 int amos_mask_person_mask_device(void *stream, const float *d_masks, const uint8_t *d_flags, uint8_t *d_out, int batch, int n_det,
                                  int mask_h, int mask_w, int out_h, int out_w);
+/* The same with the masks' crop rectangles: d_rects [batch][n_det][4] = (x0, x1, y0, y1) in mask pixels (16-byte aligned), and mask
+ * (b, i) must be ZERO at every pixel outside x0 <= x < x1, y0 <= y < y1 (what postprocess's crop leaves).  A work-group then stages and
+ * evaluates only the flagged detections whose rectangle reaches its source window; the others add nothing anywhere under it.  Same bytes
+ * as amos_mask_person_mask_device; d_rects NULL is that call.
+ * amos_mask_person_window_mode: 1 = staging rows derived from the scale and the rectangles used (default), 0 = six staging rows and the
+ * rectangles ignored (the earlier form); returns the mode in force before the call, any other argument only queries.
+ * AMOS_MASK_PERSON_WINDOW=0 / 1 in the environment is the initial value. */
+int amos_mask_person_mask_rects_device(void *stream, const float *d_masks, const uint8_t *d_flags, const float *d_rects, uint8_t *d_out,
+                                       int batch, int n_det, int mask_h, int mask_w, int out_h, int out_w);
+int amos_mask_person_window_mode(int mode);
 
 /* The prediction head's outputs for one pyramid level (yolact.py PredictionModule.forward and the cat / softmax of Yolact.forward):
  * d_raw [batch][cells][channels_padded] = the merged output convolution WITHOUT bias, channels [anchors x 4 | anchors x
@@ -1229,6 +1251,11 @@ int amos_mask_candidates_reset_device(void *stream, void *d_candidates, int batc
 int amos_mask_head_candidates_device(void *stream, const float *d_raw, const float *d_bias, float *d_loc, float *d_coef, void *d_candidates, float threshold,
                                      int batch, int cells, int channels_padded, int anchors, int n_classes_with_background, int mask_dim,
                                      int n_priors_total, int prior_offset);
+/* Form of that kernel: 1 = where anchors x n_classes_with_background <= 256, a thread owns one (anchor, class) column and walks the
+ * work-group's cells (default: the kernel is bound by vector instruction issue, and this form spends none on stepping indices), 0 = the
+ * element loops of amos_mask_head_outputs_device.  The same d_loc and d_coef bits and the same entries in every list.  Returns the mode in
+ * force before the call; any other argument only queries.  AMOS_MASK_HEAD_COLUMNS=0 / 1 in the environment is the initial value. */
+int amos_mask_head_form_mode(int mode);
 /* Top-k of `rows` lists of unique 8-byte entries (key << 32 | ~index, key = the order-preserving integer image of a float32 score): d_counts
  * int32 [rows], list r at d_entries + r x capacity.  d_values / d_indices [rows][k]: score descending, equal scores lowest index first; slots
  * past a list's count hold score -1 and index 0.  Independent of the order of the entries.  1 <= k <= 256. */
