@@ -89,6 +89,9 @@ PROTOTYPES = {
     "amos_match_motion_model": (_i, (_v, _v, _v, _v, _i, _v, _i, _v, _v, _i, _f, _f, _f, _f, _v, _v, _v, _v)),
     "amos_match_reloc_batch_device": (_i, (_v, _v)),
     "amos_match_reloc": (_i, (_v, _v, _v, _i, _v, _i, _v, _v, _v, _i, _f, _f, _f, _f, _v, _v, _v, _v)),
+    "amos_reloc_pnp_state_bytes": (_z, (_i,)),
+    "amos_match_reloc_pnp_batch_device": (_i, (_v, _v)),
+    "amos_match_reloc_pnp": (_i, (_v, _v, _i, _v, _v, _i, _v, _i, _v, _v, _v, _v, _v, _v)),
     "amos_match_pose_optimization_batch_device": (_i, (_v, _v)),
     "amos_match_pose_optimization": (_i, (_v, _v, _v, _i, _v, _v, _v, _i, _v, _v, _i, _i, _v, _v)),
     "amos_bow_create": (_i, (_i, _v, _i, _i, _i, _i, _i, _v, _v, _v, _v, _v)),
@@ -1089,6 +1092,53 @@ class RelocSearch(C.Structure):
                 ("max_y", C.c_float)]
 
 
+class RelocPnpParams(C.Structure):
+    """amos_reloc_pnp_params: 64 bytes; RELOC_PNP_PARAMS_DTYPE is the same record for numpy."""
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("probability", C.c_double),
+                ("min_inliers", C.c_int32), ("max_iterations", C.c_int32), ("epsilon", C.c_float), ("th2", C.c_float),
+                ("n_iterations", C.c_int32), ("reset", C.c_int32), ("seed", C.c_uint64), ("enabled", C.c_int32), ("pad", C.c_int32)]
+
+
+class RelocPnpResult(C.Structure):
+    """amos_reloc_pnp_result: 104 bytes; RELOC_PNP_RESULT_DTYPE is the same record for numpy."""
+    _fields_ = [("Tcw", C.c_float * 12), ("code", C.c_int32), ("has_pose", C.c_int32), ("no_more", C.c_int32), ("refined", C.c_int32),
+                ("n_inliers", C.c_int32), ("n_correspondences", C.c_int32), ("min_inliers", C.c_int32), ("max_iterations", C.c_int32),
+                ("iterations", C.c_int32), ("iterations_call", C.c_int32), ("best_inliers", C.c_int32), ("status", C.c_int32),
+                ("skipped", C.c_int32), ("pad", C.c_int32)]
+
+
+RELOC_PNP_PARAMS_DTYPE = np.dtype([("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"), ("probability", "<f8"), ("min_inliers", "<i4"),
+                                   ("max_iterations", "<i4"), ("epsilon", "<f4"), ("th2", "<f4"), ("n_iterations", "<i4"), ("reset", "<i4"),
+                                   ("seed", "<u8"), ("enabled", "<i4"), ("pad", "<i4")])
+RELOC_PNP_RESULT_DTYPE = np.dtype([("Tcw", "<f4", (12,)), ("code", "<i4"), ("has_pose", "<i4"), ("no_more", "<i4"), ("refined", "<i4"),
+                                   ("n_inliers", "<i4"), ("n_correspondences", "<i4"), ("min_inliers", "<i4"), ("max_iterations", "<i4"),
+                                   ("iterations", "<i4"), ("iterations_call", "<i4"), ("best_inliers", "<i4"), ("status", "<i4"),
+                                   ("skipped", "<i4"), ("pad", "<i4")])
+assert (C.sizeof(RelocPnpParams), C.sizeof(RelocPnpResult)) == (RELOC_PNP_PARAMS_DTYPE.itemsize, RELOC_PNP_RESULT_DTYPE.itemsize) == (64, 104)
+
+
+def reloc_pnp_params(K, seed, reset=1, n_iterations=5, probability=0.99, min_inliers=10, max_iterations=300, epsilon=0.5, th2=5.991, enabled=1):
+    """One RELOC_PNP_PARAMS_DTYPE record with the parameters of Tracking.cc:2665 (SetRansacParameters(0.99, 10, 300, 4, 0.5, 5.991), iterate(5))."""
+    p = np.zeros(1, RELOC_PNP_PARAMS_DTYPE)
+    p["fx"], p["fy"], p["cx"], p["cy"] = K
+    p["probability"], p["min_inliers"], p["max_iterations"], p["epsilon"], p["th2"] = probability, min_inliers, max_iterations, epsilon, th2
+    p["n_iterations"], p["reset"], p["seed"], p["enabled"] = n_iterations, reset, seed, enabled
+    return p[0]
+
+
+class RelocPnp(C.Structure):
+    """amos_reloc_pnp (include/amos_frontend.h)."""
+    _fields_ = [("d_kps", C.c_void_p), ("d_counts", C.c_void_p), ("frame_of_pair", C.c_void_p), ("point_off", C.c_void_p), ("d_points", C.c_void_p),
+                ("d_bow_match", C.c_void_p), ("level_sigma2", C.c_void_p), ("params", C.c_void_p), ("d_state", C.c_void_p),
+                ("d_result", C.c_void_p), ("d_inlier", C.c_void_p), ("d_match", C.c_void_p), ("d_found", C.c_void_p), ("n_frames", C.c_int32),
+                ("n_pairs", C.c_int32), ("capacity", C.c_int32), ("n_levels", C.c_int32)]
+
+
+def reloc_pnp_state_bytes(capacity):
+    """Bytes of one pair's carried PnPsolver state (amos_reloc_pnp_state_bytes)."""
+    return int(lib().amos_reloc_pnp_state_bytes(int(capacity)))
+
+
 class PoseCamera(C.Structure):
     """amos_pose_camera: 68 bytes; POSE_CAMERA_DTYPE is the same record for numpy."""
     _fields_ = [("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
@@ -1407,6 +1457,44 @@ class OrbMatcher(_Handle):
         _check(self.L.amos_match_reloc(self.h, _p(kps_un), _p(desc), n, _p(points), m, _p(fd), _p(cam), _p(sf), len(sf), *bounds, _p(query),
                                        _p(projected), _p(match), _p(stats)), "amos_match_reloc")
         return query, projected, match, stats[0]
+
+    def reloc_pnp_batch_device(self, d_kps, d_counts, n_frames, d_points, frame_of_pair, point_off, d_bow_match, level_sigma2, params, capacity,
+                               d_state, d_result, d_inlier, d_match, d_found=None):
+        """Relocalization's PnPsolver (PnPsolver.cc:120-458), one iterate() call per pair (frame, candidate keyframe) on resident frames.
+        frame_of_pair: n_pairs host ints; point_off: n_pairs + 1 host ints; params: host RELOC_PNP_PARAMS_DTYPE records, one per pair;
+        d_state: n_pairs blocks of reloc_pnp_state_bytes(capacity) bytes; d_result: RELOC_PNP_RESULT_DTYPE records.  Asynchronous on the
+        matcher's stream."""
+        sig = np.ascontiguousarray(level_sigma2, np.float32)
+        off = np.ascontiguousarray(point_off, np.int32)
+        fop = np.ascontiguousarray(frame_of_pair, np.int32)
+        par = np.ascontiguousarray(params, RELOC_PNP_PARAMS_DTYPE).reshape(-1)
+        if len(off) != len(par) + 1 or len(fop) != len(par):
+            raise ValueError("point_off holds one entry more than params, frame_of_pair as many")
+        s = RelocPnp(d_kps, d_counts, fop.ctypes.data, off.ctypes.data, d_points, d_bow_match, sig.ctypes.data, par.ctypes.data, d_state, d_result,
+                     d_inlier, d_match, d_found, n_frames, len(par), capacity, len(sig))
+        _check(self.L.amos_match_reloc_pnp_batch_device(self.h, C.byref(s)), "amos_match_reloc_pnp_batch_device")
+
+    def reloc_pnp(self, kps_un, bow_match, points, level_sigma2, params, state=None):
+        """The same for ONE pair from host arrays (amos_match_reloc_pnp): returns (result, inlier, match, found, state).  state: the blob an
+        earlier call returned (params['reset'] = 0 goes on from it), or None for a fresh one.  match and found are None without a pose."""
+        kps_un = np.ascontiguousarray(kps_un, KP_DTYPE)
+        bow_match = np.ascontiguousarray(bow_match, np.int32)
+        points = np.ascontiguousarray(points, RELOC_POINT_DTYPE)
+        sig = np.ascontiguousarray(level_sigma2, np.float32)
+        par = np.ascontiguousarray(params, RELOC_PNP_PARAMS_DTYPE).reshape(1)
+        n, m = len(kps_un), len(points)
+        if len(bow_match) != n:
+            raise ValueError("bow_match holds one entry per keypoint")
+        nbytes = reloc_pnp_state_bytes(max(n, 1))
+        state = np.zeros(nbytes, np.uint8) if state is None else np.ascontiguousarray(state, np.uint8).copy()
+        if len(state) != nbytes:
+            raise ValueError("state is not a blob of reloc_pnp_state_bytes(n) bytes")
+        result = np.zeros(1, RELOC_PNP_RESULT_DTYPE)
+        inlier, match, found = np.zeros(n, np.uint8), np.full(n, -1, np.int32), np.zeros(m, np.uint8)
+        _check(self.L.amos_match_reloc_pnp(self.h, _p(kps_un), n, _p(bow_match), _p(points), m, _p(sig), len(sig), _p(par), _p(state), _p(result),
+                                           _p(inlier), _p(match), _p(found)), "amos_match_reloc_pnp")
+        pose = bool(result[0]["has_pose"])
+        return result[0], inlier, (match if pose else None), (found if pose else None), state
 
     def pose_optimization_batch_device(self, d_kps, d_counts, d_match, d_points, point_off, cameras, capacity, inv_level_sigma2, d_outlier,
                                        d_result, point_stride=12, flags_offset=-1, has_obs_bit=0, clear_outliers=False, d_u_right=None):

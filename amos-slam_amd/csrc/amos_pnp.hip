@@ -7,11 +7,12 @@
 //                  checkSubset, so every draw of 4 distinct indices is a subset); one lane per subset runs P3P; all waves score the up to
 //                  64 models over all points (counts by wave reduction, no atomics); lane 0 replays the sequential loop in iteration order
 //                  (best model, niters).  The RNG consumption depends only on the point count, so drawing ahead changes nothing.  Then
-//                  the EPnP refit in the same launch: every sum over the inliers is owned by one lane and runs in inlier order; the
-//                  per-inlier alphas and image points go through a global scratch row of the problem; the small dense steps (PCA,
-//                  pseudo-inverse, 12 x 12 Jacobi, betas, Gauss-Newton, R and t) run on one lane.
+//                  the EPnP refit in the same launch (amos_pnp_block.h, shared with amos_reloc_pnp.hip): every sum over the inliers is
+//                  owned by one lane and runs in inlier order; the per-inlier alphas and image points go through a global scratch row of
+//                  the problem; the 12 x 12 Jacobi runs on sixteen lanes, the three beta sets on three, the other dense steps on one.
 //   k_pnp_points   Tracking.cc:955-990: the N-point lists of the reference (pre_3d, cur_2d), (0, 0, 0) -> (0, 0) where a depth is missing
 #include "amos_common.h"
+#include "amos_pnp_block.h"
 #include "amos_pnp_core.h"
 #include "amos_ransac.h"
 #include "amos_scene_flow.h"
@@ -22,7 +23,7 @@ constexpr int kPnpMaxPoints = 4096;
 constexpr int kPnpThreads = 512, kPnpWaves = kPnpThreads / 64;
 constexpr int kPnpRound = 64;
 constexpr int kPnpStatus = 5;
-constexpr int kPnpScratch = 6;  // doubles per inlier: alphas[4], u, v
+constexpr int kPnpScratch = pnp::kEpnpScratch;  // doubles per inlier: alphas[4], u, v
 
 struct PnpArgs {
     const float *obj, *img;
@@ -45,10 +46,7 @@ __global__ __launch_bounds__(kPnpThreads) void k_pnp_ransac(const PnpArgs a)
     __shared__ double sModel[kPnpRound][12];
     __shared__ int sOk[kPnpRound], sCount[kPnpRound], sSub[kPnpRound][4];
     __shared__ double sBest[12];
-    __shared__ double sM[144], sE[144];   // 12 x 12 MtM and its eigenvectors
-    __shared__ double sS[9], sCw[4][3], sCi[9];
-    __shared__ double sCcs[3][4][3], sSum[3][6], sAbt[3][9], sRt[3][12], sRep[3];
-    __shared__ int sNeg[3];
+    __shared__ EpnpShared sE;
     __shared__ int sWave[kPnpWaves];
     __shared__ ransac::State sR;
     const int p = blockIdx.x, t = threadIdx.x;
@@ -149,140 +147,17 @@ __global__ __launch_bounds__(kPnpThreads) void k_pnp_ransac(const PnpArgs a)
     auto inlier = [&](int c) { return error_of(B, c) <= a.thresh2; };
     const int m = block_compact<kPnpThreads>(n, sWave, inlier, [&](int i, int c) { if (c >= 0) sIdx[c] = (uint16_t)i; });
     if (mask) block_compact<kPnpThreads>(cnt, sWave, selected, [&](int i, int c) { mask[i] = c >= 0 && inlier(c) ? 1 : 0; });
-    // ---- EPnP on the m inliers (m = maxGood >= 4)
+    // ---- EPnP on the m inliers (m = maxGood >= 4): amos_pnp_block.h, the image points through undistortPoints and back
     double *scr = a.scratch + (size_t)p * a.maxPoints * kPnpScratch;
-    auto pw_of = [&](int j, double *pw) {
+    block_epnp<kPnpThreads, pnp::PixelRefit>(sE, m, [&](int j, double *pw) {
         const float4 P = sP[sIdx[j]];
         pw[0] = P.x; pw[1] = P.y; pw[2] = P.z;
-    };
-    const double dm = (double)m;
-    if (t < 3) {  // control point 0: the centroid
-        double acc = 0.0, pw[3];
-        for (int j = 0; j < m; j++) { pw_of(j, pw); acc = acc + pw[t]; }
-        sCw[0][t] = fm::dvd(acc, dm);
-    }
-    __syncthreads();
-    if (t < 6) {  // PW0^T PW0, upper triangle (0,0) (0,1) (0,2) (1,1) (1,2) (2,2)
-        const int r = t < 3 ? 0 : (t < 5 ? 1 : 2), c = t < 3 ? t : (t < 5 ? t - 2 : 2);
-        double acc = 0.0, pw[3];
-        for (int j = 0; j < m; j++) { pw_of(j, pw); acc = acc + (pw[r] - sCw[0][r]) * (pw[c] - sCw[0][c]); }
-        sS[3 * r + c] = acc;
-        sS[3 * c + r] = acc;
-    }
-    __syncthreads();
+    }, [&](int j, float &u, float &v) { u = sP[sIdx[j]].w; v = sV[sIdx[j]]; }, fx, fy, cx, cy, scr);
     if (t == 0) {
-        double S[9], cw[4][3], ci[9];
-        for (int k = 0; k < 9; k++) S[k] = sS[k];
-        for (int k = 0; k < 3; k++) cw[0][k] = sCw[0][k];
-        pnp::control_points(S, m, cw, ci);
-        for (int i = 1; i < 4; i++) for (int k = 0; k < 3; k++) sCw[i][k] = cw[i][k];
-        for (int k = 0; k < 9; k++) sCi[k] = ci[k];
-    }
-    __syncthreads();
-    for (int j = t; j < m; j += kPnpThreads) {  // per inlier: alphas and the refit's image point
-        double pw[3], al[4], cw0[3] = {sCw[0][0], sCw[0][1], sCw[0][2]}, ci[9];
-        for (int k = 0; k < 9; k++) ci[k] = sCi[k];
-        pw_of(j, pw);
-        pnp::alphas(ci, cw0, pw[0], pw[1], pw[2], al);
-        double u, v;
-        pnp::pixel_refit(sP[sIdx[j]].w, sV[sIdx[j]], fx, fy, cx, cy, u, v);
-        double *o = scr + (size_t)j * kPnpScratch;
-        o[0] = al[0]; o[1] = al[1]; o[2] = al[2]; o[3] = al[3]; o[4] = u; o[5] = v;
-    }
-    __syncthreads();
-    if (t < 78) {  // MtM, one lane per upper-triangle entry (r, c), rows of M in order
-        int r = 0, k = t;
-        while (k >= 12 - r) { k -= 12 - r; r++; }
-        const int c = r + k;
-        double acc = 0.0;
-        for (int j = 0; j < m; j++) {
-            const double *o = scr + (size_t)j * kPnpScratch;
-            double r1, r2, c1, c2;
-            pnp::m_entries(o, o[4], o[5], fx, fy, cx, cy, r, r1, r2);
-            pnp::m_entries(o, o[4], o[5], fx, fy, cx, cy, c, c1, c2);
-            acc = acc + r1 * c1;
-            acc = acc + r2 * c2;
-        }
-        sM[12 * r + c] = acc;
-        sM[12 * c + r] = acc;
-    }
-    __syncthreads();
-    if (t == 0) {
-        pnp::jacobi_sym(sM, sE, 12);
-        int order[12];
-        pnp::eig_order(sM, 12, false, order);
-        double v[4][12], cw[4][3], L[60], rho[6];
-        for (int i = 0; i < 4; i++) for (int k = 0; k < 12; k++) v[i][k] = sE[12 * k + order[i]];
-        for (int i = 0; i < 4; i++) for (int k = 0; k < 3; k++) cw[i][k] = sCw[i][k];
-        pnp::l6x10_rho(v, cw, L, rho);
-        const double *o0 = scr;  // the first inlier decides solve_for_sign
-        for (int w = 0; w < 3; w++) {
-            double betas[4], ccs[4][3], pc[3];
-            pnp::betas_for(L, rho, w + 1, betas);
-            pnp::ccs_of(betas, v, ccs);
-            pnp::pc_of(o0, ccs, false, pc);
-            sNeg[w] = pc[2] < 0.0 ? 1 : 0;
-            for (int i = 0; i < 4; i++) for (int k = 0; k < 3; k++) sCcs[w][i][k] = ccs[i][k];
-        }
-    }
-    __syncthreads();
-    if (t < 18) {  // sums of pc (3) and pw (3) per beta set
-        const int w = t / 6, q = t % 6;
-        double ccs[4][3];
-        for (int i = 0; i < 4; i++) for (int k = 0; k < 3; k++) ccs[i][k] = sCcs[w][i][k];
-        double acc = 0.0;
-        for (int j = 0; j < m; j++) {
-            double x;
-            if (q < 3) {
-                double pc[3];
-                pnp::pc_of(scr + (size_t)j * kPnpScratch, ccs, sNeg[w] != 0, pc);
-                x = pc[q];
-            } else {
-                double pw[3];
-                pw_of(j, pw);
-                x = pw[q - 3];
-            }
-            acc = acc + x;
-        }
-        sSum[w][q] = fm::dvd(acc, dm);
-    }
-    __syncthreads();
-    if (t < 27) {  // ABt per beta set
-        const int w = t / 9, e = t % 9, r = e / 3, c = e % 3;
-        double ccs[4][3];
-        for (int i = 0; i < 4; i++) for (int k = 0; k < 3; k++) ccs[i][k] = sCcs[w][i][k];
-        double acc = 0.0;
-        for (int j = 0; j < m; j++) {
-            double pc[3], pw[3];
-            pnp::pc_of(scr + (size_t)j * kPnpScratch, ccs, sNeg[w] != 0, pc);
-            pw_of(j, pw);
-            acc = acc + (pc[r] - sSum[w][r]) * (pw[c] - sSum[w][3 + c]);
-        }
-        sAbt[w][e] = acc;
-    }
-    __syncthreads();
-    if (t < 3) {  // R, t and the mean reprojection error per beta set
-        double H[9], Rt[12];
-        for (int k = 0; k < 9; k++) H[k] = sAbt[t][k];
-        pnp::r_and_t(H, &sSum[t][0], &sSum[t][3], Rt);
-        double acc = 0.0;
-        for (int j = 0; j < m; j++) {
-            const double *o = scr + (size_t)j * kPnpScratch;
-            double pw[3];
-            pw_of(j, pw);
-            acc = acc + pnp::reproj_term(Rt, pw, o[4], o[5], fx, fy, cx, cy);
-        }
-        sRep[t] = fm::dvd(acc, dm);
-        for (int k = 0; k < 12; k++) sRt[t][k] = Rt[k];
-    }
-    __syncthreads();
-    if (t == 0) {
-        int N = 0;
-        if (sRep[1] < sRep[0]) N = 1;
-        if (sRep[2] < sRep[N]) N = 2;
+        const int N = epnp_pick(sE);
         bool ok = true;
-        for (int k = 0; k < 12; k++) ok = ok && pnp::finite_(sRt[N][k]);
-        for (int k = 0; k < 12; k++) Rout[k] = ok ? sRt[N][k] : sBest[k];
+        for (int k = 0; k < 12; k++) ok = ok && pnp::finite_(sE.Rt[N][k]);
+        for (int k = 0; k < 12; k++) Rout[k] = ok ? sE.Rt[N][k] : sBest[k];
         st[0] = 1; st[1] = sR.maxGood; st[2] = sR.iter; st[3] = n; st[4] = ok ? 1 : -1;
     }
 }

@@ -1,7 +1,9 @@
 // amos_pnp_core.h -- the arithmetic of cv::solvePnPRansac(obj, img, K, 0, rvec, tvec, false, iters, err, conf, inliers, SOLVEPNP_P3P)
 // (OpenCV 4.5: RANSACPointSetRegistrator with modelPoints 4 + PnPRansacCallback, p3p.cpp (Gao et al. 2003), then solvePnP(inliers,
 // SOLVEPNP_EPNP), epnp.cpp (Lepetit et al. 2009)) restated from the published algorithms, written from memory of that source: PARITY WITH
-// OPENCV UNPINNED.  Included by amos_pnp.hip (device) and amos_flow.hip (the shared per-point error); compilable as
+// OPENCV UNPINNED.  Included by amos_pnp.hip (device), amos_flow.hip (the shared per-point error) and
+// amos_reloc_pnp.hip (at the end of this file: the pieces of ORB-SLAM2's PnPsolver over the same EPnP, restated in
+// tests/reloc_pnp_restatement.py; tests/host_reloc_pnp compiles them for the host); compilable as
 // plain C++ for the host.  tests/pnp_restatement.py is the same arithmetic in Python doubles and the GPU tests hold the device to it bit
 // for bit, so every value is built from + - * / sqrt only, in the written order (+ - * as written, the library builds with
 // -ffp-contract=off; / and sqrt through fm::dvd / fm::sqr), every sum from 0.0 in index order.  Where OpenCV calls something else:
@@ -679,6 +681,203 @@ FM_HD double reproj_term(const double *Rt, const double *pw, double u, double v,
     const double inv_Zc = dvd(1.0, dot3(Rt + 6, pw) + Rt[11]);
     const double ue = uc + fu * Xc * inv_Zc, ve = vc + fv * Yc * inv_Zc;
     return sqr((u - ue) * (u - ue) + (v - ve) * (v - ve));
+}
+
+// ---- the image point an EPnP reads, as a policy: solvePnP's refit sends the pixel through undistortPoints and back (pixel_refit),
+// ORB-SLAM2's PnPsolver hands EPnP the pixel as it is
+struct PixelRefit {
+    static FM_HD void at(float u, float v, double fx, double fy, double cx, double cy, double &pu, double &pv) { pixel_refit(u, v, fx, fy, cx, cy, pu, pv); }
+};
+struct PixelDirect {
+    static FM_HD void at(float u, float v, double, double, double, double, double &pu, double &pv) { pu = (double)u; pv = (double)v; }
+};
+
+constexpr int kEpnpScratch = 6;  // doubles per point: alphas[4], u, v
+
+// EPnP on m >= 4 points on ONE thread: the steps and the summation order of the block-wide form (amos_pnp_block.h), every sum from 0.0 in
+// point order.  point_of(j, pw, u, v) gives point j (world doubles, pixel floats); scr holds kEpnpScratch * m doubles; MtM and E hold 144
+// doubles each (in LDS on the device).  Rt is the beta set with the smallest mean reprojection error, not tested for finiteness.
+// jacobi12(MtM, E) is the 12 x 12 eigen-decomposition: jacobi_sym on one thread (Jacobi12Serial), or a form that applies the same rotations
+// with several lanes (amos_pnp_block.h: the lanes of a group then call epnp_serial together, on the same points and the same MtM / E).
+struct Jacobi12Serial {
+    FM_HD void operator()(double *A, double *V) const { jacobi_sym(A, V, 12); }
+};
+
+template <class Pixel, class PointOf, class Jacobi12 = Jacobi12Serial>
+FM_HD void epnp_serial(int m, PointOf point_of, double fx, double fy, double cx, double cy, double *scr, double *MtM, double *E, double *Rt,
+                       Jacobi12 jacobi12 = Jacobi12())
+{
+    const double dm = (double)m;
+    double cw[4][3], S[9], ci[9], pw[3];
+    float uf, vf;
+    for (int c = 0; c < 3; c++) {
+        double acc = 0.0;
+        for (int j = 0; j < m; j++) { point_of(j, pw, uf, vf); acc = acc + pw[c]; }
+        cw[0][c] = dvd(acc, dm);
+    }
+    for (int r = 0; r < 3; r++)
+        for (int c = r; c < 3; c++) {
+            double acc = 0.0;
+            for (int j = 0; j < m; j++) { point_of(j, pw, uf, vf); acc = acc + (pw[r] - cw[0][r]) * (pw[c] - cw[0][c]); }
+            S[3 * r + c] = acc;
+            S[3 * c + r] = acc;
+        }
+    control_points(S, m, cw, ci);
+    for (int j = 0; j < m; j++) {
+        double *o = scr + (size_t)j * kEpnpScratch;
+        point_of(j, pw, uf, vf);
+        alphas(ci, cw[0], pw[0], pw[1], pw[2], o);
+        Pixel::at(uf, vf, fx, fy, cx, cy, o[4], o[5]);
+    }
+    for (int r = 0; r < 12; r++)
+        for (int c = r; c < 12; c++) {
+            double acc = 0.0;
+            for (int j = 0; j < m; j++) {
+                const double *o = scr + (size_t)j * kEpnpScratch;
+                double r1, r2, c1, c2;
+                m_entries(o, o[4], o[5], fx, fy, cx, cy, r, r1, r2);
+                m_entries(o, o[4], o[5], fx, fy, cx, cy, c, c1, c2);
+                acc = acc + r1 * c1;
+                acc = acc + r2 * c2;
+            }
+            MtM[12 * r + c] = acc;
+            MtM[12 * c + r] = acc;
+        }
+    jacobi12(MtM, E);
+    int order[12];
+    eig_order(MtM, 12, false, order);
+    double v[4][12], L[60], rho[6];
+    for (int i = 0; i < 4; i++)
+        for (int k = 0; k < 12; k++) v[i][k] = E[12 * k + order[i]];
+    l6x10_rho(v, cw, L, rho);
+    double bestRep = 0.0;
+    for (int w = 0; w < 3; w++) {
+        double betas[4], ccs[4][3], pc[3], sum[6], H[9], cand[12];
+        betas_for(L, rho, w + 1, betas);
+        ccs_of(betas, v, ccs);
+        pc_of(scr, ccs, false, pc);  // the first point decides solve_for_sign
+        const bool neg = pc[2] < 0.0;
+        for (int q = 0; q < 6; q++) {
+            double acc = 0.0;
+            for (int j = 0; j < m; j++) {
+                double x;
+                if (q < 3) { pc_of(scr + (size_t)j * kEpnpScratch, ccs, neg, pc); x = pc[q]; }
+                else { point_of(j, pw, uf, vf); x = pw[q - 3]; }
+                acc = acc + x;
+            }
+            sum[q] = dvd(acc, dm);
+        }
+        for (int e = 0; e < 9; e++) {
+            const int r = e / 3, c = e % 3;
+            double acc = 0.0;
+            for (int j = 0; j < m; j++) {
+                pc_of(scr + (size_t)j * kEpnpScratch, ccs, neg, pc);
+                point_of(j, pw, uf, vf);
+                acc = acc + (pc[r] - sum[r]) * (pw[c] - sum[3 + c]);
+            }
+            H[e] = acc;
+        }
+        r_and_t(H, sum, sum + 3, cand);
+        double acc = 0.0;
+        for (int j = 0; j < m; j++) {
+            const double *o = scr + (size_t)j * kEpnpScratch;
+            point_of(j, pw, uf, vf);
+            acc = acc + reproj_term(cand, pw, o[4], o[5], fx, fy, cx, cy);
+        }
+        const double rep = dvd(acc, dm);
+        if (w == 0 || rep < bestRep) {
+            bestRep = rep;
+            for (int k = 0; k < 12; k++) Rt[k] = cand[k];
+        }
+    }
+}
+
+// ---- ORB-SLAM2's PnPsolver (src/PnPsolver.cc:120-458), the per-iteration pieces; tests/reloc_pnp_restatement.py is the same in Python
+constexpr int kSolverMaxPoints = 4096;
+
+// SetRansacParameters(probability, minInliers, maxIterations, 4, epsilon, .) for N correspondences: the adjusted minInliers, maxIts and
+// epsilon.  log is fm::log_, pow(eps, 3) = (e e) e.  Where the reference converts a NaN or a huge double to int: 1 - e^3 <= 0 gives one
+// iteration, a log that is not negative or a quotient >= maxIterations gives maxIterations.
+FM_HD void solver_parameters(int N, double probability, int minInliers, int maxIterations, float epsilon, int &nMin, int &maxIts, float &eps)
+{
+    eps = epsilon;
+    const float scaled = fmul((float)N, eps);
+    nMin = scaled < 1073741824.f ? (int)scaled : 1073741824;  // (the reference's conversion of a larger float is undefined)
+    if (nMin < minInliers) nMin = minInliers;
+    if (nMin < 4) nMin = 4;
+    if (N > 0) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        const float q = __fdiv_rn((float)nMin, (float)N);
+#else
+        const float q = (float)nMin / (float)N;
+#endif
+        if (eps < q) eps = q;
+    }
+    int nIt;
+    if (nMin == N) nIt = 1;
+    else {
+        const double e = (double)eps, arg = fm::sub(1.0, fm::mul(fm::mul(e, e), e));
+        if (!(arg > 0)) nIt = 1;
+        else {
+            const double num = fm::log_(fm::sub(1.0, probability)), den = fm::log_(arg);
+            if (!(den < 0)) nIt = maxIterations;
+            else {
+                const double quot = dvd(num, den);
+                nIt = quot >= (double)maxIterations ? maxIterations : (int)ceil(quot);
+            }
+        }
+    }
+    nIt = nIt < maxIterations ? nIt : maxIterations;
+    maxIts = nIt > 1 ? nIt : 1;
+}
+
+// DUtils::Random::RandomInt(0, s - 1) with a 31-bit rand() drawn from the solver's generator
+FM_HD int solver_random_int(uint64_t &rng, int s)
+{
+    const uint32_t r = fm::rng_next(rng);
+    return (int)fm::mul(dvd((double)(r >> 1), 2147483648.0), (double)s);
+}
+
+// the four draws of one iteration (PnPsolver.cc:268-283) without the copied index list: the swap-with-back of slot k is one entry of a
+// substitution table (position -> the entry moved there), the latest entry of a position wins
+FM_HD void solver_draw4(uint64_t &rng, int N, int *idx)
+{
+    int pos[4], val[4];
+    for (int k = 0; k < 4; k++) {
+        const int s = N - k, randi = solver_random_int(rng, s);
+        int a = randi, b = s - 1;
+        bool fa = false, fb = false;
+        for (int q = k - 1; q >= 0; q--) {
+            if (!fa && pos[q] == randi) { a = val[q]; fa = true; }
+            if (!fb && pos[q] == s - 1) { b = val[q]; fb = true; }
+        }
+        idx[k] = a;
+        pos[k] = randi;
+        val[k] = b;
+    }
+}
+
+// CheckInliers for one correspondence: every operation rounded, the float stores of the reference kept
+FM_HD bool solver_inlier(const double *Rt, float Xf, float Yf, float Zf, float uf, float vf, double fu, double fv, double uc, double vc, float maxErr)
+{
+    const double X = Xf, Y = Yf, Z = Zf;
+    const float Xc = (float)fm::add(fm::add(fm::add(fm::mul(Rt[0], X), fm::mul(Rt[1], Y)), fm::mul(Rt[2], Z)), Rt[9]);
+    const float Yc = (float)fm::add(fm::add(fm::add(fm::mul(Rt[3], X), fm::mul(Rt[4], Y)), fm::mul(Rt[5], Z)), Rt[10]);
+    const float invZc = (float)dvd(1.0, fm::add(fm::add(fm::add(fm::mul(Rt[6], X), fm::mul(Rt[7], Y)), fm::mul(Rt[8], Z)), Rt[11]));
+    const double ue = fm::add(uc, fm::mul(fm::mul(fu, (double)Xc), (double)invZc));
+    const double ve = fm::add(vc, fm::mul(fm::mul(fv, (double)Yc), (double)invZc));
+    const float distX = (float)fm::sub((double)uf, ue), distY = (float)fm::sub((double)vf, ve);
+    const float error2 = fadd(fmul(distX, distX), fmul(distY, distY));
+    return error2 < maxErr;
+}
+
+// rows of [R | t] as float: what the reference's convertTo(CV_32F) and copyTo into mBestTcw / mRefinedTcw store
+FM_HD void solver_tcw(const double *Rt, float *Tcw)
+{
+    for (int r = 0; r < 3; r++) {
+        for (int c = 0; c < 3; c++) Tcw[4 * r + c] = (float)Rt[3 * r + c];
+        Tcw[4 * r + 3] = (float)Rt[9 + r];
+    }
 }
 
 }  // namespace pnp
