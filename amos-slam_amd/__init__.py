@@ -107,6 +107,9 @@ PROTOTYPES = {
     "amos_match_triangulation_batch_device": (_i, (_v, _v, _v, _v, _v, _i, _i, _i)),
     "amos_match_bow_kf": (_i, (_v, _v, _v, _f, _i, _v, _v)),
     "amos_match_triangulation": (_i, (_v, _v, _v, _i, _v, _v, _v, _i, _i, _i, _v, _v)),
+    "amos_sim3_state_bytes": (_z, (_i,)),
+    "amos_match_sim3_batch_device": (_i, (_v, _v)),
+    "amos_match_sim3": (_i, (_v, _v, _v, _i, _v, _v, _i, _v, _v, _v, _i, _v, _v, _v, _v, _v)),
     "amos_match_fuse_batch_device": (_i, (_v, _v)),
     "amos_match_fuse": (_i, (_v, _v, _i, _v, _i, _i, _v, _v, _v, _v, _v, _v, _i, _v, _v, _i, _i, _i, _v, _v, _v, _v, _v)),
     "amos_mask_pre_create": (_i, (_i, _v, _i, _i, _i, _v)),
@@ -1197,6 +1200,41 @@ assert KF_GEOMETRY_DTYPE.itemsize == 44
 KF_STATUS_BAD_INDEX, KF_STATUS_BAD_OCTAVE = 1, 2  # amos_bow_search_stats.status of the keyframe pair searches
 
 
+class Sim3(C.Structure):
+    """amos_sim3 (include/amos_frontend.h)."""
+    _fields_ = [("d_kps", C.c_void_p), ("d_counts", C.c_void_p), ("d_points", C.c_void_p), ("cameras", C.c_void_p), ("d_pairs_1", C.c_void_p),
+                ("d_pairs_2", C.c_void_p), ("d_match12", C.c_void_p), ("level_sigma2", C.c_void_p), ("params", C.c_void_p),
+                ("d_state", C.c_void_p), ("d_result", C.c_void_p), ("d_inlier", C.c_void_p), ("d_match_out", C.c_void_p),
+                ("n_frames", C.c_int32), ("n_pairs", C.c_int32), ("capacity", C.c_int32), ("n_levels", C.c_int32)]
+
+
+SIM3_POINT_SKIP = 1  # amos_sim3_point.flags
+SIM3_STATUS_OCTAVE, SIM3_STATUS_MATCH_INDEX, SIM3_STATUS_RESTARTED = 1, 2, 4  # amos_sim3_result.status
+SIM3_MAX_CORRESPONDENCES = 2048
+SIM3_POINT_DTYPE = np.dtype([("pos", "<f4", (3,)), ("flags", "<i4")])  # amos_sim3_point
+SIM3_CAMERA_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4")])
+SIM3_PARAMS_DTYPE = np.dtype([("probability", "<f8"), ("min_inliers", "<i4"), ("max_iterations", "<i4"), ("n_iterations", "<i4"),
+                              ("fix_scale", "<i4"), ("reset", "<i4"), ("enabled", "<i4"), ("seed", "<u8")])
+SIM3_RESULT_DTYPE = np.dtype([("R12", "<f4", (9,)), ("t12", "<f4", (3,)), ("s12", "<f4"), ("T12", "<f4", (16,)), ("code", "<i4"),
+                              ("has_sim3", "<i4"), ("no_more", "<i4"), ("n_inliers", "<i4"), ("n_correspondences", "<i4"),
+                              ("max_iterations", "<i4"), ("iterations", "<i4"), ("iterations_call", "<i4"), ("best_inliers", "<i4"),
+                              ("status", "<i4"), ("skipped", "<i4")])
+assert (SIM3_POINT_DTYPE.itemsize, SIM3_CAMERA_DTYPE.itemsize, SIM3_PARAMS_DTYPE.itemsize, SIM3_RESULT_DTYPE.itemsize) == (16, 64, 40, 160)
+
+
+def sim3_params(seed, reset=1, n_iterations=5, probability=0.99, min_inliers=20, max_iterations=300, fix_scale=0, enabled=1):
+    """One SIM3_PARAMS_DTYPE record with the parameters of LoopClosing.cc:390, 424 (SetRansacParameters(0.99, 20, 300), iterate(5))."""
+    p = np.zeros(1, SIM3_PARAMS_DTYPE)
+    p["probability"], p["min_inliers"], p["max_iterations"], p["n_iterations"] = probability, min_inliers, max_iterations, n_iterations
+    p["fix_scale"], p["reset"], p["enabled"], p["seed"] = fix_scale, reset, enabled, seed
+    return p[0]
+
+
+def sim3_state_bytes(capacity):
+    """Bytes of one pair's carried Sim3Solver state (amos_sim3_state_bytes)."""
+    return int(lib().amos_sim3_state_bytes(int(capacity)))
+
+
 FUSE_LOCAL, FUSE_SIM3 = 0, 1
 FUSE_CAMERA_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("Ow", "<f4", (3,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"),
                               ("cy", "<f4"), ("mbf", "<f4"), ("th", "<f4")])  # amos_fuse_camera
@@ -1495,6 +1533,43 @@ class OrbMatcher(_Handle):
                                            _p(inlier), _p(match), _p(found)), "amos_match_reloc_pnp")
         pose = bool(result[0]["has_pose"])
         return result[0], inlier, (match if pose else None), (found if pose else None), state
+
+    def sim3_batch_device(self, d_kps, d_counts, d_points, cameras, d_pairs_1, d_pairs_2, n_pairs, d_match12, level_sigma2, params, capacity,
+                          d_state, d_result, d_inlier, d_match_out):
+        """LoopClosing::ComputeSim3's Sim3Solver (Sim3Solver.cc:48-523), one iterate() call per pair (keyframe-1 slot, keyframe-2 slot) on
+        resident keyframes.  cameras: host SIM3_CAMERA_DTYPE records, one per frame slot; d_pairs_1 / d_pairs_2: device int32 [n_pairs];
+        params: host SIM3_PARAMS_DTYPE records, one per pair; d_state: n_pairs blocks of sim3_state_bytes(capacity) bytes; d_result:
+        SIM3_RESULT_DTYPE records.  Asynchronous on the matcher's stream."""
+        sig = np.ascontiguousarray(level_sigma2, np.float32)
+        cams = np.ascontiguousarray(cameras, SIM3_CAMERA_DTYPE).reshape(-1)
+        par = np.ascontiguousarray(params, SIM3_PARAMS_DTYPE).reshape(-1)
+        if len(par) != n_pairs:
+            raise ValueError("params holds one record per pair")
+        s = Sim3(d_kps, d_counts, d_points, cams.ctypes.data, d_pairs_1, d_pairs_2, d_match12, sig.ctypes.data, par.ctypes.data, d_state, d_result,
+                 d_inlier, d_match_out, len(cams), n_pairs, capacity, len(sig))
+        _check(self.L.amos_match_sim3_batch_device(self.h, C.byref(s)), "amos_match_sim3_batch_device")
+
+    def sim3(self, kps1, points1, kps2, points2, cameras, match12, level_sigma2, params, state=None):
+        """The same for ONE pair from host arrays (amos_match_sim3): returns (result, inlier, match_out, state).  state: the blob an earlier
+        call returned (params['reset'] = 0 goes on from it), or None for a fresh one.  match_out is None without a Sim3."""
+        kps1, kps2 = np.ascontiguousarray(kps1, KP_DTYPE), np.ascontiguousarray(kps2, KP_DTYPE)
+        points1, points2 = np.ascontiguousarray(points1, SIM3_POINT_DTYPE), np.ascontiguousarray(points2, SIM3_POINT_DTYPE)
+        cams = np.ascontiguousarray(cameras, SIM3_CAMERA_DTYPE).reshape(-1)
+        match12 = np.ascontiguousarray(match12, np.int32)
+        sig = np.ascontiguousarray(level_sigma2, np.float32)
+        par = np.ascontiguousarray(params, SIM3_PARAMS_DTYPE).reshape(1)
+        n1, n2 = len(kps1), len(kps2)
+        if len(points1) != n1 or len(points2) != n2 or len(match12) != n1 or len(cams) != 2:
+            raise ValueError("points and match12 hold one entry per keypoint, cameras two records")
+        nbytes = sim3_state_bytes(max(n1, 1))
+        state = np.zeros(nbytes, np.uint8) if state is None else np.ascontiguousarray(state, np.uint8).copy()
+        if len(state) != nbytes:
+            raise ValueError("state is not a blob of sim3_state_bytes(n1) bytes")
+        result = np.zeros(1, SIM3_RESULT_DTYPE)
+        inlier, match_out = np.zeros(n1, np.uint8), np.full(n1, -1, np.int32)
+        _check(self.L.amos_match_sim3(self.h, _p(kps1), _p(points1), n1, _p(kps2), _p(points2), n2, _p(cams), _p(match12), _p(sig), len(sig), _p(par),
+                                      _p(state), _p(result), _p(inlier), _p(match_out)), "amos_match_sim3")
+        return result[0], inlier, (match_out if result[0]["has_sim3"] else None), state
 
     def pose_optimization_batch_device(self, d_kps, d_counts, d_match, d_points, point_off, cameras, capacity, inv_level_sigma2, d_outlier,
                                        d_result, point_stride=12, flags_offset=-1, has_obs_bit=0, clear_outliers=False, d_u_right=None):

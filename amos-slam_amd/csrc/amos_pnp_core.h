@@ -3,7 +3,8 @@
 // SOLVEPNP_EPNP), epnp.cpp (Lepetit et al. 2009)) restated from the published algorithms, written from memory of that source: PARITY WITH
 // OPENCV UNPINNED.  Included by amos_pnp.hip (device), amos_flow.hip (the shared per-point error) and
 // amos_reloc_pnp.hip (at the end of this file: the pieces of ORB-SLAM2's PnPsolver over the same EPnP, restated in
-// tests/reloc_pnp_restatement.py; tests/host_reloc_pnp compiles them for the host); compilable as
+// tests/reloc_pnp_restatement.py; tests/host_reloc_pnp compiles them for the host; amos_sim3_core.h shares jacobi_sym, solver_iterations,
+// solver_random_of and solver_draw_of with them); compilable as
 // plain C++ for the host.  tests/pnp_restatement.py is the same arithmetic in Python doubles and the GPU tests hold the device to it bit
 // for bit, so every value is built from + - * / sqrt only, in the written order (+ - * as written, the library builds with
 // -ffp-contract=off; / and sqrt through fm::dvd / fm::sqr), every sum from 0.0 in index order.  Where OpenCV calls something else:
@@ -795,9 +796,21 @@ FM_HD void epnp_serial(int m, PointOf point_of, double fx, double fy, double cx,
 // ---- ORB-SLAM2's PnPsolver (src/PnPsolver.cc:120-458), the per-iteration pieces; tests/reloc_pnp_restatement.py is the same in Python
 constexpr int kSolverMaxPoints = 4096;
 
+// the iteration count of a SetRansacParameters: ceil(log(1 - p) / log(1 - eps^3)) (PnPsolver.cc:213, Sim3Solver.cc:182).  log is fm::log_,
+// pow(eps, 3) = (e e) e.  Where the reference converts a NaN or a huge double to int: 1 - e^3 <= 0 gives one iteration, a log that is not
+// negative or a quotient >= maxIterations gives maxIterations.
+FM_HD int solver_iterations(float eps, double probability, int maxIterations)
+{
+    const double e = (double)eps, arg = fm::sub(1.0, fm::mul(fm::mul(e, e), e));
+    if (!(arg > 0)) return 1;
+    const double num = fm::log_(fm::sub(1.0, probability)), den = fm::log_(arg);
+    if (!(den < 0)) return maxIterations;
+    const double quot = dvd(num, den);
+    return quot >= (double)maxIterations ? maxIterations : (int)ceil(quot);
+}
+
 // SetRansacParameters(probability, minInliers, maxIterations, 4, epsilon, .) for N correspondences: the adjusted minInliers, maxIts and
-// epsilon.  log is fm::log_, pow(eps, 3) = (e e) e.  Where the reference converts a NaN or a huge double to int: 1 - e^3 <= 0 gives one
-// iteration, a log that is not negative or a quotient >= maxIterations gives maxIterations.
+// epsilon.
 FM_HD void solver_parameters(int N, double probability, int minInliers, int maxIterations, float epsilon, int &nMin, int &maxIts, float &eps)
 {
     eps = epsilon;
@@ -813,40 +826,28 @@ FM_HD void solver_parameters(int N, double probability, int minInliers, int maxI
 #endif
         if (eps < q) eps = q;
     }
-    int nIt;
-    if (nMin == N) nIt = 1;
-    else {
-        const double e = (double)eps, arg = fm::sub(1.0, fm::mul(fm::mul(e, e), e));
-        if (!(arg > 0)) nIt = 1;
-        else {
-            const double num = fm::log_(fm::sub(1.0, probability)), den = fm::log_(arg);
-            if (!(den < 0)) nIt = maxIterations;
-            else {
-                const double quot = dvd(num, den);
-                nIt = quot >= (double)maxIterations ? maxIterations : (int)ceil(quot);
-            }
-        }
-    }
+    int nIt = nMin == N ? 1 : solver_iterations(eps, probability, maxIterations);
     nIt = nIt < maxIterations ? nIt : maxIterations;
     maxIts = nIt > 1 ? nIt : 1;
 }
 
-// DUtils::Random::RandomInt(0, s - 1) with a 31-bit rand() drawn from the solver's generator
-FM_HD int solver_random_int(uint64_t &rng, int s)
-{
-    const uint32_t r = fm::rng_next(rng);
-    return (int)fm::mul(dvd((double)(r >> 1), 2147483648.0), (double)s);
-}
+// DUtils::Random::RandomInt(0, s - 1) with a 31-bit rand() drawn from the solver's generator (r: its next 32 bits)
+FM_HD int solver_random_of(uint32_t r, int s) { return (int)fm::mul(dvd((double)(r >> 1), 2147483648.0), (double)s); }
+FM_HD int solver_random_int(uint64_t &rng, int s) { return solver_random_of(fm::rng_next(rng), s); }
 
-// the four draws of one iteration (PnPsolver.cc:268-283) without the copied index list: the swap-with-back of slot k is one entry of a
-// substitution table (position -> the entry moved there), the latest entry of a position wins
-FM_HD void solver_draw4(uint64_t &rng, int N, int *idx)
+// the K draws of one iteration (PnPsolver.cc:268-283 with four, Sim3Solver.cc:228-249 with three) without the copied index list: the
+// swap-with-back of slot k is one entry of a substitution table (position -> the entry moved there), the latest entry of a position wins.
+// next() hands out the generator's 32-bit outputs in order (drawn ahead by one lane, or straight from the state)
+template <int K, class Next>
+FM_HD void solver_draw_of(Next next, int N, int *idx)
 {
-    int pos[4], val[4];
-    for (int k = 0; k < 4; k++) {
-        const int s = N - k, randi = solver_random_int(rng, s);
+    int pos[K], val[K];
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+        const int s = N - k, randi = solver_random_of(next(), s);
         int a = randi, b = s - 1;
         bool fa = false, fb = false;
+#pragma unroll
         for (int q = k - 1; q >= 0; q--) {
             if (!fa && pos[q] == randi) { a = val[q]; fa = true; }
             if (!fb && pos[q] == s - 1) { b = val[q]; fb = true; }
@@ -856,6 +857,12 @@ FM_HD void solver_draw4(uint64_t &rng, int N, int *idx)
         val[k] = b;
     }
 }
+template <int K>
+FM_HD void solver_draw(uint64_t &rng, int N, int *idx)
+{
+    solver_draw_of<K>([&rng]() { return fm::rng_next(rng); }, N, idx);
+}
+FM_HD void solver_draw4(uint64_t &rng, int N, int *idx) { solver_draw<4>(rng, N, idx); }
 
 // CheckInliers for one correspondence: every operation rounded, the float stores of the reference kept
 FM_HD bool solver_inlier(const double *Rt, float Xf, float Yf, float Zf, float uf, float vf, double fu, double fv, double uc, double vc, float maxErr)

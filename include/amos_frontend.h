@@ -948,6 +948,96 @@ int amos_match_triangulation(amos_match *m, const struct amos_bow_view *k1, cons
                              const amos_kf_geometry *geometry, const float *scale_factors, const float *level_sigma2, int n_levels,
                              int only_stereo, int check_orientation, int32_t *match12, amos_bow_search_stats *stats);
 
+/* ---------------------------------------------------------------- loop-closing Sim3 ----------- */
+
+/* Step 2 of LoopClosing::ComputeSim3's candidate loop (LoopClosing.cc:389-447): ORB-SLAM2's Sim3Solver (src/Sim3Solver.cc:48-523: the
+ * constructor, SetRansacParameters, iterate, ComputeSim3 after Horn 1987, CheckInliers) for a batch of PAIRS (keyframe-1 slot, keyframe-2
+ * slot) of resident keyframes, ONE iterate() call per pair and launch, and the loop of LoopClosing.cc:440-447 behind it.  The arithmetic is
+ * amos-slam_amd/csrc/amos_sim3_core.h (its header lists the convention that fixes each cv::Mat expression): PARITY WITH THE REFERENCE'S
+ * OPENCV-BACKED ARITHMETIC UNPINNED; what is pinned, bit for bit, is tests/sim3_restatement.py.
+ *
+ * Correspondences (the constructor): keyframe-1 features i1 < d_counts[slot 1] in ascending order with d_match12[i1] = j >= 0 whose point
+ * records d_points[slot 1][i1] and d_points[slot 2][j] do not carry AMOS_SIM3_POINT_SKIP (no point, or isBad()).  X3Dc = Rcw * pos + tcw
+ * with each keyframe's camera, the image points by FromCameraToImage, maxErr = (float)(9.210 * (double) level_sigma2[octave]) with the
+ * octaves of d_kps[slot 1][i1] and d_kps[slot 2][j].  An octave outside [0, n_levels) skips the feature and sets bit 0 of status, a j
+ * outside [0, d_counts[slot 2]) skips it and sets bit 1.  More than 2048 correspondences: code = -3; a slot outside [0, n_frames):
+ * code = -4; with either no other output is written.
+ * SetRansacParameters(probability, min_inliers, max_iterations) runs with reset = 1 (and when the carried state is not a solver of as
+ * many correspondences: bit 2 of status; a reset does not read the state); min_inliers and fix_scale of that call are kept in the state.
+ * The reference's unseeded rand() is one cv::RNG state per solver, seeded with `seed` at a reset and carried; every iteration consumes
+ * exactly three draws.
+ * iterate(n_iterations): N < min_inliers gives no_more at once, nothing drawn.  The loop runs while mnIterations < max_iterations (as
+ * adjusted) and nCurrentIterations < n_iterations.  An iteration whose inlier count is >= mnBestInliers becomes the best (the LAST of
+ * equal maxima stands); the call ends with that Sim3 at the first one that becomes the best with more than min_inliers inliers
+ * (strictly), and later iterations leave no trace.  Without a Sim3, no_more is set when mnIterations >= max_iterations.  A hypothesis whose
+ * quaternion has an imaginary part of norm exactly 0 has no inliers (the reference scores a NaN rotation there).  NaN is stored as
+ * 0x7FC00000.
+ * A carried state holds the best inlier set by correspondence index: the inputs of a pair must be the same in every call on its state,
+ * and d_match_out must not be d_match12. */
+typedef struct amos_sim3_point {        /* a keyframe's map point by feature: 16 bytes */
+    float pos[3];                       /* GetWorldPos() */
+    int32_t flags;                      /* bit 0 (AMOS_SIM3_POINT_SKIP): no point, or isBad() */
+} amos_sim3_point;
+#define AMOS_SIM3_POINT_SKIP 1
+
+typedef struct amos_sim3_camera {       /* per keyframe: 64 bytes */
+    float Rcw[9], tcw[3];               /* GetRotation(), GetTranslation() */
+    float fx, fy, cx, cy;               /* mK */
+} amos_sim3_camera;
+
+typedef struct amos_sim3_params {       /* per pair: 40 bytes */
+    double probability;                 /* in (0, 1): 0.99 */
+    int32_t min_inliers, max_iterations; /* 20, 300 (LoopClosing.cc:390); min_inliers >= 3, max_iterations 1 .. 65536 */
+    int32_t n_iterations;               /* iterate's argument: 5; 1 .. 65536 */
+    int32_t fix_scale;                  /* mbFixScale */
+    int32_t reset;                      /* 1: constructor + SetRansacParameters first; 0: go on from d_state */
+    int32_t enabled;                    /* 0: only the result record is written (zeros, skipped = 1) */
+    uint64_t seed;                      /* the generator's state at a reset */
+} amos_sim3_params;
+
+typedef struct amos_sim3_result {       /* per pair: 160 bytes */
+    float R12[9], t12[3], s12, T12[16]; /* mBestRotation, mBestTranslation, mBestScale, mBestT12 row-major; zeros without a Sim3 */
+    int32_t code;                       /* 0; -3: more than 2048 correspondences; -4: a slot outside the frames */
+    int32_t has_sim3, no_more;          /* !Scm.empty(), bNoMore */
+    int32_t n_inliers;                  /* nInliers (0 without a Sim3) */
+    int32_t n_correspondences;          /* N */
+    int32_t max_iterations;             /* mRansacMaxIts as SetRansacParameters adjusted it */
+    int32_t iterations, iterations_call; /* mnIterations, nCurrentIterations */
+    int32_t best_inliers;               /* mnBestInliers */
+    int32_t status;                     /* bit 0: an octave outside the table; bit 1: a match outside keyframe 2; bit 2: state restarted */
+    int32_t skipped;                    /* 1: enabled was 0 */
+} amos_sim3_result;
+
+typedef struct amos_sim3 {
+    const amos_keypoint *d_kps;         /* [frames][capacity]: mvKeysUn (octave is read) */
+    const int32_t *d_counts;            /* [frames] */
+    const amos_sim3_point *d_points;    /* [frames][capacity]: GetMapPointMatches() by feature */
+    const amos_sim3_camera *cameras;    /* host, n_frames entries */
+    const int32_t *d_pairs_1, *d_pairs_2; /* [n_pairs] frame slots: the arrays of amos_kf_pair_search */
+    const int32_t *d_match12;           /* [pairs][capacity]: SearchByBoW(KF, KF)'s rows, read in place */
+    const float *level_sigma2;          /* host, n_levels entries (mvLevelSigma2) */
+    const amos_sim3_params *params;     /* host, n_pairs entries */
+    void *d_state;                      /* in / out, [pairs] blocks of amos_sim3_state_bytes(capacity) bytes: opaque */
+    amos_sim3_result *d_result;         /* out, [pairs] */
+    uint8_t *d_inlier;                  /* out, [pairs][capacity]: vbInliers by keyframe-1 feature; always written, all zero without a Sim3 */
+    int32_t *d_match_out;               /* out with a Sim3, [pairs][capacity]: d_match12[i1] where i1 is an inlier, else -1: the row
+                                           SearchBySim3 starts from */
+    int32_t n_frames, n_pairs, capacity, n_levels;
+} amos_sim3;
+size_t amos_sim3_state_bytes(int capacity);
+/* Asynchronous on the matcher's stream (the host arrays are consumed before the call returns); ONE launch, one work-group per pair.
+ * AMOS_ERR_INVALID, before the device is touched, for a NULL handle or pointer, n_pairs < 1, n_frames < 1, a capacity outside 1 .. 65536,
+ * n_levels outside 1 .. AMOS_MAX_LEVELS, a camera that is not finite, a probability outside (0, 1), min_inliers < 3 (so that
+ * N >= min_inliers always leaves three indices to draw, which the reference takes for granted), a max_iterations or n_iterations
+ * outside 1 .. 65536.  The host reads d_result; rows and flags stay on the device for SearchBySim3 and OptimizeSim3. */
+int amos_match_sim3_batch_device(amos_match *m, const amos_sim3 *s);
+/* The host form for a C++ drop-in (amos-slam_amd/host/KeyFrameSim3.h): ONE pair, host arrays in and out, synchronous: one upload, the
+ * launch, one download.  Keyframe 1: kps1 / points1 [n1]; keyframe 2: kps2 / points2 [n2]; cameras [2]; match12 [n1].  state:
+ * amos_sim3_state_bytes(n1) bytes, read (reset = 0) and written.  inlier [n1] is always written, match_out [n1] only with a Sim3. */
+int amos_match_sim3(amos_match *m, const amos_keypoint *kps1, const amos_sim3_point *points1, int n1, const amos_keypoint *kps2,
+                    const amos_sim3_point *points2, int n2, const amos_sim3_camera *cameras, const int32_t *match12, const float *level_sigma2,
+                    int n_levels, const amos_sim3_params *params, void *state, amos_sim3_result *result, uint8_t *inlier, int32_t *match_out);
+
 /* ---------------------------------------------------------------- fuse search ---------------- */
 
 /* ORBmatcher::Fuse for a batch of PAIRS of resident keyframes: pair p is (keyframe pair_frame[p], the points point_first[p] ..
