@@ -110,6 +110,8 @@ PROTOTYPES = {
     "amos_sim3_state_bytes": (_z, (_i,)),
     "amos_match_sim3_batch_device": (_i, (_v, _v)),
     "amos_match_sim3": (_i, (_v, _v, _v, _i, _v, _v, _i, _v, _v, _v, _i, _v, _v, _v, _v, _v)),
+    "amos_match_sim3_search_batch_device": (_i, (_v, _v)),
+    "amos_match_sim3_search": (_i, (_v, _v, _v, _v, _v, _v, _v, _v, _i, _v, _v, _v, _v, _v)),
     "amos_match_fuse_batch_device": (_i, (_v, _v)),
     "amos_match_fuse": (_i, (_v, _v, _i, _v, _i, _i, _v, _v, _v, _v, _v, _v, _i, _v, _v, _i, _i, _i, _v, _v, _v, _v, _v)),
     "amos_mask_pre_create": (_i, (_i, _v, _i, _i, _i, _v)),
@@ -1235,6 +1237,30 @@ def sim3_state_bytes(capacity):
     return int(lib().amos_sim3_state_bytes(int(capacity)))
 
 
+class Sim3Search(C.Structure):
+    """amos_sim3_search (include/amos_frontend.h)."""
+    _fields_ = [("d_kps", C.c_void_p), ("d_desc", C.c_void_p), ("d_counts", C.c_void_p), ("d_cell_start", C.c_void_p), ("d_items", C.c_void_p),
+                ("d_points", C.c_void_p), ("cameras", C.c_void_p), ("scale_factors", C.c_void_p), ("d_pairs_1", C.c_void_p),
+                ("d_pairs_2", C.c_void_p), ("pairs", C.c_void_p), ("d_sim3", C.c_void_p), ("d_match12", C.c_void_p), ("d_match_out", C.c_void_p),
+                ("d_match1", C.c_void_p), ("d_match2", C.c_void_p), ("d_stats", C.c_void_p), ("n_frames", C.c_int32), ("n_pairs", C.c_int32),
+                ("capacity", C.c_int32), ("n_levels", C.c_int32), ("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float),
+                ("max_y", C.c_float)]
+
+
+SIM3_SEARCH_MATCHED_ELSEWHERE = -2  # AMOS_SIM3_SEARCH_MATCHED_ELSEWHERE
+SIM3_SEARCH_PAIR_DTYPE = np.dtype([("R12", "<f4", (9,)), ("t12", "<f4", (3,)), ("s12", "<f4"), ("th", "<f4"), ("enabled", "<i4")])  # amos_sim3_search_pair
+SIM3_SEARCH_STATS_DTYPE = np.dtype([("n_found", "<i4"), ("n_in_view_12", "<i4"), ("n_in_view_21", "<i4"), ("n_single_12", "<i4"),
+                                    ("n_single_21", "<i4"), ("skipped", "<i4"), ("code", "<i4"), ("pad", "<i4")])  # amos_sim3_search_stats
+assert (SIM3_SEARCH_PAIR_DTYPE.itemsize, SIM3_SEARCH_STATS_DTYPE.itemsize) == (60, 32)
+
+
+def sim3_search_pair(R12, t12, s12, th=7.5, enabled=1):
+    """One SIM3_SEARCH_PAIR_DTYPE record (th: 7.5 in LoopClosing.cc:454)."""
+    p = np.zeros(1, SIM3_SEARCH_PAIR_DTYPE)
+    p["R12"], p["t12"], p["s12"], p["th"], p["enabled"] = np.asarray(R12, np.float32).reshape(9), t12, s12, th, enabled
+    return p[0]
+
+
 FUSE_LOCAL, FUSE_SIM3 = 0, 1
 FUSE_CAMERA_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("Ow", "<f4", (3,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"),
                               ("cy", "<f4"), ("mbf", "<f4"), ("th", "<f4")])  # amos_fuse_camera
@@ -1727,6 +1753,42 @@ class OrbMatcher(_Handle):
                                       n_out, _p(sf), _p(s2), len(sf), mode, max_dist, _p(query), _p(in_view), _p(best_idx), _p(best_dist),
                                       _p(stats)), "amos_match_fuse")
         return query, in_view, best_idx, best_dist, stats
+
+    def sim3_search_batch_device(self, d_kps, d_desc, d_counts, d_cell_start, d_items, d_points, cameras, d_pairs_1, d_pairs_2, pairs, d_match12,
+                                 d_match_out, d_match1, d_match2, d_stats, capacity, scale_factors, bounds=(0.0, 640.0, 0.0, 480.0), d_sim3=None):
+        """ORBmatcher::SearchBySim3 (ORBmatcher.cc:1314-1555) for pairs (keyframe-1 slot, keyframe-2 slot) of resident keyframes: both
+        directions and the agreement pass in two launches.  cameras: host SIM3_CAMERA_DTYPE records, one per frame slot; pairs: host
+        SIM3_SEARCH_PAIR_DTYPE records, one per pair; d_sim3: the solver's d_result (its Sim3 replaces the records'), or None; d_match_out
+        may be d_match12.  Asynchronous on the matcher's stream."""
+        sf = np.ascontiguousarray(scale_factors, np.float32)
+        cams = np.ascontiguousarray(cameras, SIM3_CAMERA_DTYPE).reshape(-1)
+        prs = np.ascontiguousarray(pairs, SIM3_SEARCH_PAIR_DTYPE).reshape(-1)
+        s = Sim3Search(d_kps, d_desc, d_counts, d_cell_start, d_items, d_points, cams.ctypes.data, sf.ctypes.data, d_pairs_1, d_pairs_2,
+                       prs.ctypes.data, d_sim3, d_match12, d_match_out, d_match1, d_match2, d_stats, len(cams), len(prs), capacity, len(sf), *bounds)
+        _check(self.L.amos_match_sim3_search_batch_device(self.h, C.byref(s)), "amos_match_sim3_search_batch_device")
+
+    def sim3_search(self, kf1, points1, kf2, points2, cameras, pair, scale_factors, match12, bounds=(0.0, 640.0, 0.0, 480.0)):
+        """The same for ONE pair from host arrays (amos_match_sim3_search): kf1 / kf2 are dicts with keys_un and desc, cameras two
+        SIM3_CAMERA_DTYPE records (KF1's, KF2's).  Returns (match_out, match1, match2, stats); a skipped pair returns match12 and -1 rows."""
+        keep, views = [], (FrameView * 2)()
+        for v, k in zip(views, (kf1, kf2)):
+            kp, d = np.ascontiguousarray(k["keys_un"], KP_DTYPE), np.ascontiguousarray(k["desc"], np.uint8).reshape(-1, 32)
+            keep.append((kp, d))
+            v.n, v.keys_un, v.descriptors, v.u_right = len(kp), kp.ctypes.data, d.ctypes.data, None
+            v.min_x, v.max_x, v.min_y, v.max_y = bounds
+        points1, points2 = np.ascontiguousarray(points1, MAP_POINT_DTYPE), np.ascontiguousarray(points2, MAP_POINT_DTYPE)
+        n1, n2 = views[0].n, views[1].n
+        if len(points1) != n1 or len(points2) != n2 or len(match12) != n1:
+            raise ValueError("one point record per feature of each keyframe and one row entry per feature of keyframe 1")
+        cams = np.ascontiguousarray(cameras, SIM3_CAMERA_DTYPE).reshape(2)
+        pr = np.ascontiguousarray(pair, SIM3_SEARCH_PAIR_DTYPE).reshape(1)
+        sf = np.ascontiguousarray(scale_factors, np.float32)
+        match12 = np.ascontiguousarray(match12, np.int32)
+        match_out, match1, match2 = match12.copy(), np.full(n1, -1, np.int32), np.full(n2, -1, np.int32)
+        stats = np.zeros(1, SIM3_SEARCH_STATS_DTYPE)
+        _check(self.L.amos_match_sim3_search(self.h, C.addressof(views[0]), _p(points1), C.addressof(views[1]), _p(points2), _p(cams), _p(pr), _p(sf),
+                                             len(sf), _p(match12), _p(match_out), _p(match1), _p(match2), _p(stats)), "amos_match_sim3_search")
+        return match_out, match1, match2, stats[0]
 
     def sync(self):
         _check(self.L.amos_match_sync(self.h), "amos_match_sync")

@@ -137,7 +137,7 @@ __device__ __forceinline__ amos_best2 best2_from_keys(unsigned best, unsigned se
 // reference walks the cells x-major, then y, then insertion order = ascending CSR position, and its strict-< updates keep the FIRST of
 // equal distances: a min-reduction over keys (dist << 16 | CSR position) gives the same best two whatever the evaluation order.  All lanes
 // of a group call it; q is read only where `active`, the group's first lane writes *out (if not null); keep(idx) is the search's own filter.
-// lanes_window_keys leaves the two keys in every lane of the group (amos_fuse.hip keeps no record in memory).
+// lanes_window_keys leaves the two keys in every lane of the group (amos_fuse.hip and amos_sim3_search.hip keep no record in memory).
 template <class Keep>
 __device__ __forceinline__ void lanes_window_keys(const ProjArgs &a, const FrameView &fv, const WindowQuery &q, bool active, int sub, int initDist,
                                                   Keep keep, unsigned &best, unsigned &second)

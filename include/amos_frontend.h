@@ -1038,6 +1038,91 @@ int amos_match_sim3(amos_match *m, const amos_keypoint *kps1, const amos_sim3_po
                     const amos_sim3_point *points2, int n2, const amos_sim3_camera *cameras, const int32_t *match12, const float *level_sigma2,
                     int n_levels, const amos_sim3_params *params, void *state, amos_sim3_result *result, uint8_t *inlier, int32_t *match_out);
 
+/* ---------------------------------------------------------------- loop-closing Sim3 search ---- */
+
+/* Step 3 of LoopClosing::ComputeSim3's candidate loop (LoopClosing.cc:454): ORBmatcher::SearchBySim3 (ORBmatcher.cc:1314-1555) for a batch
+ * of PAIRS of resident keyframes.  Pair p is keyframe slot d_pairs_1[p] (KF1, the current keyframe), slot d_pairs_2[p] (KF2, the candidate)
+ * -- the arrays of amos_kf_pair_search and amos_sim3 -- and one Sim3.  N1 and N2 are min(d_counts[slot], capacity).  TWO launches: direction
+ * 1 (KF1's points into KF2), then direction 2 with the agreement pass; nothing returns to the host.  PARITY WITH THE REFERENCE'S
+ * OPENCV-BACKED ARITHMETIC UNPINNED; what is pinned, entry for entry, is tests/sim3_search_restatement.py.
+ *
+ * The Sim3 of a pair: pairs[p] (host), or with d_sim3 != NULL row p of the solver's amos_sim3_result array, read on the device (R12, t12, s12
+ * are its first 13 floats); pairs[p] still supplies th and enabled.  A pair with enabled == 0, or whose d_sim3 row has has_sim3 == 0 or
+ * code != 0, is SKIPPED: only its stats record is written (skipped = 1, counts 0), its rows in every output array are left untouched and
+ * its d_match12 row is not read (the solver writes d_match_out only with a Sim3).  A slot outside [0, n_frames): code = -4 in the stats
+ * record, nothing else is written for that pair.
+ *
+ * The row: d_match12 [pairs][capacity] in, d_match_out [pairs][capacity] out; d_match_out == d_match12 is allowed (the chained use behind
+ * amos_match_sim3_batch_device).  Entry i1 < N1: -1 free; j in [0, N2): vpMatches12[i1] is KF2's point at feature j (vbAlreadyMatched1[i1]
+ * and vbAlreadyMatched2[j]); any other value: matched, but GetIndexInKeyFrame(pKF2) is outside [0, N2) (vbAlreadyMatched1[i1] only;
+ * AMOS_SIM3_SEARCH_MATCHED_ELSEWHERE for a drop-in's use).  On return d_match_out[i1] is the input entry, or idx2 where the agreement pass
+ * accepted (i1, idx2), which can only happen where the entry was -1.  Entries from N1 on are copied when the arrays differ, otherwise ignored.
+ *
+ * Hops (:1333-1335):  sR12[r][c] = (float) ((double) s12 * R12[r][c]);  sR21[r][c] = (float) ((1.0 / (double) s12) * R12[c][r]);
+ *   t21[r] = (float) (-(((double) sR21[r][0] * t12[0] + (double) sR21[r][1] * t12[1]) + (double) sR21[r][2] * t12[2]));  t12 as given.
+ * One direction (:1367-1449 into KF2 with (R1w, t1w) then (sR21, t21); :1456-1533 into KF1 with (R2w, t2w) then (sR12, t12)), for every
+ * source feature that has a point without AMOS_MAP_POINT_SKIP and is not already matched on its side:
+ *   pc = hop (Rfw * P + tfw)   two gemms: per row ((R0 P0 + R1 P1) + R2 P2) + t in double, one rounding to float;  pc.z < 0.0f is out
+ *   invz = 1.0f / z;  x = X * invz;  u = fx * x + cx;  v alike, with KF1'S INTRINSICS IN BOTH DIRECTIONS (:1318-1321); every operation
+ *   rounded, nothing fused
+ *   KeyFrame::IsInImage: u >= min_x && u < max_x && v >= min_y && v < max_y; a projection that is not finite fails it
+ *   dist3D = (float) sqrt(((double) X^2 + (double) Y^2) + (double) Z^2) of pc (cv::norm)
+ *   dist3D < 0.8f * min_distance || dist3D > 1.2f * max_distance is out;  there is no viewing-angle test
+ *   level = the table form of MapPoint::PredictScale (see "local map search" and "fuse search")
+ * Search: exactly the AMOS_FUSE_SIM3 search with radius th * scale_factors[level]: KeyFrame::GetFeaturesInArea without a level filter,
+ * octaves level - 1 .. level, no chi-square gate, the nearest descriptor by strict < in CSR order, accepted at bestDist <= AMOS_TH_HIGH.
+ * The results are vnMatch1[i1] and vnMatch2[i2], each the accepted feature or -1.
+ * Agreement (:1539-1552): i1 takes idx2 = vnMatch1[i1] when idx2 >= 0 && vnMatch2[idx2] == i1; n_found counts those. */
+#define AMOS_SIM3_SEARCH_MATCHED_ELSEWHERE (-2)
+struct amos_frame_view;                 /* include/amos_host_types.h */
+typedef struct amos_sim3_search_pair {  /* per pair: 60 bytes */
+    float R12[9], t12[3], s12;          /* read when d_sim3 == NULL */
+    float th;                           /* 7.5 in LoopClosing.cc:454 */
+    int32_t enabled;                    /* 0: the pair is skipped */
+} amos_sim3_search_pair;
+typedef struct amos_sim3_search_stats { /* per pair: 32 bytes */
+    int32_t n_found;                    /* the reference's return value */
+    int32_t n_in_view_12, n_in_view_21; /* source features that reached their window, per direction */
+    int32_t n_single_12, n_single_21;   /* accepted features per direction, before the agreement */
+    int32_t skipped;                    /* 1: enabled == 0 or no Sim3 in d_sim3 */
+    int32_t code;                       /* 0; -4: a slot outside the frames */
+    int32_t pad;
+} amos_sim3_search_stats;
+typedef struct amos_sim3_search {
+    const amos_keypoint *d_kps;         /* [frames][capacity]: mvKeysUn */
+    const uint8_t *d_desc;              /* [frames][capacity][32] */
+    const int32_t *d_counts;            /* [frames] */
+    const int32_t *d_cell_start;        /* [frames][64*48+1]       (amos_frame_grid_build_batch_device) */
+    const int32_t *d_items;             /* [frames][capacity] */
+    const amos_map_point *d_points;     /* [frames][capacity]: GetMapPointMatches() by feature; AMOS_MAP_POINT_SKIP: no point, or isBad();
+                                           pos, min_distance, max_distance (raw) and desc are read, normal is not */
+    const amos_sim3_camera *cameras;    /* host, n_frames entries: the record the solver takes */
+    const float *scale_factors;         /* host, n_levels entries: one table and one set of bounds per call */
+    const int32_t *d_pairs_1, *d_pairs_2; /* [n_pairs] frame slots */
+    const amos_sim3_search_pair *pairs; /* host, n_pairs entries */
+    const amos_sim3_result *d_sim3;     /* [n_pairs] or NULL: amos_match_sim3_batch_device's d_result, read in place */
+    const int32_t *d_match12;           /* [pairs][capacity] */
+    int32_t *d_match_out;               /* [pairs][capacity]; may be d_match12 */
+    int32_t *d_match1;                  /* out, [pairs][capacity]: vnMatch1, -1 from N1 on */
+    int32_t *d_match2;                  /* out, [pairs][capacity]: vnMatch2, -1 from N2 on */
+    amos_sim3_search_stats *d_stats;    /* out, [pairs] */
+    int32_t n_frames, n_pairs, capacity, n_levels;
+    float min_x, max_x, min_y, max_y;   /* KeyFrame::mnMinX .. mnMaxY */
+} amos_sim3_search;
+/* Asynchronous on the matcher's stream; the host arrays are consumed before the call returns.  AMOS_ERR_INVALID, with a text and before the
+ * device is touched, for a NULL handle or required pointer, n_pairs < 1, n_frames < 1, a capacity outside 1 .. 65536, n_levels outside
+ * 1 .. AMOS_MAX_LEVELS, empty bounds, a camera or (d_sim3 == NULL, enabled pairs) a host-side Sim3 that is not finite or has s12 <= 0, a th
+ * that is not finite or <= 0, d_match1 or d_match2 aliasing a row array or each other. */
+int amos_match_sim3_search_batch_device(amos_match *m, const amos_sim3_search *s);
+/* The host form for a C++ drop-in (amos-slam_amd/host/KeyFrameSim3Search.h): ONE pair, host arrays in and out, synchronous: one upload
+ * (Frame::PosInGrid on the way), AssignFeaturesToGrid for both keyframes, the two launches, one download.  points1 [kf1->n], points2
+ * [kf2->n]; cameras [2]: KF1's, KF2's; the bounds are the views' (they must agree); match12, match_out [kf1->n]; match1 [kf1->n] and
+ * match2 [kf2->n] may be NULL.  A keyframe without features is valid.  A skipped pair leaves match_out, match1 and match2 untouched. */
+int amos_match_sim3_search(amos_match *m, const struct amos_frame_view *kf1, const amos_map_point *points1, const struct amos_frame_view *kf2,
+                           const amos_map_point *points2, const amos_sim3_camera *cameras, const amos_sim3_search_pair *sim3,
+                           const float *scale_factors, int n_levels, const int32_t *match12, int32_t *match_out, int32_t *match1,
+                           int32_t *match2, amos_sim3_search_stats *stats);
+
 /* ---------------------------------------------------------------- fuse search ---------------- */
 
 /* ORBmatcher::Fuse for a batch of PAIRS of resident keyframes: pair p is (keyframe pair_frame[p], the points point_first[p] ..
