@@ -112,6 +112,8 @@ PROTOTYPES = {
     "amos_match_sim3": (_i, (_v, _v, _v, _i, _v, _v, _i, _v, _v, _v, _i, _v, _v, _v, _v, _v)),
     "amos_match_sim3_search_batch_device": (_i, (_v, _v)),
     "amos_match_sim3_search": (_i, (_v, _v, _v, _v, _v, _v, _v, _v, _i, _v, _v, _v, _v, _v)),
+    "amos_match_sim3_optimize_batch_device": (_i, (_v, _v)),
+    "amos_match_sim3_optimize": (_i, (_v, _v, _v, _i, _v, _v, _i, _v, _v, _v, _i, _v, _v, _v)),
     "amos_match_fuse_batch_device": (_i, (_v, _v)),
     "amos_match_fuse": (_i, (_v, _v, _i, _v, _i, _i, _v, _v, _v, _v, _v, _v, _i, _v, _v, _i, _i, _i, _v, _v, _v, _v, _v)),
     "amos_mask_pre_create": (_i, (_i, _v, _i, _i, _i, _v)),
@@ -1261,6 +1263,32 @@ def sim3_search_pair(R12, t12, s12, th=7.5, enabled=1):
     return p[0]
 
 
+class Sim3Optimize(C.Structure):
+    """amos_sim3_optimize (include/amos_frontend.h)."""
+    _fields_ = [("d_kps", C.c_void_p), ("d_counts", C.c_void_p), ("d_points", C.c_void_p), ("cameras", C.c_void_p), ("d_pairs_1", C.c_void_p),
+                ("d_pairs_2", C.c_void_p), ("inv_level_sigma2", C.c_void_p), ("pairs", C.c_void_p), ("d_sim3", C.c_void_p),
+                ("d_match12", C.c_void_p), ("d_match_out", C.c_void_p), ("d_result", C.c_void_p), ("n_frames", C.c_int32), ("n_pairs", C.c_int32),
+                ("capacity", C.c_int32), ("n_levels", C.c_int32)]
+
+
+SIM3_OPT_STATUS_OCTAVE = 1  # amos_sim3_opt_result.status
+SIM3_OPT_PAIR_DTYPE = np.dtype([("R12", "<f4", (9,)), ("t12", "<f4", (3,)), ("s12", "<f4"), ("th2", "<f4"), ("fix_scale", "<i4"),
+                                ("enabled", "<i4")])  # amos_sim3_opt_pair
+SIM3_OPT_RESULT_DTYPE = np.dtype([("q", "<f8", (4,)), ("t", "<f8", (3,)), ("s", "<f8"), ("lambda", "<f8", (2,)), ("chi2", "<f8", (2,)),
+                                  ("R12", "<f4", (9,)), ("t12", "<f4", (3,)), ("s12", "<f4"), ("Scw", "<f4", (16,)), ("n_correspondences", "<i4"),
+                                  ("n_bad_first", "<i4"), ("n_inliers", "<i4"), ("rounds", "<i4"), ("iterations", "<i4", (2,)),
+                                  ("trials", "<i4", (2,)), ("status", "<i4"), ("skipped", "<i4"), ("code", "<i4")])  # amos_sim3_opt_result
+assert (SIM3_OPT_PAIR_DTYPE.itemsize, SIM3_OPT_RESULT_DTYPE.itemsize) == (64, 256)
+
+
+def sim3_opt_pair(R12, t12, s12, th2=10.0, fix_scale=0, enabled=1):
+    """One SIM3_OPT_PAIR_DTYPE record (th2: 10 in LoopClosing.cc:461)."""
+    p = np.zeros(1, SIM3_OPT_PAIR_DTYPE)
+    p["R12"], p["t12"], p["s12"], p["th2"] = np.asarray(R12, np.float32).reshape(9), t12, s12, th2
+    p["fix_scale"], p["enabled"] = fix_scale, enabled
+    return p[0]
+
+
 FUSE_LOCAL, FUSE_SIM3 = 0, 1
 FUSE_CAMERA_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("Ow", "<f4", (3,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"),
                               ("cy", "<f4"), ("mbf", "<f4"), ("th", "<f4")])  # amos_fuse_camera
@@ -1789,6 +1817,35 @@ class OrbMatcher(_Handle):
         _check(self.L.amos_match_sim3_search(self.h, C.addressof(views[0]), _p(points1), C.addressof(views[1]), _p(points2), _p(cams), _p(pr), _p(sf),
                                              len(sf), _p(match12), _p(match_out), _p(match1), _p(match2), _p(stats)), "amos_match_sim3_search")
         return match_out, match1, match2, stats[0]
+
+    def sim3_optimize_batch_device(self, d_kps, d_counts, d_points, cameras, d_pairs_1, d_pairs_2, pairs, d_match12, d_match_out, d_result,
+                                   capacity, inv_level_sigma2, d_sim3=None):
+        """Optimizer::OptimizeSim3 (Optimizer.cc:1364-1590) for pairs (keyframe-1 slot, keyframe-2 slot) of resident keyframes, one launch.
+        cameras: host SIM3_CAMERA_DTYPE records, one per frame slot; pairs: host SIM3_OPT_PAIR_DTYPE records, one per pair; d_sim3: the
+        solver's d_result (its Sim3 replaces the records'), or None; d_match_out may be d_match12; d_result: SIM3_OPT_RESULT_DTYPE records.
+        Asynchronous on the matcher's stream."""
+        sig = np.ascontiguousarray(inv_level_sigma2, np.float32)
+        cams = np.ascontiguousarray(cameras, SIM3_CAMERA_DTYPE).reshape(-1)
+        prs = np.ascontiguousarray(pairs, SIM3_OPT_PAIR_DTYPE).reshape(-1)
+        s = Sim3Optimize(d_kps, d_counts, d_points, cams.ctypes.data, d_pairs_1, d_pairs_2, sig.ctypes.data, prs.ctypes.data, d_sim3, d_match12,
+                         d_match_out, d_result, len(cams), len(prs), capacity, len(sig))
+        _check(self.L.amos_match_sim3_optimize_batch_device(self.h, C.byref(s)), "amos_match_sim3_optimize_batch_device")
+
+    def sim3_optimize(self, kps1, points1, kps2, points2, cameras, match12, inv_level_sigma2, pair):
+        """The same for ONE pair from host arrays (amos_match_sim3_optimize): returns (result, match_out); a skipped pair returns match12."""
+        kps1, kps2 = np.ascontiguousarray(kps1, KP_DTYPE), np.ascontiguousarray(kps2, KP_DTYPE)
+        points1, points2 = np.ascontiguousarray(points1, SIM3_POINT_DTYPE), np.ascontiguousarray(points2, SIM3_POINT_DTYPE)
+        cams = np.ascontiguousarray(cameras, SIM3_CAMERA_DTYPE).reshape(-1)
+        match12 = np.ascontiguousarray(match12, np.int32)
+        sig = np.ascontiguousarray(inv_level_sigma2, np.float32)
+        pr = np.ascontiguousarray(pair, SIM3_OPT_PAIR_DTYPE).reshape(1)
+        n1, n2 = len(kps1), len(kps2)
+        if len(points1) != n1 or len(points2) != n2 or len(match12) != n1 or len(cams) != 2:
+            raise ValueError("points and match12 hold one entry per keypoint, cameras two records")
+        result, match_out = np.zeros(1, SIM3_OPT_RESULT_DTYPE), match12.copy()
+        _check(self.L.amos_match_sim3_optimize(self.h, _p(kps1), _p(points1), n1, _p(kps2), _p(points2), n2, _p(cams), _p(match12), _p(sig), len(sig),
+                                               _p(pr), _p(match_out), _p(result)), "amos_match_sim3_optimize")
+        return result[0], match_out
 
     def sync(self):
         _check(self.L.amos_match_sync(self.h), "amos_match_sync")

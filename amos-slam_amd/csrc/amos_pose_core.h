@@ -334,83 +334,97 @@ inline double tree_sum(double *p)
 }
 static_assert(kThreads == 256, "tree_sum combines four blocks of 64");
 
-// (H + lambda I) x = b by LDL^T with diagonal pivoting (see the head of the file).  H: upper triangle row-major; A (36), y (6), perm (6):
-// work.  Returns false, x untouched, when a pivot is negative.
-FM_HD bool solve6(const double *H, double lambda, const double *b, double *x, double *A, double *y, int *perm)
+// (H + lambda I) x = b by LDL^T with diagonal pivoting (see the head of the file), in D dimensions (6: the pose; 7: the Sim3 of
+// amos_sim3_opt_core.h).  H: upper triangle row-major; A (D D), y (D), perm (D): work.  Returns false, x untouched, when a pivot is negative.
+template <int D>
+FM_HD bool solve_ldlt(const double *H, double lambda, const double *b, double *x, double *A, double *y, int *perm)
 {
     int k = 0;
-    for (int i = 0; i < 6; i++)
-        for (int j = i; j < 6; j++, k++) A[i * 6 + j] = A[j * 6 + i] = i == j ? add(H[k], lambda) : H[k];
-    for (int i = 0; i < 6; i++) perm[i] = i;
+    for (int i = 0; i < D; i++)
+        for (int j = i; j < D; j++, k++) A[i * D + j] = A[j * D + i] = i == j ? add(H[k], lambda) : H[k];
+    for (int i = 0; i < D; i++) perm[i] = i;
     bool ok = true;
-    for (k = 0; k < 6; k++) {
+    for (k = 0; k < D; k++) {
         int best = k;
-        double bv = fm::fabs_(A[k * 6 + k]);
-        for (int i = k + 1; i < 6; i++) {
-            const double v = fm::fabs_(A[i * 6 + i]);
+        double bv = fm::fabs_(A[k * D + k]);
+        for (int i = k + 1; i < D; i++) {
+            const double v = fm::fabs_(A[i * D + i]);
             if (v > bv) { bv = v; best = i; }
         }
         if (best != k) {
-            for (int j = 0; j < 6; j++) { const double t = A[k * 6 + j]; A[k * 6 + j] = A[best * 6 + j]; A[best * 6 + j] = t; }
-            for (int j = 0; j < 6; j++) { const double t = A[j * 6 + k]; A[j * 6 + k] = A[j * 6 + best]; A[j * 6 + best] = t; }
+            for (int j = 0; j < D; j++) { const double t = A[k * D + j]; A[k * D + j] = A[best * D + j]; A[best * D + j] = t; }
+            for (int j = 0; j < D; j++) { const double t = A[j * D + k]; A[j * D + k] = A[j * D + best]; A[j * D + best] = t; }
             const int t = perm[k]; perm[k] = perm[best]; perm[best] = t;
         }
-        const double d = A[k * 6 + k];
+        const double d = A[k * D + k];
         if (d < 0.0) ok = false;
         if (fm::fabs_(d) > kTiny) {
-            for (int i = k + 1; i < 6; i++) A[i * 6 + k] = dvd(A[k * 6 + i], d);  // L; row k right of the diagonal keeps the column as it was
-            for (int j = k + 1; j < 6; j++)
-                for (int i = j; i < 6; i++) A[j * 6 + i] = A[i * 6 + j] = sub(A[i * 6 + j], mul(A[i * 6 + k], A[k * 6 + j]));
+            for (int i = k + 1; i < D; i++) A[i * D + k] = dvd(A[k * D + i], d);  // L; row k right of the diagonal keeps the column as it was
+            for (int j = k + 1; j < D; j++)
+                for (int i = j; i < D; i++) A[j * D + i] = A[i * D + j] = sub(A[i * D + j], mul(A[i * D + k], A[k * D + j]));
         } else {
-            for (int i = k + 1; i < 6; i++) A[i * 6 + k] = 0.0;
+            for (int i = k + 1; i < D; i++) A[i * D + k] = 0.0;
         }
     }
     if (!ok) return false;
-    for (int i = 0; i < 6; i++) y[i] = b[perm[i]];
-    for (int i = 1; i < 6; i++)
-        for (int j = 0; j < i; j++) y[i] = sub(y[i], mul(A[i * 6 + j], y[j]));
-    for (int i = 0; i < 6; i++) y[i] = fm::fabs_(A[i * 6 + i]) > kTiny ? dvd(y[i], A[i * 6 + i]) : 0.0;
-    for (int i = 4; i >= 0; i--)
-        for (int j = i + 1; j < 6; j++) y[i] = sub(y[i], mul(A[j * 6 + i], y[j]));
-    for (int i = 0; i < 6; i++) x[perm[i]] = y[i];
+    for (int i = 0; i < D; i++) y[i] = b[perm[i]];
+    for (int i = 1; i < D; i++)
+        for (int j = 0; j < i; j++) y[i] = sub(y[i], mul(A[i * D + j], y[j]));
+    for (int i = 0; i < D; i++) y[i] = fm::fabs_(A[i * D + i]) > kTiny ? dvd(y[i], A[i * D + i]) : 0.0;
+    for (int i = D - 2; i >= 0; i--)
+        for (int j = i + 1; j < D; j++) y[i] = sub(y[i], mul(A[j * D + i], y[j]));
+    for (int i = 0; i < D; i++) x[perm[i]] = y[i];
     return true;
+}
+FM_HD bool solve6(const double *H, double lambda, const double *b, double *x, double *A, double *y, int *perm)
+{
+    return solve_ldlt<6>(H, lambda, b, x, A, y, perm);
 }
 
 // ---- OptimizationAlgorithmLevenberg::solve as a state machine.  ONE caller (the device's lane 0, the host loop) owns the state; between
-// its steps the edges are summed: lm_iteration_begin() takes the 28 sums at `cur`, lm_trial_done() the robust chi2 at `trial`.
-struct Lm {
-    Pose cur, trial, lastEval;  // lastEval: where computeActiveErrors ran last (the error an inlier edge keeps into the classification)
-    double H[21], b[6], x[6], A[36], y[6];
+// its steps the edges are summed: lm_iteration_begin() takes the D (D + 1) / 2 + D + 1 sums at `cur`, lm_trial_done() the robust chi2 at
+// `trial`.  D and the vertex type P are parameters (P needs pose_update(const P &, const double *, P &), found by its namespace); maxIter is
+// optimize()'s argument.  Lm is the 6-dimension instance of PoseOptimization.
+template <int D, class P>
+struct LmT {
+    static constexpr int kH = D * (D + 1) / 2;
+    P cur, trial, lastEval;  // lastEval: where computeActiveErrors ran last (the error an inlier edge keeps into the classification)
+    double H[kH], b[D], x[D], A[D * D], y[D];
     double lambda, ni, currentChi, iniChi, rho;
-    int perm[6];
-    int nBad, qmax, iter, trials, solved;
+    int perm[D];
+    int nBad, qmax, iter, trials, solved, maxIter;
 };
+using Lm = LmT<6, Pose>;
 
-FM_HD void lm_round_begin(Lm &s, const Pose &init)
+template <int D, class P>
+FM_HD void lm_round_begin(LmT<D, P> &s, const P &init, int maxIter = kIterations)
 {
     s.cur = init;
     s.lastEval = init;
-    for (int i = 0; i < 6; i++) s.x[i] = 0.0;
+    for (int i = 0; i < D; i++) s.x[i] = 0.0;
     s.lambda = 0.0; s.ni = 2.0; s.currentChi = 0.0; s.iniChi = 0.0; s.rho = 0.0;
-    s.nBad = 0; s.qmax = 0; s.iter = 0; s.trials = 0; s.solved = 0;
+    s.nBad = 0; s.qmax = 0; s.iter = 0; s.trials = 0; s.solved = 0; s.maxIter = maxIter;
 }
 
-FM_HD void lm_make_trial(Lm &s)
+template <int D, class P>
+FM_HD void lm_make_trial(LmT<D, P> &s)
 {
-    s.solved = solve6(s.H, s.lambda, s.b, s.x, s.A, s.y, s.perm) ? 1 : 0;
+    s.solved = solve_ldlt<D>(s.H, s.lambda, s.b, s.x, s.A, s.y, s.perm) ? 1 : 0;
     pose_update(s.cur, s.x, s.trial);
 }
 
-FM_HD void lm_iteration_begin(Lm &s, const double *sums)
+template <int D, class P>
+FM_HD void lm_iteration_begin(LmT<D, P> &s, const double *sums)
 {
-    for (int i = 0; i < 21; i++) s.H[i] = sums[i];
-    for (int i = 0; i < 6; i++) s.b[i] = sums[21 + i];
-    s.currentChi = s.iniChi = sums[27];
+    constexpr int kH = LmT<D, P>::kH;
+    for (int i = 0; i < kH; i++) s.H[i] = sums[i];
+    for (int i = 0; i < D; i++) s.b[i] = sums[kH + i];
+    s.currentChi = s.iniChi = sums[kH + D];
     s.lastEval = s.cur;
     if (s.iter == 0) {  // computeLambdaInit: tau max |H_jj|, std::max's comparisons
         double m = 0.0;
         int k = 0;
-        for (int j = 0; j < 6; k += 6 - j, j++) {
+        for (int j = 0; j < D; k += D - j, j++) {
             const double a = fm::fabs_(s.H[k]);
             m = a < m ? m : a;
         }
@@ -424,12 +438,13 @@ FM_HD void lm_iteration_begin(Lm &s, const double *sums)
 }
 
 // -> kActTrial (s.trial is the next trial), kActIterate (linearise again at s.cur) or kActRoundEnd
-FM_HD int lm_trial_done(Lm &s, double chiSum)
+template <int D, class P>
+FM_HD int lm_trial_done(LmT<D, P> &s, double chiSum)
 {
     const double tempChi = s.solved ? chiSum : kDblMax;
     s.lastEval = s.trial;
     double scale = 0.0;
-    for (int j = 0; j < 6; j++) scale = add(scale, mul(s.x[j], add(mul(s.lambda, s.x[j]), s.b[j])));
+    for (int j = 0; j < D; j++) scale = add(scale, mul(s.x[j], add(mul(s.lambda, s.x[j]), s.b[j])));
     scale = add(scale, 1e-3);
     s.rho = dvd(sub(s.currentChi, tempChi), scale);
     if (s.rho > 0.0 && sub(tempChi, tempChi) == 0.0) {  // g2o_isfinite
@@ -455,7 +470,7 @@ FM_HD int lm_trial_done(Lm &s, double chiSum)
     if (s.qmax == kTrials || s.rho == 0.0) return kActRoundEnd;
     if (mul(sub(s.iniChi, s.currentChi), 1e3) < s.iniChi) s.nBad++;
     else s.nBad = 0;
-    if (s.nBad >= 3 || s.iter == kIterations) return kActRoundEnd;
+    if (s.nBad >= 3 || s.iter == s.maxIter) return kActRoundEnd;
     return kActIterate;
 }
 

@@ -1123,6 +1123,77 @@ int amos_match_sim3_search(amos_match *m, const struct amos_frame_view *kf1, con
                            const float *scale_factors, int n_levels, const int32_t *match12, int32_t *match_out, int32_t *match1,
                            int32_t *match2, amos_sim3_search_stats *stats);
 
+/* ---------------------------------------------------------------- loop-closing Sim3 optimisation */
+
+/* Step 4 of LoopClosing::ComputeSim3's candidate loop (LoopClosing.cc:461): Optimizer::OptimizeSim3 (Optimizer.cc:1364-1590) for a batch of
+ * PAIRS of resident keyframes -- the arrays of amos_sim3 -- reading SearchBySim3's rows and the solver's result records in place.  ONE
+ * launch, k_sim3_optimize, one work-group of 256 threads per pair; the host reads one amos_sim3_opt_result per pair.  The arithmetic is
+ * amos-slam_amd/csrc/amos_sim3_opt_core.h (its header lists the deviations): g2o's 7-dof vertex, the two projection edges per
+ * correspondence with g2o's numeric central-difference Jacobian (delta 1e-9), a Huber kernel of width (float) sqrt(th2) on every edge in
+ * both optimisations, Levenberg-Marquardt as amos_pose_core.h restates it.  PARITY WITH A COMPILED g2o UNPINNED (g2o needs Eigen, which this
+ * project does not carry); what is pinned, bit for bit, is tests/sim3_optimization_restatement.py.
+ *
+ * Correspondences: keyframe-1 features i < N1 in ascending order whose row entry j lies in [0, N2), where d_points[slot 1][i] and
+ * d_points[slot 2][j] do not carry AMOS_SIM3_POINT_SKIP.  -1, AMOS_SIM3_SEARCH_MATCHED_ELSEWHERE and any other value are no correspondence.
+ * An octave outside [0, n_levels) (either keypoint) skips the feature and sets bit 0 of status.  There is no cap below capacity.
+ * The Sim3 of a pair: pairs[p] (host), or with d_sim3 != NULL row p of the solver's amos_sim3_result array, read on the device; pairs[p]
+ * still supplies th2, fix_scale and enabled.  A pair with enabled == 0, or whose d_sim3 row has has_sim3 == 0 or code != 0, is SKIPPED: only
+ * its result record is written (zeros, skipped = 1), its rows are neither read nor written.  A slot outside [0, n_frames): code = -4 in
+ * the record (zeros otherwise), nothing else is written for that pair.
+ *
+ * optimize(5); a correspondence with e12.chi2 > th2 || e21.chi2 > th2 (double; NaN is an inlier; the errors of the last evaluated estimate)
+ * is cleared: d_match_out[i] = -1, and it leaves the problem.  n_correspondences - n_bad_first < 10: n_inliers = 0, rounds = 1, the row
+ * keeps the cleared entries and the record carries THE INPUT Sim3 (R12, t12, s12 as given; q, t, s and Scw made from them).  Otherwise
+ * optimize(n_bad_first > 0 ? 10 : 5) from the estimate reached, with a fresh lambda; it clears more entries and n_inliers counts the rest.
+ * The row: d_match12 in, d_match_out out, [pairs][capacity]; d_match_out == d_match12 is allowed (the chained use behind
+ * amos_match_sim3_search_batch_device); otherwise all capacity entries are copied first. */
+typedef struct amos_sim3_opt_pair {     /* per pair: 64 bytes */
+    float R12[9], t12[3], s12;          /* read when d_sim3 == NULL: g2o::Sim3(R, t, s) */
+    float th2;                          /* 10 in LoopClosing.cc:461 */
+    int32_t fix_scale;                  /* mbFixScale: 0 or 1 */
+    int32_t enabled;                    /* 0: the pair is skipped */
+} amos_sim3_opt_pair;
+typedef struct amos_sim3_opt_result {   /* per pair: 256 bytes */
+    double q[4], t[3], s;               /* the vertex's estimate: rotation x, y, z, w (not normalised, as g2o keeps it), translation, scale */
+    double lambda[2], chi2[2];          /* per optimisation: the last lambda, the robust chi2 */
+    float R12[9], t12[3], s12;          /* toRotationMatrix(q), t, s rounded once to float (the input floats when n_inliers = 0 came early) */
+    float Scw[16];                      /* gScm * Sim3(R2w, t2w, 1.0) as Converter::toCvMat stores it: [s R | t] over 0 0 0 1, row-major */
+    int32_t n_correspondences, n_bad_first;
+    int32_t n_inliers;                  /* the reference's return value */
+    int32_t rounds;                     /* optimisations run: 0 (no correspondence), 1 or 2 */
+    int32_t iterations[2], trials[2];   /* per optimisation */
+    int32_t status;                     /* bit 0: an octave outside the table */
+    int32_t skipped;                    /* 1: enabled == 0 or no Sim3 in d_sim3 */
+    int32_t code;                       /* 0; -4: a slot outside the frames */
+} amos_sim3_opt_result;
+typedef struct amos_sim3_optimize {
+    const amos_keypoint *d_kps;         /* [frames][capacity]: mvKeysUn (pt and octave are read) */
+    const int32_t *d_counts;            /* [frames] */
+    const amos_sim3_point *d_points;    /* [frames][capacity]: GetMapPointMatches() by feature */
+    const amos_sim3_camera *cameras;    /* host, n_frames entries */
+    const int32_t *d_pairs_1, *d_pairs_2; /* [n_pairs] frame slots */
+    const float *inv_level_sigma2;      /* host, n_levels entries (mvInvLevelSigma2) */
+    const amos_sim3_opt_pair *pairs;    /* host, n_pairs entries */
+    const amos_sim3_result *d_sim3;     /* [n_pairs] or NULL: amos_match_sim3_batch_device's d_result, read in place */
+    const int32_t *d_match12;           /* [pairs][capacity] */
+    int32_t *d_match_out;               /* [pairs][capacity]; may be d_match12 */
+    amos_sim3_opt_result *d_result;     /* out, [pairs] */
+    int32_t n_frames, n_pairs, capacity, n_levels;
+} amos_sim3_optimize;
+/* Asynchronous on the matcher's stream; the host arrays are consumed before the call returns.  The compacted correspondences live in a
+ * workspace the handle owns; no atomics, nothing to zero between calls.  AMOS_ERR_INVALID, with a text and before the device is touched, for a
+ * NULL handle or required pointer, n_pairs < 1, n_frames < 1, a capacity outside 1 .. 65536, n_levels outside 1 .. AMOS_MAX_LEVELS, a camera
+ * that is not finite, a fix_scale or enabled other than 0 or 1, and for an enabled pair a th2 that is not finite or <= 0 or (d_sim3 == NULL)
+ * a Sim3 that is not finite or has s12 <= 0. */
+int amos_match_sim3_optimize_batch_device(amos_match *m, const amos_sim3_optimize *s);
+/* The host form for a C++ drop-in (amos-slam_amd/host/KeyFrameSim3Optimize.h): ONE pair, host arrays in and out, synchronous: one upload,
+ * the launch, one download.  Keyframe 1: kps1 / points1 [n1]; keyframe 2: kps2 / points2 [n2]; cameras [2]; match12 in and match_out out
+ * [n1] (they may be the same array).  A skipped pair leaves match_out untouched. */
+int amos_match_sim3_optimize(amos_match *m, const amos_keypoint *kps1, const amos_sim3_point *points1, int n1, const amos_keypoint *kps2,
+                             const amos_sim3_point *points2, int n2, const amos_sim3_camera *cameras, const int32_t *match12,
+                             const float *inv_level_sigma2, int n_levels, const amos_sim3_opt_pair *pair, int32_t *match_out,
+                             amos_sim3_opt_result *result);
+
 /* ---------------------------------------------------------------- fuse search ---------------- */
 
 /* ORBmatcher::Fuse for a batch of PAIRS of resident keyframes: pair p is (keyframe pair_frame[p], the points point_first[p] ..
