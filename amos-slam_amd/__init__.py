@@ -114,6 +114,8 @@ PROTOTYPES = {
     "amos_match_sim3_search": (_i, (_v, _v, _v, _v, _v, _v, _v, _v, _i, _v, _v, _v, _v, _v)),
     "amos_match_sim3_optimize_batch_device": (_i, (_v, _v)),
     "amos_match_sim3_optimize": (_i, (_v, _v, _v, _i, _v, _v, _i, _v, _v, _v, _i, _v, _v, _v)),
+    "amos_match_loop_points_batch_device": (_i, (_v, _v)),
+    "amos_match_loop_points": (_i, (_v, _v, _v, _i, _v, _v, _v, _v, _i, _v, _i, _v, _v)),
     "amos_match_fuse_batch_device": (_i, (_v, _v)),
     "amos_match_fuse": (_i, (_v, _v, _i, _v, _i, _i, _v, _v, _v, _v, _v, _v, _i, _v, _v, _i, _i, _i, _v, _v, _v, _v, _v)),
     "amos_mask_pre_create": (_i, (_i, _v, _i, _i, _i, _v)),
@@ -1289,6 +1291,33 @@ def sim3_opt_pair(R12, t12, s12, th2=10.0, fix_scale=0, enabled=1):
     return p[0]
 
 
+class LoopPointsSearch(C.Structure):
+    """amos_loop_points_search (include/amos_frontend.h)."""
+    _fields_ = [("d_kps", C.c_void_p), ("d_desc", C.c_void_p), ("d_counts", C.c_void_p), ("d_cell_start", C.c_void_p), ("d_items", C.c_void_p),
+                ("scale_factors", C.c_void_p), ("d_points", C.c_void_p), ("point_first", C.c_void_p), ("point_count", C.c_void_p),
+                ("queries", C.c_void_p), ("d_opt", C.c_void_p), ("d_matched", C.c_void_p), ("d_found", C.c_void_p),
+                ("d_point_of_feature2", C.c_void_p), ("d_loop_match", C.c_void_p), ("d_stats", C.c_void_p), ("n_frames", C.c_int32),
+                ("n_queries", C.c_int32), ("n_points", C.c_int32), ("capacity", C.c_int32), ("n_levels", C.c_int32), ("min_x", C.c_float),
+                ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float)]
+
+
+LOOP_POINTS_QUERY_DTYPE = np.dtype([("Scw", "<f4", (16,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"), ("th", "<f4"), ("frame", "<i4"),
+                                    ("max_dist", "<i4"), ("min_inliers", "<i4"), ("min_total", "<i4"), ("enabled", "<i4"),
+                                    ("found_from_match", "<i4")])  # amos_loop_points_query
+LOOP_POINTS_STATS_DTYPE = np.dtype([("n_candidates", "<i4"), ("n_in_view", "<i4"), ("n_matches", "<i4"), ("n_researched", "<i4"),
+                                    ("n_total", "<i4"), ("accepted", "<i4"), ("status", "<i4"), ("skipped", "<i4")])  # amos_loop_points_stats
+assert (LOOP_POINTS_QUERY_DTYPE.itemsize, LOOP_POINTS_STATS_DTYPE.itemsize) == (108, 32)
+
+
+def loop_points_query(frame, Scw, fx, fy, cx, cy, th=10.0, max_dist=50, min_inliers=20, min_total=40, enabled=1, found_from_match=0):
+    """One LOOP_POINTS_QUERY_DTYPE record with the parameters of LoopClosing.cc:464, :534 and :546."""
+    q = np.zeros(1, LOOP_POINTS_QUERY_DTYPE)
+    q["Scw"] = np.asarray(Scw, np.float32).reshape(16)
+    q["fx"], q["fy"], q["cx"], q["cy"], q["th"], q["frame"] = fx, fy, cx, cy, th, frame
+    q["max_dist"], q["min_inliers"], q["min_total"], q["enabled"], q["found_from_match"] = max_dist, min_inliers, min_total, enabled, found_from_match
+    return q[0]
+
+
 FUSE_LOCAL, FUSE_SIM3 = 0, 1
 FUSE_CAMERA_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("Ow", "<f4", (3,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"),
                               ("cy", "<f4"), ("mbf", "<f4"), ("th", "<f4")])  # amos_fuse_camera
@@ -1846,6 +1875,42 @@ class OrbMatcher(_Handle):
         _check(self.L.amos_match_sim3_optimize(self.h, _p(kps1), _p(points1), n1, _p(kps2), _p(points2), n2, _p(cams), _p(match12), _p(sig), len(sig),
                                                _p(pr), _p(match_out), _p(result)), "amos_match_sim3_optimize")
         return result[0], match_out
+
+    def loop_points_batch_device(self, d_kps, d_desc, d_counts, d_cell_start, d_items, n_frames, d_points, n_points, point_first, point_count, queries,
+                                 d_matched, d_loop_match, d_stats, capacity, scale_factors, bounds=(0.0, 640.0, 0.0, 480.0), d_opt=None, d_found=None,
+                                 d_point_of_feature2=None):
+        """ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) (ORBmatcher.cc:388-512) and nTotalMatches >= min_total
+        (LoopClosing.cc:538-546) for queries (keyframe slot, point range, Scw, row) on resident keyframes.  point_first, point_count: host ints,
+        one per query; queries: host LOOP_POINTS_QUERY_DTYPE records; d_opt: amos_match_sim3_optimize_batch_device's d_result (its Scw replaces
+        the records', and its rows decide which queries run), or None.  Asynchronous on the matcher's stream."""
+        sf = np.ascontiguousarray(scale_factors, np.float32)
+        p0, pc = (np.ascontiguousarray(a, np.int32) for a in (point_first, point_count))
+        qs = np.ascontiguousarray(queries, LOOP_POINTS_QUERY_DTYPE).reshape(-1)
+        if not (len(p0) == len(pc) == len(qs)):
+            raise ValueError("one entry per query in point_first, point_count and queries")
+        s = LoopPointsSearch(d_kps, d_desc, d_counts, d_cell_start, d_items, sf.ctypes.data, d_points, _p(p0), _p(pc), qs.ctypes.data, d_opt, d_matched,
+                             d_found, d_point_of_feature2, d_loop_match, d_stats, n_frames, len(qs), n_points, capacity, len(sf), *bounds)
+        _check(self.L.amos_match_loop_points_batch_device(self.h, C.byref(s)), "amos_match_loop_points_batch_device")
+
+    def loop_points(self, kf, points, query, scale_factors, matched=None, found=None, point_of_feature2=None, bounds=(0.0, 640.0, 0.0, 480.0)):
+        """The same for ONE query from host arrays (amos_match_loop_points): kf is a dict with keys_un and desc.  Returns (loop_match, stats);
+        a skipped query returns a row of -1."""
+        kp, d = np.ascontiguousarray(kf["keys_un"], KP_DTYPE), np.ascontiguousarray(kf["desc"], np.uint8).reshape(-1, 32)
+        view = FrameView()
+        view.n, view.keys_un, view.descriptors, view.u_right = len(kp), kp.ctypes.data, d.ctypes.data, None
+        view.min_x, view.max_x, view.min_y, view.max_y = bounds
+        points = np.ascontiguousarray(points, MAP_POINT_DTYPE)
+        q = np.ascontiguousarray(query, LOOP_POINTS_QUERY_DTYPE).reshape(1)
+        sf = np.ascontiguousarray(scale_factors, np.float32)
+        row = None if matched is None else np.ascontiguousarray(matched, np.int32)
+        fd = None if found is None else np.ascontiguousarray(found, np.uint8)
+        pf2 = None if point_of_feature2 is None else np.ascontiguousarray(point_of_feature2, np.int32)
+        if (row is not None and len(row) != len(kp)) or (fd is not None and len(fd) != len(points)):
+            raise ValueError("one row entry per feature and one found byte per point")
+        loop_match, stats = np.full(len(kp), -1, np.int32), np.zeros(1, LOOP_POINTS_STATS_DTYPE)
+        _check(self.L.amos_match_loop_points(self.h, C.addressof(view), _p(points), len(points), _p(q), _p(row), _p(fd), _p(pf2),
+                                             0 if pf2 is None else len(pf2), _p(sf), len(sf), _p(loop_match), _p(stats)), "amos_match_loop_points")
+        return loop_match, stats[0]
 
     def sync(self):
         _check(self.L.amos_match_sync(self.h), "amos_match_sync")

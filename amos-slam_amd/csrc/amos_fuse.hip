@@ -57,27 +57,15 @@ __global__ __launch_bounds__(256) void k_fuse(const FuseArgs a)
         mp = a.points + pr.first + i;
         const bool skipped = (mp->flags & AMOS_MAP_POINT_SKIP) || (a.skip && a.skip[o]);
         if (!skipped) {
-            float PcX, PcY, PcZ;
-            camera_point(c.Rcw, c.tcw, mp->pos, PcX, PcY, PcZ);
-            if (!(PcZ < 0.0f)) {
-                const float invz = __fdiv_rn(1.0f, PcZ);
-                const float u = __fadd_rn(__fmul_rn(c.fx, __fmul_rn(PcX, invz)), c.cx);
-                const float v = __fadd_rn(__fmul_rn(c.fy, __fmul_rn(PcY, invz)), c.cy);
-                if (u >= a.minX && u < a.maxX && v >= a.minY && v < a.maxY) {  // KeyFrame::IsInImage: a NaN or an infinity fails it
-                    float PO[3];
-                    const float dist = point_offset(mp->pos, c.Ow, PO);
-                    if (in_distance_band(dist, mp->min_distance, mp->max_distance)) {
-                        if (!(normal_dot(PO, mp->normal) < __dmul_rn(0.5, (double)dist))) {
-                            level = predict_scale_level(a, mp->max_distance, dist);
-                            q.u = u; q.v = v;
-                            q.ur = a.chi2 ? __fsub_rn(u, __fmul_rn(c.mbf, invz)) : 0.f;
-                            q.lo = level - 1; q.hi = level;
-                            q.r = __fmul_rn(c.th, a.scale[level]);
-                            q.d = load_desc_words(mp->desc);
-                            inView = true;
-                        }
-                    }
-                }
+            KeyframeProjection pj;
+            if (keyframe_prefilter(a, c.Rcw, c.tcw, c.Ow, c.fx, c.fy, c.cx, c.cy, *mp, pj) == 0) {
+                level = pj.level;
+                q.u = pj.u; q.v = pj.v;
+                q.ur = a.chi2 ? __fsub_rn(pj.u, __fmul_rn(c.mbf, pj.invz)) : 0.f;
+                q.lo = level - 1; q.hi = level;
+                q.r = __fmul_rn(c.th, a.scale[level]);
+                q.d = load_desc_words(mp->desc);
+                inView = true;
             }
         }
     }

@@ -1,10 +1,11 @@
-// amos_projection_search.h -- what the projection-window searches share: k_window_best2 of amos_match.hip and the four map-point searches
-// (local map: amos_local.hip, motion model: amos_motion.hip, relocalisation: amos_reloc.hip, Fuse: amos_fuse.hip).  On the device:
-//   - Frame::GetFeaturesInArea (Frame.cc:894-1003) plus the best / second-best Hamming loop over a frame's cell CSR (all five);
-//   - the steps of a point's projection that the four spell alike: camera_point, point_offset, normal_dot, in_distance_band, pixel_in_bounds,
-//     copy_desc, predict_scale_level;
-//   - the parts of the greedy acceptance of local, motion and relocalisation: TakenBitmap, wave_research, rotation_bin, three_maxima
-//     (Fuse has no greedy stage).  The sequential loop around them is written out in each accept kernel: three shared forms of it were
+// amos_projection_search.h -- what the projection-window searches share: k_window_best2 of amos_match.hip and the five map-point searches
+// (local map: amos_local.hip, motion model: amos_motion.hip, relocalisation: amos_reloc.hip, Fuse: amos_fuse.hip, loop points:
+// amos_loop_points.hip).  On the device:
+//   - Frame::GetFeaturesInArea (Frame.cc:894-1003) plus the best / second-best Hamming loop over a frame's cell CSR (all six);
+//   - the steps of a point's projection that they spell alike: camera_point, point_offset, normal_dot, in_distance_band, pixel_in_bounds,
+//     copy_desc, predict_scale_level; keyframe_prefilter, the whole pre-filter of the two keyframe-side searches (Fuse, loop points);
+//   - the parts of the greedy acceptance of local, motion, relocalisation and loop points: TakenBitmap, wave_research, rotation_bin,
+//     three_maxima (Fuse has no greedy stage).  The sequential loop around them is written out in each accept kernel: three shared forms of it were
 //     measured and each cost the relocalisation kernel 2 to 17 % (profiles/r14_point_searches.txt).
 // On the host: the argument filling, validation, scratch layout and staging of their entries.
 // A search itself keeps how it finds its query and which gates stand between the projection's steps, its extra filter and its accept loop.
@@ -66,9 +67,9 @@ __device__ __forceinline__ int predict_scale_level(const ProjArgs &a, float maxD
     return min(level, a.nLevels - 1);
 }
 
-// ---- the steps of a point's projection that the point searches (amos_local.hip, amos_motion.hip, amos_reloc.hip, amos_fuse.hip) spell
-// alike.  The gates between them, 1 / z, the order of the pixel's products and Fuse's half-open IsInImage differ on purpose and stay in
-// the kernels (DESIGN.md section 1 lists them).
+// ---- the steps of a point's projection that the point searches (amos_local.hip, amos_motion.hip, amos_reloc.hip, amos_fuse.hip,
+// amos_loop_points.hip) spell alike.  The gates between them, 1 / z and the order of the pixel's products differ on purpose between the
+// frame searches, which keep them in their kernels, and the keyframe-side ones (keyframe_prefilter below); DESIGN.md section 1 lists them.
 
 // Pc = R P + t: one gemm row each, double accumulation, one rounding
 __device__ __forceinline__ void camera_point(const float *R, const float *t, const float *P, float &x, float &y, float &z)
@@ -104,6 +105,32 @@ __device__ __forceinline__ void copy_desc(uint8_t *dst, const uint8_t *src)
 {
 #pragma unroll
     for (int k = 0; k < 8; k++) reinterpret_cast<uint32_t *>(dst)[k] = reinterpret_cast<const uint32_t *>(src)[k];
+}
+
+// The pre-filter of the keyframe-side searches (amos_fuse.hip: Fuse, ORBmatcher.cc:1042-1083 / :1199-1244; amos_loop_points.hip:
+// SearchByProjection(pKF, Scw), :416-462) as include/amos_frontend.h "fuse search" defines it: p3Dc.z < 0 is out, invz = 1.0f / z,
+// u = fx * (X * invz) + cx, the half-open KeyFrame::IsInImage (a pixel that is not finite fails it), the distance band, the 60-degree test
+// in double, the predicted level.  -> 0 in view, or the gate that rejected the point; u, v and invz hold what was computed up to there.
+enum { kViewBehind = 1, kViewImage = 2, kViewBand = 3, kViewAngle = 4 };
+struct KeyframeProjection { float u, v, invz; int level; };
+__device__ __forceinline__ int keyframe_prefilter(const ProjArgs &a, const float *Rcw, const float *tcw, const float *Ow, float fx, float fy, float cx,
+                                                  float cy, const amos_map_point &mp, KeyframeProjection &o)
+{
+    o.u = o.v = o.invz = 0.f;
+    o.level = 0;
+    float PcX, PcY, PcZ;
+    camera_point(Rcw, tcw, mp.pos, PcX, PcY, PcZ);
+    if (PcZ < 0.0f) return kViewBehind;
+    o.invz = __fdiv_rn(1.0f, PcZ);
+    o.u = __fadd_rn(__fmul_rn(fx, __fmul_rn(PcX, o.invz)), cx);
+    o.v = __fadd_rn(__fmul_rn(fy, __fmul_rn(PcY, o.invz)), cy);
+    if (!(o.u >= a.minX && o.u < a.maxX && o.v >= a.minY && o.v < a.maxY)) return kViewImage;  // KeyFrame::IsInImage: a NaN or an infinity fails it
+    float PO[3];
+    const float dist = point_offset(mp.pos, Ow, PO);
+    if (!in_distance_band(dist, mp.min_distance, mp.max_distance)) return kViewBand;
+    if (normal_dot(PO, mp.normal) < __dmul_rn(0.5, (double)dist)) return kViewAngle;
+    o.level = predict_scale_level(a, mp.max_distance, dist);
+    return 0;
 }
 
 // one candidate of a window (CSR position j): its key dist << 16 | j, or none when a gate rejects it: the level window, the box, the right

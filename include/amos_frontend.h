@@ -1194,6 +1194,94 @@ int amos_match_sim3_optimize(amos_match *m, const amos_keypoint *kps1, const amo
                              const float *inv_level_sigma2, int n_levels, const amos_sim3_opt_pair *pair, int32_t *match_out,
                              amos_sim3_opt_result *result);
 
+/* ---------------------------------------------------------------- loop-closing point search ---- */
+
+/* The last step of LoopClosing::ComputeSim3 (LoopClosing.cc:534-546): ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th)
+ * (ORBmatcher.cc:388-512) and the count that accepts or rejects the loop, for a batch of QUERIES on resident keyframes.  Query q is (the
+ * current keyframe's slot queries[q].frame, the points point_first[q] .. point_first[q] + point_count[q] - 1 of d_points, an Scw, row q of
+ * d_matched).  With d_opt the Scw is read on the device from amos_match_sim3_optimize_batch_device's result records, so the chain BoW search
+ * -> Sim3Solver -> SearchBySim3 -> OptimizeSim3 -> this search stays resident and the host reads one amos_loop_points_stats per candidate.
+ *
+ * Scw (:397-403; amos-slam_amd/csrc/amos_loop_points_core.h, compiled for host and device):
+ *   scw = (float) sqrt(((double) S00^2 + (double) S01^2) + (double) S02^2)            the first row of sRcw
+ *   inv = (float) (1.0 / (double) scw);  Rcw = sRcw * inv,  tcw = st * inv            one float32 product per element
+ *   Ow  = (float) -(((double) R0c t0 + (double) R1c t1) + (double) R2c t2)            -Rcw^T tcw
+ * spAlreadyFound (:407-408, :420), either or both of: d_found[point_first[q] + i] != 0; with queries[q].found_from_match, the points that the
+ * entry row names through d_point_of_feature2: for every feature i < N of the keyframe whose row entry j lies in [0, capacity) and whose map
+ * entry p = d_point_of_feature2[q][j] lies in [0, point_count[q]), point p of the query is found.
+ * Pre-filter (:416-462): a point with AMOS_MAP_POINT_SKIP (isBad()) or found is no candidate; the others pass the AMOS_FUSE_SIM3 pre-filter of
+ * "fuse search" below, unchanged: p3Dc.z < 0.0f is out, invz = 1.0f / z, u = fx * (X * invz) + cx, the half-open KeyFrame::IsInImage, the
+ * 0.8f / 1.2f distance band, the viewing angle in double, the level in its table form.  A u or v that is not finite is out of view and sets
+ * bit 0 of the query's status.
+ * Search (:464-507): radius th * scale_factors[level]; KeyFrame::GetFeaturesInArea without a level check, |kp.x - u| < r && |kp.y - v| < r;
+ * levels level - 1 .. level; FEATURES THAT ARE OCCUPIED AT THAT MOMENT ARE PASSED OVER (:482); the nearest descriptor by strict < in the
+ * order x-major cells, then y, then insertion; accepted when bestDist <= max_dist, and the accept occupies the feature.  The points are
+ * decided in list order; there is no ratio test and no rotation histogram.  On entry feature i is occupied when d_matched[q][i] != -1: every
+ * other value is a non-NULL pointer, AMOS_SIM3_SEARCH_MATCHED_ELSEWHERE included, so the row amos_match_sim3_optimize_batch_device leaves in
+ * d_match_out is read in place.  d_matched is never written.
+ * Launches: k_loop_found (only when a query has found_from_match), k_loop_project (one thread per point), k_loop_window_best2 (eight lanes per
+ * point in view: the best two of the features free ON ENTRY), k_loop_accept (one wave per query: the sequential loop over those records
+ * against a bitmap of the occupied features; a point whose two recorded features both lay within max_dist and are both taken by then has
+ * its window searched again by the whole wave, and n_researched counts these; a second beyond max_dist settles the point without a search,
+ * since it is the nearest of everything but the best).
+ * A query is SKIPPED when enabled == 0, or with d_opt when row q has skipped != 0, code != 0 or n_inliers < min_inliers (the test of
+ * LoopClosing.cc:464): only its stats record is written (zeros, skipped = 1); its rows are neither read nor written. */
+typedef struct amos_loop_points_query {  /* per query: 108 bytes */
+    float Scw[16];                      /* read when d_opt == NULL: row-major, as Converter::toCvMat stores it */
+    float fx, fy, cx, cy;               /* pKF->fx .. cy */
+    float th;                           /* 10 in LoopClosing.cc:534 */
+    int32_t frame;                      /* the current keyframe's slot, in [0, n_frames) */
+    int32_t max_dist;                   /* TH_LOW = 50 */
+    int32_t min_inliers;                /* 20 (LoopClosing.cc:464); read with d_opt */
+    int32_t min_total;                  /* 40 (LoopClosing.cc:546) */
+    int32_t enabled;                    /* 0: the query is skipped */
+    int32_t found_from_match;           /* 0 or 1: mark the points of the entry row's features through d_point_of_feature2 */
+} amos_loop_points_query;
+typedef struct amos_loop_points_stats { /* per query: 32 bytes */
+    int32_t n_candidates;               /* points neither bad nor found */
+    int32_t n_in_view;                  /* candidates that passed the pre-filter */
+    int32_t n_matches;                  /* the reference's return value */
+    int32_t n_researched;               /* points whose window was searched again against the bitmap */
+    int32_t n_total;                    /* features i < N occupied on entry + n_matches: nTotalMatches of LoopClosing.cc:538-543 */
+    int32_t accepted;                   /* n_total >= min_total */
+    int32_t status;                     /* bit 0: a projection was not finite */
+    int32_t skipped;                    /* 1: nothing but this record was written */
+} amos_loop_points_stats;
+typedef struct amos_loop_points_search {
+    const amos_keypoint *d_kps;         /* [frames][capacity]: mvKeysUn */
+    const uint8_t *d_desc;              /* [frames][capacity][32] */
+    const int32_t *d_counts;            /* [frames] */
+    const int32_t *d_cell_start;        /* [frames][64*48+1]       (amos_frame_grid_build_batch_device) */
+    const int32_t *d_items;             /* [frames][capacity] */
+    const float *scale_factors;         /* host, n_levels entries */
+    const amos_map_point *d_points;     /* n_points: mvpLoopMapPoints; bit 0 of flags: isBad() */
+    const int32_t *point_first, *point_count; /* host, n_queries: ranges of different queries may coincide */
+    const amos_loop_points_query *queries; /* host, n_queries */
+    const amos_sim3_opt_result *d_opt;  /* [n_queries] or NULL: amos_match_sim3_optimize_batch_device's d_result, read in place */
+    const int32_t *d_matched;           /* [queries][capacity]: vpMatched on entry, -1 = free */
+    const uint8_t *d_found;             /* n_points or NULL */
+    const int32_t *d_point_of_feature2; /* [queries][capacity] or NULL (required by found_from_match): keyframe-2 feature -> index in the query's list, or -1 */
+    int32_t *d_loop_match;              /* out, [queries][capacity]: per feature the index in the query's list of the point this call matched to it, or -1 */
+    amos_loop_points_stats *d_stats;    /* out, [n_queries] */
+    int32_t n_frames, n_queries, n_points, capacity, n_levels;
+    float min_x, max_x, min_y, max_y;   /* KeyFrame::mnMinX .. mnMaxY */
+} amos_loop_points_search;
+/* Asynchronous on the matcher's stream; every host array is consumed before the call returns.  The per-point records live in a workspace the
+ * handle owns; nothing has to be zeroed between calls and a smaller call on a reused handle is valid.  All capacity entries of an executed
+ * query's d_loop_match row are written.  AMOS_ERR_INVALID, with a text and before the device is touched, for a NULL handle or required
+ * pointer, n_queries < 1, n_frames < 1, n_points < 0, a frame outside n_frames, a point range outside n_points, a capacity outside
+ * 1 .. 65536, n_levels outside 1 .. AMOS_MAX_LEVELS, empty image bounds, a th or intrinsics that are not finite (th <= 0 included), with
+ * d_opt == NULL an Scw that is not finite or whose first row has norm 0, a max_dist outside 0 .. 255, an enabled or found_from_match other
+ * than 0 or 1, and found_from_match without d_point_of_feature2. */
+int amos_match_loop_points_batch_device(amos_match *m, const amos_loop_points_search *s);
+/* The host form for a C++ drop-in (amos-slam_amd/host/KeyFrameLoopPoints.h): ONE query, host arrays in and out, synchronous: one upload,
+ * AssignFeaturesToGrid, the launches, one download.  matched [kf->n] (or NULL: every feature free); found [n_points] or NULL;
+ * point_of_feature2 [n2] or NULL; loop_match [kf->n] out.  A keyframe without features and a list without points are valid.  A skipped
+ * query leaves loop_match untouched. */
+int amos_match_loop_points(amos_match *m, const struct amos_frame_view *kf, const amos_map_point *points, int n_points,
+                           const amos_loop_points_query *query, const int32_t *matched, const uint8_t *found, const int32_t *point_of_feature2,
+                           int n2, const float *scale_factors, int n_levels, int32_t *loop_match, amos_loop_points_stats *stats);
+
 /* ---------------------------------------------------------------- fuse search ---------------- */
 
 /* ORBmatcher::Fuse for a batch of PAIRS of resident keyframes: pair p is (keyframe pair_frame[p], the points point_first[p] ..
