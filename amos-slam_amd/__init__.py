@@ -107,6 +107,9 @@ PROTOTYPES = {
     "amos_match_triangulation_batch_device": (_i, (_v, _v, _v, _v, _v, _i, _i, _i)),
     "amos_match_bow_kf": (_i, (_v, _v, _v, _f, _i, _v, _v)),
     "amos_match_triangulation": (_i, (_v, _v, _v, _i, _v, _v, _v, _i, _i, _i, _v, _v)),
+    "amos_match_new_points_batch_device": (_i, (_v, _v)),
+    "amos_kf_geometry_from_poses": (_i, (_v, _v, _v)),
+    "amos_match_new_points": (_i, (_v, _v, _v, _i, _v, _v, _v, _v, _v, _v, _v, _v, _i, _i, _i, _v, _v)),
     "amos_sim3_state_bytes": (_z, (_i,)),
     "amos_match_sim3_batch_device": (_i, (_v, _v)),
     "amos_match_sim3": (_i, (_v, _v, _v, _i, _v, _v, _i, _v, _v, _v, _i, _v, _v, _v, _v, _v)),
@@ -1206,6 +1209,37 @@ assert KF_GEOMETRY_DTYPE.itemsize == 44
 KF_STATUS_BAD_INDEX, KF_STATUS_BAD_OCTAVE = 1, 2  # amos_bow_search_stats.status of the keyframe pair searches
 
 
+class NewPoints(C.Structure):
+    """amos_new_points (include/amos_frontend.h)."""
+    _fields_ = [("d_kps", C.c_void_p), ("d_kps_raw", C.c_void_p), ("d_counts", C.c_void_p), ("d_u_right", C.c_void_p), ("d_depth", C.c_void_p),
+                ("d_pairs_1", C.c_void_p), ("d_pairs_2", C.c_void_p), ("d_match12", C.c_void_p), ("d_scale_factors", C.c_void_p),
+                ("d_level_sigma2", C.c_void_p), ("cameras", C.c_void_p), ("pairs_1", C.c_void_p), ("pairs_2", C.c_void_p), ("enabled", C.c_void_p),
+                ("d_new", C.c_void_p), ("d_verdict", C.c_void_p), ("d_stats", C.c_void_p), ("n_frames", C.c_int32), ("n_pairs", C.c_int32),
+                ("capacity", C.c_int32), ("n_levels", C.c_int32)]
+
+
+# AMOS_NEW_POINT_*: the verdict of a match
+(NEW_POINT_TRIANGULATED, NEW_POINT_UNPROJECTED_1, NEW_POINT_UNPROJECTED_2, NEW_POINT_LOW_PARALLAX, NEW_POINT_W_ZERO, NEW_POINT_BEHIND_1,
+ NEW_POINT_BEHIND_2, NEW_POINT_REPROJECTION_1, NEW_POINT_REPROJECTION_2, NEW_POINT_DISTANCE_ZERO, NEW_POINT_SCALE, NEW_POINT_CLAIMED,
+ NEW_POINT_OCTAVE) = range(13)
+NEW_POINT_VERDICTS = 13
+NEW_POINTS_BAD_MATCH, NEW_POINTS_BAD_OCTAVE, NEW_POINTS_BAD_SLOT = 1, 2, 4  # amos_new_points_stats.status
+KF_CAMERA_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("Ow", "<f4", (3,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"),
+                            ("cy", "<f4"), ("invfx", "<f4"), ("invfy", "<f4"), ("mb", "<f4"), ("mbf", "<f4"), ("scale_factor", "<f4")])  # amos_kf_camera
+NEW_POINT_DTYPE = np.dtype([("idx1", "<i4"), ("idx2", "<i4"), ("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("verdict", "<i4")])  # amos_new_point
+NEW_POINTS_STATS_DTYPE = np.dtype([("n_matches", "<i4"), ("n_new", "<i4"), ("n_verdict", "<i4", (NEW_POINT_VERDICTS,)), ("status", "<i4")])
+assert (KF_CAMERA_DTYPE.itemsize, NEW_POINT_DTYPE.itemsize, NEW_POINTS_STATS_DTYPE.itemsize) == (96, 24, 64)
+
+
+def kf_geometry_from_poses(cam1, cam2):
+    """LocalMapping::ComputeF12, the epipole and the stereo / RGB-D baseline gate from two KF_CAMERA_DTYPE records
+    (amos_kf_geometry_from_poses) -> (KF_GEOMETRY_DTYPE record, False when the neighbour is skipped).  Host only."""
+    c1, c2 = np.ascontiguousarray(cam1, KF_CAMERA_DTYPE).reshape(1), np.ascontiguousarray(cam2, KF_CAMERA_DTYPE).reshape(1)
+    g = np.zeros(1, KF_GEOMETRY_DTYPE)
+    rc = _check(lib().amos_kf_geometry_from_poses(_p(c1), _p(c2), _p(g)), "amos_kf_geometry_from_poses")
+    return g[0], rc == 1
+
+
 class Sim3(C.Structure):
     """amos_sim3 (include/amos_frontend.h)."""
     _fields_ = [("d_kps", C.c_void_p), ("d_counts", C.c_void_p), ("d_points", C.c_void_p), ("cameras", C.c_void_p), ("d_pairs_1", C.c_void_p),
@@ -1769,6 +1803,57 @@ class OrbMatcher(_Handle):
         _check(self.L.amos_match_triangulation(self.h, C.byref(v1), ptrs, len(views), _p(geo), _p(sf), _p(sg), len(sf), int(bool(only_stereo)),
                                                int(bool(check_orientation)), _p(match12), _p(stats)), "amos_match_triangulation")
         return match12, stats
+
+    def new_points_batch_device(self, d_kps, d_counts, d_pairs_1, d_pairs_2, pairs, capacity, d_match12, d_scale_factors, d_level_sigma2, n_levels,
+                                cameras, d_new, d_stats, d_verdict=None, d_u_right=None, d_depth=None, d_kps_raw=None, enabled=None):
+        """LocalMapping::CreateNewMapPoints between its search and its `new MapPoint` (LocalMapping.cc:424-597) for the pairs of one
+        triangulation_batch_device call, reading d_match12 in place (amos_match_new_points_batch_device).  pairs: the host (slot 1, slot 2)
+        pairs that d_pairs_1 / d_pairs_2 hold; cameras: host KF_CAMERA_DTYPE records, one per frame slot; enabled: host flags, one per pair
+        (a neighbour that failed the baseline gate: 0), or None.  Asynchronous on the matcher's stream."""
+        cams = np.ascontiguousarray(cameras, KF_CAMERA_DTYPE).reshape(-1)
+        prs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        p1, p2 = np.ascontiguousarray(prs[:, 0]), np.ascontiguousarray(prs[:, 1])
+        en = None if enabled is None else np.ascontiguousarray(enabled, np.uint8)
+        if en is not None and len(en) != len(prs):
+            raise ValueError("enabled holds one flag per pair")
+        s = NewPoints(d_kps, d_kps_raw, d_counts, d_u_right, d_depth, d_pairs_1, d_pairs_2, d_match12, d_scale_factors, d_level_sigma2,
+                      cams.ctypes.data, p1.ctypes.data, p2.ctypes.data, None if en is None else en.ctypes.data, d_new, d_verdict, d_stats, len(cams),
+                      len(prs), capacity, n_levels)
+        _check(self.L.amos_match_new_points_batch_device(self.h, C.byref(s)), "amos_match_new_points_batch_device")
+
+    def new_points(self, k1, k2s, cam1, cams2, scale_factors, level_sigma2, only_stereo=False, check_orientation=False):
+        """The whole of CreateNewMapPoints up to `new MapPoint` for ONE keyframe 1 against the keyframes k2s from host arrays
+        (amos_match_new_points): dicts as for triangulation plus depth (float32 per feature; needed with u_right) and optionally keys_raw
+        (mvKeys; default: keys).  cam1 / cams2: KF_CAMERA_DTYPE records.  Returns (one NEW_POINT_DTYPE array per keyframe 2 in creation order,
+        stats [len(k2s)]); a neighbour that fails the baseline gate has zero stats."""
+        def view(k):
+            return self._bow_view(k["keys"], k["desc"], k["node_ids"], k["node_off"], k["node_idx"], k.get("has_point"), k.get("u_right"))
+
+        def extra(k, n):
+            raw = None if k.get("keys_raw") is None else np.ascontiguousarray(k["keys_raw"], KP_DTYPE)
+            depth = None if k.get("depth") is None else np.ascontiguousarray(k["depth"], np.float32)
+            if (raw is not None and len(raw) != n) or (depth is not None and len(depth) != n):
+                raise ValueError("keys_raw and depth hold one entry per keypoint")
+            return raw, depth
+        v1, keep1 = view(k1)
+        views = [view(k) for k in k2s]
+        raw1, depth1 = extra(k1, v1.n)
+        extras = [extra(k, v.n) for k, (v, _) in zip(k2s, views)]
+        c1 = np.ascontiguousarray(cam1, KF_CAMERA_DTYPE).reshape(1)
+        c2 = np.ascontiguousarray(cams2, KF_CAMERA_DTYPE).reshape(-1)
+        sf, sg = np.ascontiguousarray(scale_factors, np.float32), np.ascontiguousarray(level_sigma2, np.float32)
+        if len(c2) != len(views) or len(sf) != len(sg):
+            raise ValueError("cams2 holds one record per keyframe 2, scale_factors and level_sigma2 one entry per level")
+        n2 = len(views)
+        ptrs = (C.c_void_p * max(n2, 1))(*[C.addressof(v) for v, _ in views])
+        raws = (C.c_void_p * max(n2, 1))(*[None if r is None else r.ctypes.data for r, _ in extras])
+        depths = (C.c_void_p * max(n2, 1))(*[None if d is None else d.ctypes.data for _, d in extras])
+        rows, stats = np.zeros((n2, max(v1.n, 1)), NEW_POINT_DTYPE), np.zeros(n2, NEW_POINTS_STATS_DTYPE)
+        _check(self.L.amos_match_new_points(self.h, C.byref(v1), ptrs, n2, _p(c1), _p(c2), _p(raw1), raws, _p(depth1), depths, _p(sf), _p(sg), len(sf),
+                                            int(bool(only_stereo)), int(bool(check_orientation)), _p(rows), _p(stats)), "amos_match_new_points")
+        if v1.n == 0:
+            return [np.zeros(0, NEW_POINT_DTYPE) for _ in range(n2)], stats
+        return [rows[k, :stats["n_new"][k]].copy() for k in range(n2)], stats
 
     def fuse_batch_device(self, d_kps, d_desc, d_counts, d_cell_start, d_items, d_points, n_points, n_frames, pair_frame, point_first, point_count,
                           out_off, cameras, capacity, scale_factors, inv_level_sigma2, d_query, d_in_view, d_best_idx, d_best_dist, d_stats,

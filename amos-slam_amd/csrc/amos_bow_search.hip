@@ -354,13 +354,14 @@ static size_t staged_view_bytes(int nv, size_t cap) { return (size_t)nv * (cap *
 static size_t pair_match_bytes(size_t cap, int nPairs) { return align64(sizeof(int32_t) * cap * nPairs); }
 static size_t pair_out_bytes(size_t cap, int nPairs) { return pair_match_bytes(cap, nPairs) + align64(sizeof(amos_bow_search_stats) * nPairs); }
 
-// The staging arena for the views, `ownBytes` of the form's own inputs and the download; dOut for match [nPairs][cap] and stats [nPairs].
-static int host_pairs_begin(amos_match *m, int nv, size_t cap, int nPairs, size_t ownBytes)
+// The staging arena for the views, `ownBytes` of the form's own inputs and the download; dOut for match [nPairs][cap] and stats [nPairs],
+// and `extraOut` bytes of the form's own results behind them.
+static int host_pairs_begin(amos_match *m, int nv, size_t cap, int nPairs, size_t ownBytes, size_t extraOut = 0)
 {
     AMOS_HIP_CHECK(hipSetDevice(m->device));
-    int rc = stage_begin(m, staged_view_bytes(nv, cap) + ownBytes + pair_out_bytes(cap, nPairs));
+    int rc = stage_begin(m, staged_view_bytes(nv, cap) + ownBytes + pair_out_bytes(cap, nPairs) + extraOut);
     if (rc != AMOS_OK) return rc;
-    return grow_out(m, pair_out_bytes(cap, nPairs));
+    return grow_out(m, pair_out_bytes(cap, nPairs) + extraOut);
 }
 
 // The views staged for ONE upload: a view's arrays at the front of its slot, zeros behind; has_point and u_right are staged when any
@@ -522,6 +523,100 @@ int amos_match_triangulation(amos_match *m, const amos_bow_view *k1, const amos_
     if ((rc = stage_flush(m)) != AMOS_OK ||
         (rc = amos_match_triangulation_batch_device(m, &s, dGeo, dScale, dSigma, n_levels, only_stereo, check_orientation)) != AMOS_OK) return rc;
     return download_pairs(m, cap, n2, k1->n, match12, stats);
+}
+
+// CreateNewMapPoints up to its `new MapPoint` for one keyframe 1 and n2 neighbours: geometry and baseline gate per neighbour on the host,
+// the kept neighbours staged like amos_match_triangulation's, the search's two launches and amos_match_new_points_batch_device's two on
+// the stream, one download of the new-point records and their stats.
+int amos_match_new_points(amos_match *m, const amos_bow_view *k1, const amos_bow_view *const *k2s, int n2, const amos_kf_camera *cam1,
+                          const amos_kf_camera *cams2, const amos_keypoint *kps_raw1, const amos_keypoint *const *kps_raw2, const float *depth1,
+                          const float *const *depth2, const float *scale_factors, const float *level_sigma2, int n_levels, int only_stereo,
+                          int check_orientation, amos_new_point *new_points, amos_new_points_stats *stats)
+{
+    bool ok = m && stats && k2s && n2 >= 1 && n2 <= AMOS_NEW_POINTS_MAX_PAIRS && cam1 && cams2 && scale_factors && level_sigma2 && n_levels >= 1 &&
+              n_levels <= AMOS_MAX_LEVELS && bow_view_ok(k1) && (k1->n == 0 || new_points) && (k1->n == 0 || !k1->u_right || depth1);
+    for (int v = 0; ok && v < n2; v++) ok = bow_view_ok(k2s[v]) && (k2s[v]->n == 0 || !k2s[v]->u_right || (depth2 && depth2[v]));
+    if (!ok) {
+        set_error("amos_match_new_points: invalid argument (a NULL pointer, n2 or n_levels out of range, a stereo view without depths, or a view "
+                  "whose node ids, offsets or feature indices are out of order or range)");
+        return AMOS_ERR_INVALID;
+    }
+    std::vector<int> kept;
+    std::vector<amos_kf_geometry> geo;
+    std::vector<amos_kf_camera> cams(1, *cam1);
+    for (int v = 0; v < n2; v++) {
+        amos_kf_geometry g;
+        if (amos_kf_geometry_from_poses(cam1, cams2 + v, &g) != 1) continue;  // the baseline gate
+        kept.push_back(v);
+        geo.push_back(g);
+        cams.push_back(cams2[v]);
+    }
+    std::memset(stats, 0, sizeof(amos_new_points_stats) * (size_t)n2);
+    const int nk = (int)kept.size(), nv = nk + 1;
+    if (nk == 0) return AMOS_OK;
+    size_t cap = (size_t)std::max(k1->n, 1);
+    for (int v : kept) cap = std::max(cap, (size_t)k2s[v]->n);
+    const size_t bytesNew = align64(sizeof(amos_new_point) * cap * nk), bytesStats = align64(sizeof(amos_new_points_stats) * (size_t)nk);
+    int rc = host_pairs_begin(m, nv, cap, nk,
+                              (size_t)nk * (sizeof(amos_kf_geometry) + 8) + 2 * 64 * (AMOS_MAX_LEVELS / 16 + 1) + 256 +
+                                  (size_t)nv * (cap * (sizeof(amos_keypoint) + 4) + 128) + bytesNew + bytesStats,
+                              bytesNew + bytesStats);
+    if (rc != AMOS_OK) return rc;
+    std::vector<const amos_bow_view *> views(nv);
+    std::vector<const amos_keypoint *> raws(nv);
+    std::vector<const float *> depths(nv);
+    views[0] = k1; raws[0] = kps_raw1; depths[0] = depth1;
+    bool anyRaw = kps_raw1 != nullptr;
+    for (int i = 0; i < nk; i++) {
+        views[i + 1] = k2s[kept[i]];
+        raws[i + 1] = kps_raw2 ? kps_raw2[kept[i]] : nullptr;
+        depths[i + 1] = depth2 ? depth2[kept[i]] : nullptr;
+        anyRaw |= raws[i + 1] != nullptr;
+    }
+    amos_kf_pair_search s;
+    stage_views(m, views.data(), nv, cap, nk, 0, true, s);
+    std::vector<int32_t> slots(2 * (size_t)nk, 0);
+    for (int i = 0; i < nk; i++) slots[nk + i] = i + 1;
+    s.d_pairs_1 = stage_input<int32_t>(m, slots.data(), sizeof(int32_t) * 2 * nk);
+    s.d_pairs_2 = s.d_pairs_1 + nk;
+    const amos_kf_geometry *dGeo = stage_input<amos_kf_geometry>(m, geo.data(), sizeof(amos_kf_geometry) * nk);
+    const float *dScale = stage_input<float>(m, scale_factors, sizeof(float) * n_levels);
+    const float *dSigma = stage_input<float>(m, level_sigma2, sizeof(float) * n_levels);
+    amos_new_points q = {};
+    if (anyRaw) {  // a view without raw keypoints of its own: its keys
+        const size_t o = stage_take(m, nv * cap * sizeof(amos_keypoint));
+        std::memset(m->hStage + o, 0, nv * cap * sizeof(amos_keypoint));
+        for (int v = 0; v < nv; v++)
+            if (views[v]->n) std::memcpy(m->hStage + o + v * cap * sizeof(amos_keypoint), raws[v] ? raws[v] : views[v]->keys, sizeof(amos_keypoint) * (size_t)views[v]->n);
+        q.d_kps_raw = (const amos_keypoint *)(m->dArena + o);
+    }
+    if (s.d_u_right) {
+        const size_t o = stage_take(m, nv * cap * sizeof(float));
+        float *h = (float *)(m->hStage + o);
+        std::fill(h, h + nv * cap, -1.0f);
+        for (int v = 0; v < nv; v++)
+            if (views[v]->n && depths[v]) std::memcpy(h + v * cap, depths[v], sizeof(float) * (size_t)views[v]->n);
+        q.d_depth = (const float *)(m->dArena + o);
+    }
+    uint8_t *out = (uint8_t *)m->dOut + pair_out_bytes(cap, nk);
+    q.d_kps = s.d_kps; q.d_counts = s.d_counts; q.d_u_right = s.d_u_right; q.d_pairs_1 = s.d_pairs_1; q.d_pairs_2 = s.d_pairs_2;
+    q.d_match12 = s.d_match12; q.d_scale_factors = dScale; q.d_level_sigma2 = dSigma; q.cameras = cams.data();
+    q.pairs_1 = slots.data(); q.pairs_2 = slots.data() + nk; q.enabled = nullptr;
+    q.d_new = (amos_new_point *)out; q.d_verdict = nullptr; q.d_stats = (amos_new_points_stats *)(out + bytesNew);
+    q.n_frames = nv; q.n_pairs = nk; q.capacity = (int32_t)cap; q.n_levels = n_levels;
+    if ((rc = stage_flush(m)) != AMOS_OK ||
+        (rc = amos_match_triangulation_batch_device(m, &s, dGeo, dScale, dSigma, n_levels, only_stereo, check_orientation)) != AMOS_OK ||
+        (rc = amos_match_new_points_batch_device(m, &q)) != AMOS_OK) return rc;
+    const uint8_t *h = m->hStage + stage_take(m, bytesNew + bytesStats);
+    AMOS_HIP_CHECK(hipMemcpyAsync((void *)h, out, bytesNew + bytesStats, hipMemcpyDeviceToHost, m->stream));
+    AMOS_HIP_CHECK(hipStreamSynchronize(m->stream));
+    const amos_new_points_stats *st = (const amos_new_points_stats *)(h + bytesNew);
+    for (int i = 0; i < nk; i++) {
+        stats[kept[i]] = st[i];
+        const size_t n = (size_t)std::min(std::max(st[i].n_new, 0), k1->n);
+        if (n) std::memcpy(new_points + (size_t)kept[i] * k1->n, h + sizeof(amos_new_point) * cap * i, sizeof(amos_new_point) * n);
+    }
+    return AMOS_OK;
 }
 
 }  // extern "C"

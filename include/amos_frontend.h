@@ -948,6 +948,109 @@ int amos_match_triangulation(amos_match *m, const struct amos_bow_view *k1, cons
                              const amos_kf_geometry *geometry, const float *scale_factors, const float *level_sigma2, int n_levels,
                              int only_stereo, int check_orientation, int32_t *match12, amos_bow_search_stats *stats);
 
+/* ---------------------------------------------------------------- new map points -------------- */
+
+/* What LocalMapping::CreateNewMapPoints (LocalMapping.cc:313-626) does with the matches of SearchForTriangulation, for the n_pairs
+ * (keyframe-1 slot, keyframe-2 slot) pairs of one search call: per match the parallax of the two rays, the 4 x 4 SVD or
+ * KeyFrame::UnprojectStereo, the two depth signs, the two reprojection gates and the scale-consistency gate (:424-597).  It reads
+ * d_match12 exactly as amos_match_triangulation_batch_device left it on the device: the two calls go to the matcher's stream back to
+ * back, no copy and no synchronisation between them.  What remains on the host is `new MapPoint` and the observation bookkeeping
+ * (:601-623) over the records of d_new.  The arithmetic is amos-slam_amd/csrc/amos_new_points_core.h (its header lists the convention
+ * that fixes each expression, the reference's quirks that are kept and what a NaN does): PARITY WITH THE REFERENCE'S OPENCV-BACKED
+ * ARITHMETIC UNPINNED; what is pinned, bit for bit, is tests/new_points_restatement.py.  The monocular median-depth gate is out of scope.
+ *
+ * Per pair: keyframe-1 features i < min(d_counts[slot 1], capacity) with j = d_match12[pair][i] != -1 are the matches; a j outside
+ * [0, min(d_counts[slot 2], capacity)) is skipped and sets status bit 0.  Every match gets a verdict (AMOS_NEW_POINT_*); an octave
+ * outside [0, n_levels) on either side gets OCTAVE and sets status bit 1 (the reference would index its tables out of range).
+ *
+ * THE CLAIM RULE (where this entry departs from the reference, by definition).  The reference searches neighbour k + 1 after neighbour
+ * k's new points were added to the current keyframe, so a keyframe-1 feature that already produced a point is skipped there; the
+ * one-call search for all neighbours cannot see that.  Here: among the enabled pairs that share a keyframe-1 slot, taken in pair order,
+ * a keyframe-1 feature yields at most ONE point; the winner is the first pair in which its match is accepted (verdict 0, 1 or 2), an
+ * accepted match of that feature in a later pair gets CLAIMED.  The reference's later search would not have visited the feature at all,
+ * which could have freed its keyframe-2 candidate for another feature: the one-call search does not replay that; it is a property of the
+ * merged search.  Two enabled pairs with the same keyframe-2 slot are outside the LocalMapping shape: AMOS_ERR_INVALID.
+ *
+ * Outputs.  d_new[pair][0 .. n_new): the accepted matches of the pair, compact, in ascending idx1 -- the order in which the reference
+ * creates its MapPoints, so mnIds follow it; records at and beyond n_new are NOT written.  d_verdict[pair][0 .. capacity) (may be
+ * NULL): the verdict of feature i, -1 without a match; written over the whole row.  d_stats[pair]: n_matches (the matches with a
+ * verdict), n_new, n_verdict[v] and status.  A pair with enabled[pair] == 0 (the neighbour failed the baseline gate :361-374) writes zero
+ * stats and a row of -1; a pair slot outside [0, n_frames) does the same and sets status bit 2.
+ * TWO launches: k_new_points_solve (256 features x pairs per work-group, the matches compacted so that the lanes that run the Jacobi
+ * are dense, one match per lane) and k_new_points_emit (one work-group per pair: the claim rule, the compaction, the sums). */
+#define AMOS_NEW_POINT_TRIANGULATED 0   /* accepted, from the SVD */
+#define AMOS_NEW_POINT_UNPROJECTED_1 1  /* accepted, UnprojectStereo of keyframe 1 */
+#define AMOS_NEW_POINT_UNPROJECTED_2 2  /* accepted, UnprojectStereo of keyframe 2 */
+#define AMOS_NEW_POINT_LOW_PARALLAX 3   /* the final `else continue` (:499) */
+#define AMOS_NEW_POINT_W_ZERO 4
+#define AMOS_NEW_POINT_BEHIND_1 5
+#define AMOS_NEW_POINT_BEHIND_2 6
+#define AMOS_NEW_POINT_REPROJECTION_1 7
+#define AMOS_NEW_POINT_REPROJECTION_2 8
+#define AMOS_NEW_POINT_DISTANCE_ZERO 9
+#define AMOS_NEW_POINT_SCALE 10
+#define AMOS_NEW_POINT_CLAIMED 11
+#define AMOS_NEW_POINT_OCTAVE 12
+#define AMOS_NEW_POINT_VERDICTS 13
+#define AMOS_NEW_POINTS_BAD_MATCH 1     /* status bits */
+#define AMOS_NEW_POINTS_BAD_OCTAVE 2
+#define AMOS_NEW_POINTS_BAD_SLOT 4
+#define AMOS_NEW_POINTS_MAX_PAIRS 64
+typedef struct amos_kf_camera {         /* per keyframe: 96 bytes */
+    float Rcw[9], tcw[3];               /* GetRotation(), GetTranslation() */
+    float Ow[3];                        /* GetCameraCenter() */
+    float fx, fy, cx, cy, invfx, invfy;
+    float mb, mbf;
+    float scale_factor;                 /* mfScaleFactor */
+} amos_kf_camera;
+typedef struct amos_new_point {         /* 24 bytes */
+    int32_t idx1, idx2;
+    float x, y, z;                      /* x3D */
+    int32_t verdict;                    /* 0, 1 or 2: where x3D came from */
+} amos_new_point;
+typedef struct amos_new_points_stats {  /* 64 bytes */
+    int32_t n_matches, n_new;
+    int32_t n_verdict[AMOS_NEW_POINT_VERDICTS];
+    int32_t status;
+} amos_new_points_stats;
+typedef struct amos_new_points {
+    const amos_keypoint *d_kps;         /* [frames][capacity]: mvKeysUn (the arrays of amos_kf_pair_search) */
+    const amos_keypoint *d_kps_raw;     /* [frames][capacity]: mvKeys (x and y are read, by UnprojectStereo), or NULL = d_kps (rectified input) */
+    const int32_t *d_counts;            /* [frames] */
+    const float *d_u_right;             /* [frames][capacity] or NULL (no feature is stereo) */
+    const float *d_depth;               /* [frames][capacity]: mvDepth; may be NULL when d_u_right is */
+    const int32_t *d_pairs_1, *d_pairs_2; /* [n_pairs] frame slots */
+    const int32_t *d_match12;           /* [n_pairs][capacity]: the search's result, in place */
+    const float *d_scale_factors, *d_level_sigma2; /* [n_levels] */
+    const amos_kf_camera *cameras;      /* host, n_frames entries */
+    const int32_t *pairs_1, *pairs_2;   /* host, [n_pairs]: the slots that d_pairs_1 / d_pairs_2 hold */
+    const uint8_t *enabled;             /* host, [n_pairs]: 0 = the neighbour failed the baseline gate; NULL = all enabled */
+    amos_new_point *d_new;              /* out, [n_pairs][capacity] */
+    int32_t *d_verdict;                 /* out, [n_pairs][capacity], or NULL */
+    amos_new_points_stats *d_stats;     /* out, [n_pairs] */
+    int32_t n_frames, n_pairs, capacity, n_levels; /* n_pairs 1 .. 64, capacity 1 .. 65536, n_levels 1 .. AMOS_MAX_LEVELS */
+} amos_new_points;
+/* Asynchronous on the matcher's stream.  AMOS_ERR_INVALID, before the device is touched, for a NULL handle or argument (d_kps_raw,
+ * d_u_right, d_depth with it, enabled and d_verdict apart), a count out of range, a host pair slot outside [0, n_frames), two enabled
+ * pairs with the same keyframe-2 slot, or a camera of an enabled pair that is not finite or has fx, fy <= 0. */
+int amos_match_new_points_batch_device(amos_match *m, const amos_new_points *s);
+/* LocalMapping::ComputeF12 (:743-779), the epipole of ORBmatcher.cc:818-825 and the stereo / RGB-D baseline gate (:361-374) from the two
+ * keyframes' records: the host compilation of amos_new_points_core.h's pair_geometry.  Returns 1, or 0 when |Ow2 - Ow1| < c2->mb (the
+ * neighbour is skipped; g is written either way), AMOS_ERR_INVALID for a NULL argument. */
+int amos_kf_geometry_from_poses(const amos_kf_camera *c1, const amos_kf_camera *c2, amos_kf_geometry *g);
+/* The host form, synchronous: ONE keyframe 1 against n2 neighbours from host arrays.  Geometry and gate per neighbour
+ * (amos_kf_geometry_from_poses); gated neighbours are dropped from the call, their stats are zero; ONE upload (keyframe 1 staged once),
+ * the search's two launches, the two launches above, ONE download.  cams2, kps_raw2, depth2: n2 entries; kps_raw1 / kps_raw2[v] (the raw
+ * keypoints, NULL = the view's keys) and depth1 / depth2[v] (NULL: allowed for a view without u_right) hold the view's n entries.
+ * new_points holds n2 rows of k1->n records (row v: stats[v].n_new valid ones), stats n2.  AMOS_ERR_INVALID, before the device is
+ * touched, for a NULL argument, n2 outside 1 .. 64, n_levels out of range, a view that amos_match_bow rejects or a stereo view without
+ * depths. */
+int amos_match_new_points(amos_match *m, const struct amos_bow_view *k1, const struct amos_bow_view *const *k2s, int n2,
+                          const amos_kf_camera *cam1, const amos_kf_camera *cams2, const amos_keypoint *kps_raw1,
+                          const amos_keypoint *const *kps_raw2, const float *depth1, const float *const *depth2, const float *scale_factors,
+                          const float *level_sigma2, int n_levels, int only_stereo, int check_orientation, amos_new_point *new_points,
+                          amos_new_points_stats *stats);
+
 /* ---------------------------------------------------------------- loop-closing Sim3 ----------- */
 
 /* Step 2 of LoopClosing::ComputeSim3's candidate loop (LoopClosing.cc:389-447): ORB-SLAM2's Sim3Solver (src/Sim3Solver.cc:48-523: the
